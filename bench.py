@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- self-play throughput of the HIP engine (games/s + MCTS sims/s, 11x11 Hex @ 400 sims).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload selfplay|resnet|tree]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload selfplay|resnet|tree] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline alone: it sets the pool up, warms up, times `--steps` moves and prints the line
+(`value`, `ms_per_step` = milliseconds of one timed move, the roofline of that same run).  Every further leg and side
+measurement described below -- the nested tree-only, configs[4]-shape, product-surface, training-step and train-loop
+legs, the replay exchange, the CPU baselines and the library-GEMM yardstick -- runs only under `--full`.
+`--dump-outputs DIR` writes, after the timed moves, what the timed path left behind as DIR/<name>.npy (float32 /
+float64): the search results at every game's root, every game's state and the play counters of the timed moves.  The
+inputs are seeded (weights, start positions, device RNG), so the same arguments give the same files run to run.
 
 A "step" is one engine move: every one of the `--games` concurrent games runs a full
 400-simulation search ((400//10+1)*10 = 410 select_leaf calls, mcts.py:268), draws its move on
@@ -14,7 +22,7 @@ Default workload = the north-star headline, BASELINE.json configs[2]: 4096 concu
 heads launch pair).  The tree-only sub-benchmark, configs[1] (uniform priors, no net: HBM model of
 SURVEY 8(d)), is measured the same way right after it and nested in the same line as "tree".
 `--workload resnet` / `--workload tree` run one of the two alone (profiling).  Two more legs are nested in the
-default line: "config5" -- BASELINE configs[4]'s shape on this one GPU (13x13, 19x256 resnet, 800 -> 810 sims,
+`--full` line: "config5" -- BASELINE configs[4]'s shape on this one GPU (13x13, 19x256 resnet, 800 -> 810 sims,
 `--c5-games` games, one warm-up and `--c5-steps` timed moves) with its own `roofline` (the wide tower's per-layer MFMA
 kernel) and `cpu_baseline` -- and "api": the product surface the trainer calls (Player.read, parallel_player.py:
 24-28) driven for `--api-moves` engine moves after the pool transplant, rows/s over the last 60 of them beside
@@ -207,6 +215,40 @@ def pool_positions(E):
         seq[0::2], seq[1::2] = xs, os_
         moves.append(seq.tolist())
     return moves
+
+
+# play_steps' work counters (its timings are left out): how many games, plies, simulations and evaluations the timed
+# moves did and what their searches and finished games summed to
+DUMP_COUNTERS = ("positions", "games", "game_errors", "plies", "selects", "evals", "sum_depth", "sum_k_interior",
+                 "sum_k_leaf", "sum_search_value", "sum_root_width", "sum_action_logprob", "sum_reward_last",
+                 "sum_game_length")
+DUMP_BUDGET = 60 << 20       # bytes; above it a fixed, seeded sample of the game slots is written
+
+
+def dump_outputs(E, st, out_dir):
+    """--dump-outputs: what the timed moves computed, as DIR/<name>.npy -- every game's root after the last move
+    (Engine.get_root: child visits / values / priors of the search tree kept for the next move), every game's state
+    (Engine.get_games: board, colour to move, result, ply) and `play_counters` (DUMP_COUNTERS of the timed moves, in
+    that order).  Integer arrays are written as float32 (exact: all below 2^24), counters as float64.  Should the
+    per-game arrays exceed DUMP_BUDGET, a fixed sample of the slots (seeded, sorted) is written; `game_slots` names the
+    slots written either way.  ~10 MB at the headline's 4096 games."""
+    import numpy as np
+    per_game = {"root_" + k: v for k, v in E.get_root().items()}
+    per_game.update({"game_" + k: v for k, v in E.get_games().items()})
+    G = len(per_game["game_ply"])
+    total = sum(4 * v.size for v in per_game.values())
+    slots = np.arange(G)
+    if total > DUMP_BUDGET:
+        keep = max(1, G * DUMP_BUDGET // total)
+        slots = np.sort(np.random.RandomState(0x5EED).choice(G, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in per_game.items():
+        v = v[slots]
+        if v.dtype.kind in "iu":
+            assert np.abs(v).max(initial=0) < (1 << 24), name
+        np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float32))
+    np.save(os.path.join(out_dir, "game_slots.npy"), slots.astype(np.float32))
+    np.save(os.path.join(out_dir, "play_counters.npy"), np.array([float(st[k]) for k in DUMP_COUNTERS], np.float64))
 
 
 def run_workload(workload, args, rank, world, local_rank, steps, warmup, sync, torch):
@@ -853,6 +895,11 @@ def main():
     ap.add_argument("--exchange-plies", type=int, default=0,
                     help="replay exchange after exactly this many further moves of every slot (default: a short top-up "
                          "until the first game finishes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every nested leg and side measurement (tree-only, configs[4] shape, Player.read, "
+                         "training step and loop, replay exchange, CPU baselines, GEMM yardstick); default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed moves, write what they computed (roots, game states, counters) as DIR/<name>.npy")
     args = ap.parse_args()
     headline = "tree" if args.workload == "tree" else "resnet"
     if args.steps is None:
@@ -904,8 +951,10 @@ def main():
     per_rank = rank_report(dist, torch, local_rank, st, elapsed)      # before the max-over-ranks reduction
     elapsed, sums = reduce_over_ranks(dist, torch, elapsed, [float(st[k]) for k in SUM_KEYS])
     E = ex["engine"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(E, st, args.dump_outputs)
     exchange = None
-    if headline == "resnet" and not args.no_replay_exchange:
+    if args.full and headline == "resnet" and not args.no_replay_exchange:
         exchange = replay_exchange(E, dist, torch, local_rank, args.exchange_plies)
     E.close()
 
@@ -950,19 +999,19 @@ def main():
             line["world"]["per_rank"] = per_rank
             line["roofline"].update(world_fields(per_rank, line["value"], exchange, args.ref_n1,
                                                  dist.get_backend() if dist is not None else None))
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 line["box"] = box_calibration(torch)
             except Exception as exc:
                 line["box"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args, headline, ex["net_state"])
             except Exception as exc:  # the oracle is test infrastructure; report, don't fail the bench
                 line["cpu_baseline"] = {"error": repr(exc)}
 
     # ---- nested tree-only sub-benchmark (configs[1]), measured the same way ---------------------
-    nested = args.workload == "selfplay" and (world == 1 or args.all_legs)    # N > 1: eight ranks each settling three engines
+    nested = args.full and args.workload == "selfplay" and (world == 1 or args.all_legs)   # N > 1: eight ranks each settling three engines
     if nested:                                                                # is the slow part of a SCALE run
         st_t, el_t, ex_t = run_workload("tree", args, rank, world, local_rank, args.tree_steps, args.tree_warmup,
                                         sync, torch)
@@ -1018,7 +1067,7 @@ def main():
             line["config5"] = c5
 
     # ---- nested product-surface leg: Player.read for a whole game length -----------------------------------
-    if args.workload == "selfplay" and args.api_moves > 0 and world == 1:
+    if args.full and args.workload == "selfplay" and args.api_moves > 0 and world == 1:
         try:
             api = run_api(args, rank, world, local_rank, ex.get("start"), torch)
             line["api"] = api
@@ -1027,14 +1076,15 @@ def main():
             line["api"] = {"error": repr(exc)}
 
     # ---- nested leg beside the path: the reference's training step on the replay ring, eager and captured ----
-    if args.workload == "selfplay" and not args.no_train_step and world == 1 and (args.board, args.blocks, args.chans) == (11, 6, 64):
+    if (args.full and args.workload == "selfplay" and not args.no_train_step and world == 1
+            and (args.board, args.blocks, args.chans) == (11, 6, 64)):
         try:
             line["train_step"] = run_train_step(args, local_rank, torch)
         except Exception as exc:
             line["train_step"] = {"error": repr(exc)}
 
     # ---- nested leg beside the path: the trainer's loop, refills inline against self-play beside the steps ---------
-    if (args.workload == "selfplay" and not args.no_train_step and args.loop_steps > 0 and world == 1
+    if (args.full and args.workload == "selfplay" and not args.no_train_step and args.loop_steps > 0 and world == 1
             and (args.board, args.blocks, args.chans) == (11, 6, 64)):
         try:
             line["train_loop"] = run_train_loop(args, local_rank)

@@ -1,30 +1,57 @@
 """Checkpoint compatibility: the reference's shipped policy file through
 azalea_amd.Policy.load must give what the reference's own Policy.load gives (golden G8: schema,
-per-tensor digests, forward outputs), and checkpoints written here must load back.  CPU only; the
-file itself is read from the reference tree when it is present (it is not on the GPU box)."""
+per-tensor digests, forward outputs), and checkpoints written here must load back.  CPU only.  The shipped
+file (4 MB) is not part of the repository: AZX_REF_CHECKPOINT may name a copy of it; otherwise the test rebuilds
+the same policy from G8's tensors in that file's layout (see shipped_checkpoint)."""
+import collections
 import hashlib
 import os
 
 import numpy as np
-import pytest
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CKPT = os.environ.get("AZX_REF_CHECKPOINT", "/root/reference/models/hex11-20180712-3362.policy.pth")
+CKPT = os.environ.get("AZX_REF_CHECKPOINT")
 HYPER_TYPES = {"network_type": str, "board_size": int, "num_blocks": int, "base_chans": int,
                "simulations": int, "search_batch_size": int, "exploration_depth": int}
+# the shipped file's SGD settings (optimizer.param_groups[0] of hex11-20180712-3362.policy.pth)
+SHIPPED_SGD = {"lr": 6.560999999999998e-06, "momentum": 0.9, "dampening": 0, "weight_decay": 0.0001,
+               "nesterov": False, "initial_lr": 0.1}
 
 
 def golden():
     return np.load(os.path.join(GOLDEN, "g8_checkpoint.npz"))
 
 
-@pytest.mark.skipif(not os.path.exists(CKPT), reason="reference checkpoint not present on this machine")
-def test_shipped_checkpoint_loads_like_the_reference():
+def shipped_checkpoint(z, path):
+    """The shipped policy file rebuilt from G8 in its layout: the legacy (pre-zip) torch serialisation of
+    {'policy': {'net': the network's parameters and BatchNorm buffers in module order -- no num_batches_tracked, which
+    the torch of 2018 did not keep -- and the eleven hyper-parameters as int / float / str}, 'optimizer': an SGD
+    state_dict with one momentum buffer per parameter}.  G8's tensor digests were taken from the shipped file, so the
+    rebuilt one holds the same tensors bit for bit."""
+    from azalea_amd.network import HexNetwork
+    n, blocks, chans = [int(x) for x in z["cfg"]]
+    order = [k for k in HexNetwork(board_size=n, num_blocks=blocks, base_chans=chans).state_dict()
+             if not k.endswith("num_batches_tracked")]
+    net = collections.OrderedDict((k, torch.tensor(z["w:" + k])) for k in order)
+    policy = {str(k): HYPER_TYPES.get(str(k), float)(str(v)) for k, v in zip(z["hyper_names"], z["hyper_values"])}
+    policy["net"] = net
+    params = [k for k in order if "running_" not in k]
+    optimizer = {"state": {i: {"momentum_buffer": torch.zeros_like(net[k])} for i, k in enumerate(params)},
+                 "param_groups": [dict(SHIPPED_SGD, params=list(range(len(params))))]}
+    torch.save({"policy": policy, "optimizer": optimizer}, path, _use_new_zipfile_serialization=False)
+    return path
+
+
+def test_shipped_checkpoint_loads_like_the_reference(tmp_path):
     from azalea_amd.policy import Policy
     z = golden()
-    assert hashlib.sha256(open(CKPT, "rb").read()).hexdigest() == str(z["file_sha256"])
-    policy = Policy.load(CKPT, device="cpu")
+    if CKPT:
+        path = CKPT
+        assert hashlib.sha256(open(CKPT, "rb").read()).hexdigest() == str(z["file_sha256"])
+    else:
+        path = shipped_checkpoint(z, str(tmp_path / "hex11-20180712-3362.policy.pth"))
+    policy = Policy.load(path, device="cpu")
     for name, want in zip(z["hyper_names"], z["hyper_values"]):
         got = getattr(policy, str(name))
         cast = HYPER_TYPES.get(str(name), float)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +48,7 @@ def _check_common(d, steps, warmup):
 def test_default_line_is_the_selfplay_headline_with_the_tree_numbers_nested():
     """The default workload is the north-star headline (configs[2]: resnet-driven self-play) from a
     de-synchronised pool, with the configs[1] tree-only run nested as "tree"; small sizes here."""
-    d = _run("--steps", "2", "--warmup", "1", "--games", "64", "--sims", "40", "--tree-steps", "6",
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--games", "64", "--sims", "40", "--tree-steps", "6",
              "--tree-warmup", "2", "--board", "7", "--blocks", "1", "--api-moves", "70")
     _check_common(d, 2, 1)
     assert "config5" not in d and "train_step" not in d        # only nested under the 11x11 / 6x64 headline
@@ -80,7 +81,7 @@ def test_default_line_nests_the_config5_shape_with_roofline_and_cpu_baseline():
     """Under the real headline shape (11x11, 6x64) the line also carries BASELINE configs[4]'s shape on one GPU as
     "config5" -- 13x13, 19x256, 810 select_leaf calls, one warm-up + three timed moves -- with its own roofline and
     cpu_baseline (few games here)."""
-    d = _run("--steps", "1", "--warmup", "1", "--games", "32", "--tree-steps", "4", "--tree-warmup", "1",
+    d = _run("--full", "--steps", "1", "--warmup", "1", "--games", "32", "--tree-steps", "4", "--tree-warmup", "1",
              "--c5-games", "8", "--api-moves", "0", "--settle", "30", "--loop-steps", "0")
     _check_common(d, 1, 1)
     assert d["config"]["workload"].startswith("BASELINE configs[2]") and "api" not in d and "train_loop" not in d
@@ -116,7 +117,7 @@ def test_default_line_nests_the_config5_shape_with_roofline_and_cpu_baseline():
 
 
 def test_tree_bench_line():
-    d = _run("--workload", "tree", "--steps", "3", "--warmup", "1", "--games", "256")
+    d = _run("--full", "--workload", "tree", "--steps", "3", "--warmup", "1", "--games", "256")
     _check_common(d, 3, 1)
     assert d["config"]["workload"].startswith("BASELINE configs[1]")
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["peak"] == 8000.0
@@ -127,9 +128,37 @@ def test_tree_bench_line():
 
 
 def test_resnet_bench_line():
-    d = _run("--workload", "resnet", "--steps", "1", "--warmup", "1", "--games", "64", "--sims", "40",
+    d = _run("--full", "--workload", "resnet", "--steps", "1", "--warmup", "1", "--games", "64", "--sims", "40",
              "--no-cpu-baseline", "--desync", "0")
     _check_common(d, 1, 1)
     assert d["config"]["workload"].startswith("BASELINE configs[2]") and "lock-step" in d["config"]["start"]
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["unit"] == "TFLOP/s"
     assert round(d["value"] * d["elapsed_s"]) == 64 * 1 * 50
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_what_it_computed(tmp_path):
+    """Without --full the line is the headline alone (no nested leg, no side measurement), --steps sets the timed
+    moves, and --dump-outputs writes what those moves computed: the same files, bit for bit, from a second run with the
+    same arguments."""
+    args = ("--steps", "3", "--warmup", "1", "--games", "64", "--sims", "40", "--board", "7", "--blocks", "1")
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _run(*args, "--dump-outputs", str(out))
+        assert d["metric"] == "mcts_sims_per_sec" and d["unit"] == "sims/s" and d["value"] > 0
+        assert d["higher_is_better"] is True and isinstance(d["dtype"], str) and d["steps"] == 3 and d["warmup"] == 1
+        assert abs(d["ms_per_step"] - 1e3 * d["elapsed_s"] / 3) < 1e-9 * d["ms_per_step"]
+        assert round(d["value"] * d["elapsed_s"]) == 64 * 3 * 50 and d["plies"] == 64 * 3
+        for leg in ("tree", "config5", "api", "train_step", "train_loop", "box", "cpu_baseline", "replay_allgather"):
+            assert leg not in d, leg
+        files = {p.name[:-4]: np.load(p) for p in out.glob("*.npy")}
+        assert {"root_child_visits", "root_child_prior", "game_board", "game_ply", "game_slots", "play_counters"} <= set(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["root_child_visits"].shape == (64, 49) and files["game_board"].shape == (64, 7, 7)
+        c = dict(zip(bench.DUMP_COUNTERS, files["play_counters"]))
+        assert c["selects"] == 64 * 3 * 50 and c["plies"] == 64 * 3
+        runs.append(files)
+    assert set(runs[0]) == set(runs[1])
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name

@@ -105,7 +105,7 @@ def _bench(args, world):
     if world > 1:      # the driver's launch line; the launcher is a fresh child process (nothing here re-execs)
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port())]
-    cmd += [os.path.join(root, "bench.py"), "--gpus", str(world)] + args
+    cmd += [os.path.join(root, "bench.py"), "--gpus", str(world), "--full"] + args     # the replay exchange
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-3000:]

@@ -24,7 +24,7 @@ PASSES=${@:-stats fetch write sq1 sq2}
 export TMPDIR=/tmp
 # --no-train-step: the training-step leg runs each mode in a CHILD process, which would inherit the profiler's
 # preload and write into the same -d directory (tools/prof_train.sh profiles the training step on its own)
-ARGS="--steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline --api-moves 0 --no-train-step ${EXTRA:-}"
+ARGS="--full --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline --api-moves 0 --no-train-step ${EXTRA:-}"
 C5="--workload resnet --board 13 --blocks 19 --chans 256 --sims 200 --games ${C5GAMES:-512} --steps 1 --warmup 0 --no-cpu-baseline --no-replay-exchange --no-train-step"
 pmc() {   # name, counters...
   local name=$1; shift
