@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -93,13 +94,23 @@ struct azx_engine {
     int32_t *cidx_maxk = nullptr;
     // timing
     std::vector<hipEvent_t> ev_pool;
-    std::vector<char> ev_tag;           // 0 = tree kernel, 1 = network (tower + heads)
+    std::vector<char> ev_tag;           // 0 = tree kernel, 1 = network (tower + heads), 2 = reference mark (not booked)
     std::vector<int> ev_weight;         // moves covered by the timed launch (k_play: several)
+    // pipelined play: the two half-pools' launches of one phase share a group id (> 0) and count as ONE launch; their
+    // time is the union of the grouped launches' spans (read against the reference mark ev_ref, recorded before them):
+    // the device time during which such launches were running
+    std::vector<int> ev_group, ev_ref;
+    int ev_groups = 0;
     size_t ev_used = 0;
     AzxNet *net = nullptr;
     // diagnostic switches, read once at azx_create (azx_kernel_info reports them)
     bool force_generic = false;         // AZX_MCTS_GENERIC: every tree launch on the generic instantiation
     bool no_persistent = false;         // AZX_NO_PERSISTENT: per-move launches instead of k_play
+    bool pipeline = true;               // AZX_PIPELINE=0: the resnet play loop on one stream (no half-pools)
+    // pipelined play: the second half-pool's stream, made on first use on the engine stream's CU mask
+    hipStream_t stream_b = nullptr;
+    std::vector<uint32_t> cu_mask;      // azx_reserve_cus's mask (empty = all CUs)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int64_t dbg_qcap = 0;               // azx_debug_set_queue_cap
 };
 
@@ -171,6 +182,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     e->cfg = *cfg;
     { const char *v = getenv("AZX_MCTS_GENERIC"); e->force_generic = v && atoi(v) != 0; }
     { const char *v = getenv("AZX_NO_PERSISTENT"); e->no_persistent = v && atoi(v) != 0; }
+    { const char *v = getenv("AZX_PIPELINE"); e->pipeline = !(v && atoi(v) == 0); }
     HIPCHECK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     DevEngine &d = e->d;
     memset(&d, 0, sizeof d);
@@ -185,6 +197,8 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     d.seed = cfg->seed;
     d.uid_stride = std::max(1, cfg->game_index_stride);
     d.uid_offset = cfg->game_index_offset;
+    d.slot_base = 0;
+    d.pool_games = d.G;
     d.noise_alpha = (float)cfg->noise_alpha;
     d.noise_scale = 0.0;
     d.exploration_depth = cfg->exploration_depth;
@@ -211,7 +225,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.leaf_node, E); A(d.leaf_len, E); A(d.leaf_eval, E); A(d.leaf_link, E); A(d.leaf_cells, E);
     A(d.leaf_mask, E * 4); A(d.path, E * pstride);
     A(d.ev_board, E * AZX_CELL_STRIDE); A(d.ev_src, E); A(d.ev_flip, E);
-    A(d.ev_value, E); A(d.ev_prior, E * AZX_CELL_STRIDE); A(d.n_eval, 4);
+    A(d.ev_value, E); A(d.ev_prior, E * AZX_CELL_STRIDE); A(d.n_eval, 4);   // (n_eval[1]: the second half-pool's count)
     A(d.counters, G * CTR_COUNT); A(d.q_count, 2); A(d.stat_sums, G * 8);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
@@ -261,6 +275,9 @@ extern "C" void azx_destroy(azx_engine *e) {
     if (e->export_board) (void)hipFree(e->export_board);
     if (e->export_prob) (void)hipFree(e->export_prob);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
+    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
+    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+    if (e->stream_b) { (void)hipStreamSynchronize(e->stream_b); (void)hipStreamDestroy(e->stream_b); }
     for (int i = 0; i < 8; ++i) {
         if (e->cidx_ev[i]) { (void)hipEventSynchronize(e->cidx_ev[i]); (void)hipEventDestroy(e->cidx_ev[i]); }
         if (e->cidx_host[i]) (void)hipHostFree(e->cidx_host[i]);
@@ -297,6 +314,12 @@ extern "C" int azx_reserve_cus(azx_engine *e, int cus_per_xcd, int *reserved_out
     e->stream = fresh;
     if (e->net) azx_net_set_stream(e->net, fresh, per ? mask.data() : nullptr, per ? words : 0);
     (void)hipStreamDestroy(old);
+    if (e->stream_b) {      // the second half-pool's stream is made again, on the new mask, at its next use
+        (void)hipStreamSynchronize(e->stream_b);
+        (void)hipStreamDestroy(e->stream_b);
+        e->stream_b = nullptr;
+    }
+    e->cu_mask.assign(mask.begin(), per ? mask.end() : mask.begin());
     e->reserved_cus = per * xcds;
     if (!e->cidx_maxk) TRY(dev_alloc(e, &e->cidx_maxk, 4));     // (so that the trainer's thread never allocates beside a play)
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -304,11 +327,62 @@ extern "C" int azx_reserve_cus(azx_engine *e, int cus_per_xcd, int *reserved_out
     return AZX_OK;
 }
 
+// ---- pipelined play: two half-pools -----------------------------------------------------------
+// The resnet play loop can run the pool as two halves, slots [0, G/2) and [G/2, G), each on its own stream: one
+// half's search phases and its tower launches' ramp and tail overlap the other half's tower.  The games
+// are independent (the device RNG is keyed by the global game index, each tower row depends on its own board alone),
+// so the halves compute what the one-stream loop computes.
+static bool use_pipeline(const azx_engine *e) {
+    return e->pipeline && e->d.evaluator == AZX_EVAL_RESNET && e->d.G % 2 == 0 && e->d.G >= 1024 &&
+           azx_net_rows_splittable(e->net);
+}
+
+// DevEngine over slots [base, base + n): every per-slot array offset by `base` slots, the evaluation queue the
+// matching part of ev_* with its own count `n_eval`; the pool-wide harvest queue (q_*, q_count) stays shared
+static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval) {
+    DevEngine v = d;
+    const size_t b = (size_t)base, bs = (size_t)d.bs, nc = (size_t)d.ncells, pstride = nc + (nc & 1);
+    v.G = n;
+    v.slot_base = d.slot_base + base;
+    v.cells += b * d.slots * 64;
+    v.ghdr += b;
+    v.thdr += b;
+    v.arena[0] += b * d.cap;
+    v.arena[1] += b * d.cap;
+    v.leaf_node += b * bs; v.leaf_len += b * bs; v.leaf_eval += b * bs; v.leaf_link += b * bs; v.leaf_cells += b * bs;
+    v.leaf_mask += b * bs * 4;
+    v.path += b * bs * pstride;
+    v.ev_board += b * bs * AZX_CELL_STRIDE;
+    v.ev_src += b * bs;
+    v.ev_flip += b * bs;
+    v.ev_value += b * bs;
+    v.ev_prior += b * bs * AZX_CELL_STRIDE;
+    v.n_eval = n_eval;
+    if (v.noise) v.noise += b * d.n_select * d.noise_stride;
+    v.counters += b * CTR_COUNT;
+    v.stat_sums += b * 8;
+    if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
+    if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
+    if (v.row_k) v.row_k += b * nc;
+    if (v.row_meta) v.row_meta += b * nc * AZX_ROW_METRICS;
+    return v;
+}
+
+static int pipeline_streams(azx_engine *e) {
+    if (!e->stream_b) {
+        if (e->cu_mask.empty()) HIPCHECK(hipStreamCreateWithFlags(&e->stream_b, hipStreamNonBlocking));
+        else HIPCHECK(hipExtStreamCreateWithCUMask(&e->stream_b, (uint32_t)e->cu_mask.size(), e->cu_mask.data()));
+    }
+    if (!e->ev_fork) HIPCHECK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+    if (!e->ev_join) HIPCHECK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+    return AZX_OK;
+}
+
 extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
     if (!e || !buf || cap < 1) return fail(AZX_EINVAL, "null argument");
     const DevEngine &d = e->d;
     const int S = d.slots <= 2 ? 2 : 3;
-    char tree[96], play[96];
+    char tree[96], play[128];
     if (d.evaluator == AZX_EVAL_UNIFORM || d.evaluator == AZX_EVAL_UNIFORM_HASH) {
         // the FAST instantiation also needs the default prior table and device (or no) noise: decided per launch
         DevEngine probe = d;
@@ -319,12 +393,14 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                                                                        : "k_mcts + k_choose + k_advance per move");
     } else {
         snprintf(tree, sizeof tree, "k_mcts<%d,generic> (BEGIN / APPLY|SELECT / APPLY phases)", S);
-        snprintf(play, sizeof play, "phases + k_choose + k_advance per move");
+        snprintf(play, sizeof play, "%s", use_pipeline(e) ? "phases + k_choose + k_advance per move, two half-pools on two streams"
+                                                          : "phases + k_choose + k_advance per move, one stream");
     }
     std::string text = std::string("tree=") + tree + "; play=" + play + "; net=" +
                        (e->net ? azx_net_kernel_info(e->net) : "none") +
                        "; switches: AZX_MCTS_GENERIC=" + (e->force_generic ? "1" : "0") +
                        " AZX_NO_PERSISTENT=" + (e->no_persistent ? "1" : "0") +
+                       " AZX_PIPELINE=" + (e->pipeline ? "1" : "0") +
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
@@ -418,7 +494,7 @@ extern "C" int azx_reset(azx_engine *e, const int32_t *slots, int n_slots, const
 }
 
 // ---- timing of the tree kernels (roofline: algorithmic bytes / measured launch time) --------
-static void time_begin(azx_engine *e, char tag = 0) {
+static void time_begin(azx_engine *e, char tag = 0, hipStream_t s = nullptr, int group = 0, int ref = -1) {
     if (e->ev_used + 2 > e->ev_pool.size()) {
         if (e->ev_pool.size() >= 1 << 16) return;
         hipEvent_t a, b;
@@ -426,31 +502,71 @@ static void time_begin(azx_engine *e, char tag = 0) {
         e->ev_pool.push_back(a);
         e->ev_pool.push_back(b);
     }
-    if (e->ev_tag.size() < e->ev_pool.size() / 2) e->ev_tag.resize(e->ev_pool.size() / 2, 0);
-    e->ev_tag[e->ev_used / 2] = tag;
-    if (e->ev_weight.size() < e->ev_pool.size() / 2) e->ev_weight.resize(e->ev_pool.size() / 2, 1);
-    e->ev_weight[e->ev_used / 2] = 1;
-    (void)hipEventRecord(e->ev_pool[e->ev_used], e->stream);
+    const size_t n = e->ev_pool.size() / 2, i = e->ev_used / 2;
+    if (e->ev_tag.size() < n) { e->ev_tag.resize(n, 0); e->ev_weight.resize(n, 1); e->ev_group.resize(n, 0); e->ev_ref.resize(n, -1); }
+    e->ev_tag[i] = tag;
+    e->ev_weight[i] = 1;
+    e->ev_group[i] = ref >= 0 ? group : 0;
+    e->ev_ref[i] = ref;
+    (void)hipEventRecord(e->ev_pool[e->ev_used], s ? s : e->stream);
 }
-static void time_end(azx_engine *e, int weight = 1) {
+// (on the stream time_begin recorded on: a pipelined launch is timed on its half-pool's stream)
+static void time_end(azx_engine *e, int weight = 1, hipStream_t s = nullptr) {
     if (e->ev_used + 2 > e->ev_pool.size()) return;     // pool full: time_begin recorded nothing either
-    (void)hipEventRecord(e->ev_pool[e->ev_used + 1], e->stream);
+    (void)hipEventRecord(e->ev_pool[e->ev_used + 1], s ? s : e->stream);
     e->ev_weight[e->ev_used / 2] = weight;
     e->ev_used += 2;
 }
+// a reference mark on stream s for grouped launches issued after it (its pool index, -1 when the pool is full)
+static int time_mark(azx_engine *e, hipStream_t s) {
+    time_begin(e, 2, s);
+    if (e->ev_used + 2 > e->ev_pool.size()) return -1;
+    const int ref = (int)e->ev_used;
+    time_end(e, 1, s);
+    return ref;
+}
 static void time_collect(azx_engine *e, azx_play_stats *st) {
-    for (size_t i = 0; i + 1 < e->ev_used; i += 2) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e->ev_pool[i], e->ev_pool[i + 1]) == hipSuccess) {
-            if (e->ev_tag[i / 2]) { st->net_seconds += ms * 1e-3; st->net_launches += 1; }
-            else {
-                st->mcts_seconds += ms * 1e-3;
-                st->mcts_launches += e->ev_weight[i / 2];
-                st->mcts_kernel_launches += 1;
-            }
+    auto book = [&](char tag, int weight, double seconds, int launches) {
+        if (tag == 1) { st->net_seconds += seconds; st->net_launches += launches; }
+        else {
+            st->mcts_seconds += seconds;
+            st->mcts_launches += weight * launches;
+            st->mcts_kernel_launches += launches;
         }
+    };
+    std::map<int, char> groups;                                      // group id -> tag (one launch each)
+    std::map<std::pair<int, char>, std::vector<std::pair<float, float>>> spans;   // (reference, tag) -> spans (ms)
+    for (size_t i = 0; i + 1 < e->ev_used; i += 2) {
+        const size_t k = i / 2;
+        if (e->ev_tag[k] == 2) continue;
+        float ms = 0.f;
+        if (!e->ev_group[k]) {
+            if (hipEventElapsedTime(&ms, e->ev_pool[i], e->ev_pool[i + 1]) == hipSuccess)
+                book(e->ev_tag[k], e->ev_weight[k], ms * 1e-3, 1);
+            continue;
+        }
+        float b = 0.f, en = 0.f;
+        const hipEvent_t ref = e->ev_pool[e->ev_ref[k]];
+        if (hipEventElapsedTime(&b, ref, e->ev_pool[i]) != hipSuccess || hipEventElapsedTime(&en, ref, e->ev_pool[i + 1]) != hipSuccess)
+            continue;
+        groups[e->ev_group[k]] = e->ev_tag[k];
+        spans[{e->ev_ref[k], e->ev_tag[k]}].push_back({b, en});
+    }
+    for (const auto &g : groups) book(g.second, 1, 0.0, 1);
+    for (auto &kv : spans) {
+        std::vector<std::pair<float, float>> &v = kv.second;
+        std::sort(v.begin(), v.end());
+        double total = 0.0;
+        float lo = v[0].first, hi = v[0].second;
+        for (const auto &iv : v) {
+            if (iv.first > hi) { total += hi - lo; lo = iv.first; hi = iv.second; }
+            else hi = std::max(hi, iv.second);
+        }
+        total += hi - lo;
+        book(kv.first.second, 1, total * 1e-3, 0);
     }
     e->ev_used = 0;
+    e->ev_groups = 0;
 }
 
 static int upload_noise(azx_engine *e, const double *noise, int n_select, int noise_stride,
@@ -949,6 +1065,53 @@ static int enqueue_ply(azx_engine *e) {
     return AZX_OK;
 }
 
+// `plies` moves of the resnet play loop as two half-pools (use_pipeline): half A on the engine stream, half B on
+// stream_b.  Each half's phases follow each other on its own stream only; the host issues them phase by phase,
+// alternating the halves, so that one half's tower is queued while the other half runs its search phases.  Half B
+// starts after half A's first tree launch (everything queued on the engine stream before it included), which puts the
+// halves one phase apart from the start; the engine stream waits for half B at the end.
+static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
+    TRY(pipeline_streams(e));
+    if (!azx_net_ready(e->net)) return fail(AZX_ESTATE, "azx_set_weights has not been called");
+    const DevEngine &d = e->d;
+    const int half = d.G / 2, rows = half * d.bs;
+    const DevEngine hv[2] = {pool_view(d, 0, half, d.n_eval), pool_view(d, half, half, d.n_eval + 1)};
+    const hipStream_t hs[2] = {e->stream, e->stream_b};
+    const int nb = e->num_batches;
+    // the launch statistics count one phase's two half-pool launches as one launch of the whole pool
+    const int ref = time_mark(e, hs[0]);
+    for (int64_t p = 0; p < plies; ++p) {
+        // phase 0: BEGIN; phases 1..nb: APPLY|SELECT; each followed by the half's network evaluation
+        for (int ph = 0; ph <= nb; ++ph) {
+            const int g_tree = ++e->ev_groups, g_net = ++e->ev_groups;
+            for (int h = 0; h < 2; ++h) {
+                HIPCHECK(hipMemsetAsync(hv[h].n_eval, 0, sizeof(int32_t), hs[h]));
+                time_begin(e, 0, hs[h], g_tree, ref);
+                azx_launch_mcts(hv[h], ph ? MODE_APPLY | MODE_SELECT : MODE_BEGIN, nb, hs[h], e->force_generic);
+                time_end(e, 1, hs[h]);
+                if (p == 0 && ph == 0 && h == 0) {
+                    HIPCHECK(hipEventRecord(e->ev_fork, hs[0]));
+                    HIPCHECK(hipStreamWaitEvent(hs[1], e->ev_fork, 0));
+                }
+                time_begin(e, 1, hs[h], g_net, ref);
+                azx_net_eval_rows(e->net, hv[h], h * rows, rows, hs[h]);
+                time_end(e, 1, hs[h]);
+            }
+        }
+        const int g_tree = ++e->ev_groups;
+        for (int h = 0; h < 2; ++h) {
+            time_begin(e, 0, hs[h], g_tree, ref);
+            azx_launch_mcts(hv[h], MODE_APPLY, nb, hs[h], e->force_generic);
+            time_end(e, 1, hs[h]);
+            azx_launch_choose(hv[h], hs[h]);
+            azx_launch_advance(hv[h], nullptr, 1, hs[h]);
+        }
+    }
+    HIPCHECK(hipEventRecord(e->ev_join, hs[1]));
+    HIPCHECK(hipStreamWaitEvent(hs[0], e->ev_join, 0));
+    return AZX_OK;
+}
+
 extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stats) {
     if (!e || !stats) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -976,7 +1139,8 @@ extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stat
             time_end(e, n);
             p += n;
         }
-        for (; p < plies; ++p) TRY(enqueue_ply(e));
+        if (p < plies && use_pipeline(e)) TRY(enqueue_plies_pipelined(e, plies - p));
+        else for (; p < plies; ++p) TRY(enqueue_ply(e));
     }
     HIPCHECK(hipEventRecord(t1, e->stream));
     HIPCHECK(hipGetLastError());
@@ -1024,7 +1188,8 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
             time_end(e, chunk);
             p += chunk;
         } else {
-            TRY(enqueue_ply(e));
+            if (use_pipeline(e)) TRY(enqueue_plies_pipelined(e, 1));
+            else TRY(enqueue_ply(e));
             p += 1;
         }
         HIPCHECK(hipMemcpyAsync(&rows, d.q_count, sizeof rows, hipMemcpyDeviceToHost, e->stream));

@@ -104,6 +104,8 @@ struct DevEngine {
     int32_t device_noise;
     uint64_t seed;
     int32_t uid_stride, uid_offset;   // uid = (slot + G * gen) * uid_stride + uid_offset (azx_config.game_index_*)
+    int32_t slot_base, pool_games;    // a view of slots [slot_base, slot_base + G) of a pool of pool_games (the pipelined
+                                      // schedule's half-pools): the uid above is taken with slot_base + g and pool_games
     const float *prior_by_k;   // [ncells+1]
     int32_t prior_default;     // 1: prior_by_k is the default float32 1/k table
     unsigned long long *counters;   // [G][CTR_COUNT] per-game (no atomics); the host sums over games

@@ -106,7 +106,7 @@ __device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1
 // global index of the gen-th game slot g starts (seeds come from the global game index, so
 // a fixed seed plays the same set of games on 1, 2 or 8 GPUs -- rank r of W passes stride W, offset r)
 __device__ __forceinline__ int64_t game_uid(const DevEngine &E, int g, int gen) {
-    return ((int64_t)g + (int64_t)E.G * gen) * E.uid_stride + E.uid_offset;
+    return ((int64_t)(E.slot_base + g) + (int64_t)E.pool_games * gen) * E.uid_stride + E.uid_offset;
 }
 __device__ __forceinline__ Philox game_rng(const DevEngine &E, int64_t uid) {
     Philox ph;

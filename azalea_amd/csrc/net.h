@@ -23,6 +23,11 @@ int azx_net_debug_weights(AzxNet *net, int which, void *out, int64_t cap, int64_
 const char *azx_net_kernel_info(const AzxNet *net);   // which tower / heads kernels this net launches
 // evaluate the packed requests ev_board[0 .. *d.n_eval) -> ev_value, ev_prior (by original cell)
 void azx_net_eval(AzxNet *net, const DevEngine &d, hipStream_t st);
+// the same for a view of part of the pool (d's ev_* and n_eval point at that part's queue, of at most max_n requests),
+// on scratch rows [row0, row0 + max_n): calls on disjoint row ranges may overlap on different streams -- when
+// azx_net_rows_splittable (every tower but the wide one, whose layer launches run on side streams of their own)
+bool azx_net_rows_splittable(const AzxNet *net);
+void azx_net_eval_rows(AzxNet *net, const DevEngine &d, int row0, int max_n, hipStream_t st);
 // Network.run on host arrays (network.py:87-105): value[B], moves_logprob[B][K]
 int azx_net_forward_host(AzxNet *net, int B, int K, const int32_t *boards,
                          const int32_t *legal_moves, float *value, float *logprob, hipStream_t st);

@@ -1915,18 +1915,25 @@ void azx_net_destroy(AzxNet *net) {
 bool azx_net_ready(const AzxNet *net) { return net && net->ready; }
 
 
-// tower + heads over boards[0 .. n) (n read from n_eval_ptr on the device when given)
+// tower + heads over boards[0 .. n) (n read from n_eval_ptr on the device when given).  The scratch rows used are
+// [row0, row0 + max_n) of the net's buffers, so that two calls on disjoint row ranges may run at the same time on two
+// streams (the pipelined play schedule's half-pools); the wide tower's buffers are not split (row0 must be 0 there).
 static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, const int32_t *n_eval_ptr,
-                    int n_host, int max_n, float *logit, float *value, float *prior, hipStream_t st) {
+                    int n_host, int max_n, float *logit, float *value, float *prior, hipStream_t st, size_t row0 = 0) {
     const NetDev &d = net->d;
     if (max_n <= 0) return;
+    const size_t act_rows = row0 * d.ncells * d.C;
+    float *const act = net->act + act_rows;
+    float *const act2 = net->act2 ? net->act2 + act_rows : nullptr;
+    float *const act3 = net->act3 ? net->act3 + act_rows : nullptr;
+    float *const hfeat_rows = net->hfeat ? net->hfeat + row0 * 6 * d.ncells : nullptr;
     const float *hfeat = nullptr;    // set when the tower kernel already produced the heads' conv planes
     if (net->use_mfma) {
         const size_t lds = net->lds_bytes;
         if (net->tower_variant == 4) {
             const dim3 grid((max_n + F16X3_BPB - 1) / F16X3_BPB), block(F16X3_BPB * 128);
-            hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, net->hfeat);
-            hfeat = net->hfeat;
+            hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, hfeat_rows);
+            hfeat = hfeat_rows;
         } else if (net->tower_variant == 5) {
             const dim3 grid(max_n, d.C / 128), block(256);
             hipLaunchKernelGGL(k_stem_wide_f16x3, grid, block, 0, st, d, boards, net->wideX,
@@ -1975,23 +1982,23 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
                 }
             }
         } else if (net->tower_variant == 1) {
-            hipLaunchKernelGGL((k_tower_mfma<64, 4, 2, 1, 2>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, net->act);
+            hipLaunchKernelGGL((k_tower_mfma<64, 4, 2, 1, 2>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
         } else if (net->tower_variant == 2) {
-            hipLaunchKernelGGL((k_tower_mfma<64, 6, 1, 2, 2>), dim3(max_n), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, net->act);
+            hipLaunchKernelGGL((k_tower_mfma<64, 6, 1, 2, 2>), dim3(max_n), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
         } else {
-            hipLaunchKernelGGL((k_tower_mfma<32, 6, 2, 2, 1>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, net->act);
+            hipLaunchKernelGGL((k_tower_mfma<32, 6, 2, 2, 1>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
         }
     } else {
         const int grid = 2048;
-        hipLaunchKernelGGL(k_stem_generic, dim3(grid), dim3(256), 0, st, d, boards, n_eval_ptr, n_host, net->act);
-        float *x = net->act, *y = net->act2, *z = net->act3;
+        hipLaunchKernelGGL(k_stem_generic, dim3(grid), dim3(256), 0, st, d, boards, n_eval_ptr, n_host, act);
+        float *x = act, *y = act2, *z = act3;
         for (int b = 0; b < d.blocks; ++b) {
             hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b, x, (const float *)nullptr, n_eval_ptr, n_host, y);
             hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b + 1, y, x, n_eval_ptr, n_host, z);
             std::swap(x, z);
         }
-        if (x != net->act)   // heads read net->act
-            (void)hipMemcpyAsync(net->act, x, (size_t)max_n * d.ncells * d.C * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (x != act)   // heads read act
+            (void)hipMemcpyAsync(act, x, (size_t)max_n * d.ncells * d.C * sizeof(float), hipMemcpyDeviceToDevice, st);
     }
     if (hfeat != nullptr && net->opt_heads_mfma && d.ncells <= 128) {
         // the fused tower left the six head planes: the FC layers run as fp32 MFMA GEMMs over tiles of 32 boards
@@ -2000,7 +2007,7 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
     } else {
         const size_t hl = ((size_t)(6 * d.ncells + 64) * HEADS_BPB + (size_t)HEADS_BPB * AZX_CELL_STRIDE +
                            (size_t)(HEADS_KSPLIT - 1) * (64 + 192) * HEADS_BPB) * sizeof(float);
-        hipLaunchKernelGGL(k_heads, dim3((max_n + HEADS_BPB - 1) / HEADS_BPB), dim3(192 * HEADS_KSPLIT), hl, st, d, net->act, hfeat, boards, flip, n_eval_ptr, n_host, logit, value, prior);
+        hipLaunchKernelGGL(k_heads, dim3((max_n + HEADS_BPB - 1) / HEADS_BPB), dim3(192 * HEADS_KSPLIT), hl, st, d, act, hfeat, boards, flip, n_eval_ptr, n_host, logit, value, prior);
     }
 }
 
@@ -2022,6 +2029,13 @@ int azx_net_check_range(AzxNet *net, hipStream_t st) {
 
 void azx_net_eval(AzxNet *net, const DevEngine &e, hipStream_t st) {
     run_net(net, e.ev_board, e.ev_flip, e.n_eval, 0, net->max_evals, net->logit, e.ev_value, e.ev_prior, st);
+}
+
+bool azx_net_rows_splittable(const AzxNet *net) { return net && !(net->use_mfma && net->tower_variant == 5); }
+
+void azx_net_eval_rows(AzxNet *net, const DevEngine &e, int row0, int max_n, hipStream_t st) {
+    run_net(net, e.ev_board, e.ev_flip, e.n_eval, 0, max_n, net->logit + (size_t)row0 * AZX_CELL_STRIDE, e.ev_value,
+            e.ev_prior, st, (size_t)row0);
 }
 
 int azx_net_forward_host(AzxNet *net, int B, int K, const int32_t *boards, const int32_t *legal_moves,
