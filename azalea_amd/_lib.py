@@ -23,6 +23,7 @@ def record_bytes(cells):
 
 EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH, EVAL_EXTERNAL = 0, 1, 2, 3
 FLAG_NO_COMPACT = 1
+EEXTERNAL = -7           # AZX_EEXTERNAL: the registered external evaluator failed or produced a bad row
 
 
 class AzxError(RuntimeError):
@@ -60,6 +61,9 @@ _u64p = C.POINTER(C.c_uint64)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
+
+# azx_eval_fn (include/azx.h): user, n, kmax, board_dev, legal_moves_dev, value_dev, prior_dev, hip_stream
+EVAL_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp)
 
 # every symbol include/azx.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -111,6 +115,7 @@ SYMBOLS = {
     "azx_kernel_info": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "azx_debug_set_queue_cap": (C.c_int, [_vp, C.c_int64]),
     "azx_stream": (_vp, [_vp]),
+    "azx_set_external_evaluator": (C.c_int, [_vp, _vp, _vp]),   # fn passed as a pointer (NULL = unregister)
 }
 
 class TrainConfig(C.Structure):

@@ -21,6 +21,7 @@
 #include "net.h"
 #include "train.h"
 #include "replay_kernels.h"
+#include "ext_kernels.h"
 
 #ifndef AZX_SRC_SHA
 #define AZX_SRC_SHA "unknown"      // the Makefile passes the digest of the kernel sources (profiles are keyed to it)
@@ -70,6 +71,14 @@ struct azx_engine {
     int ext_batches_done = 0;
     std::vector<int> ext_order;                 // eval indices sorted by (slot, leaf)
     std::vector<std::vector<int>> ext_cells;    // original legal cells per sorted entry
+    // registered device evaluator (azx_set_external_evaluator): the hand-over buffers, the last host read of
+    // ext.info, and the slots a failed evaluation left with half-done searches (refused until azx_reset)
+    azx_eval_fn ext_fn = nullptr;
+    void *ext_user = nullptr;
+    ExtBufs ext = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int32_t ext_info[4] = {0, 0, AZX_EXT_NO_ERROR, 0};
+    std::vector<char> ext_dirty;
+    bool ext_failed = false;
     // play mode
     bool play_ready = false;
     int64_t q_alloc = 0;
@@ -152,7 +161,7 @@ struct DevGuard {
     } while (0)
 
 extern "C" const char *azx_last_error(void) { return g_err.c_str(); }
-extern "C" int azx_version(void) { return 5; }   // 5: AZX_ERANGE, azx_debug_weights, device-side weight pack
+extern "C" int azx_version(void) { return 7; }   // 7: azx_set_external_evaluator, AZX_EEXTERNAL (include/azx.h)
 
 extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     if (!cfg || !out) return fail(AZX_EINVAL, "null argument");
@@ -490,6 +499,10 @@ extern "C" int azx_reset(azx_engine *e, const int32_t *slots, int n_slots, const
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(e->stream));
     e->ext_active = false;
+    if (e->ext_failed) {
+        for (int i = 0; i < n_slots; ++i) e->ext_dirty[slots ? slots[i] : i] = 0;
+        e->ext_failed = std::find(e->ext_dirty.begin(), e->ext_dirty.end(), 1) != e->ext_dirty.end();
+    }
     return AZX_OK;
 }
 
@@ -597,9 +610,127 @@ static int upload_noise(azx_engine *e, const double *noise, int n_select, int no
     return AZX_OK;
 }
 
-// one whole search on the stream (no host sync) for the device-side evaluators
+// ---- registered external evaluator (azx_set_external_evaluator) ------------------------------------------------
+static bool ext_registered(const azx_engine *e) { return e->d.evaluator == AZX_EVAL_EXTERNAL && e->ext_fn; }
+
+static int ext_refuse(const azx_engine *e) {
+    if (!e->ext_failed) return AZX_OK;
+    return fail(AZX_ESTATE, "an external evaluation failed and left searches half done: azx_reset every slot first");
+}
+
+// a failed hand-over: the slots' searches stop where they are; nothing queued is waited for by a later call
+static int ext_fail(azx_engine *e, const char *fmt, ...) {
+    char buf[768];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (void)hipStreamSynchronize(e->stream);
+    const int32_t clear = AZX_EXT_NO_ERROR;
+    (void)hipMemcpyAsync(e->ext.info + 2, &clear, sizeof clear, hipMemcpyHostToDevice, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+    e->ext_info[2] = clear;
+    e->ext_active = false;
+    e->ev_used = 0;                       // the timed launches of the failed call are not booked
+    e->ev_groups = 0;
+    e->ext_failed = true;
+    std::fill(e->ext_dirty.begin(), e->ext_dirty.end(), 1);
+    return fail(AZX_EEXTERNAL, "%s", buf);
+}
+
+// what k_ext_import found wrong with the first bad row since the last read (ext_info[2])
+static int ext_check_rows(azx_engine *e) {
+    const int32_t w = e->ext_info[2];
+    if (w == AZX_EXT_NO_ERROR) return AZX_OK;
+    const int row = w >> 3, what = w & 7;
+    return ext_fail(e, "external evaluator: row %d of its batch %s", row,
+                    (what & 1) ? "has a value that is not finite"
+                    : (what & 2) ? "has a negative (or NaN) prior probability"
+                                 : "has prior probabilities whose sum is not 1 within 1e-4 (mcts.py:211-213)");
+}
+
+static int ext_read_info(azx_engine *e) {
+    HIPCHECK(hipMemcpyAsync(e->ext_info, e->ext.info, sizeof e->ext_info, hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return ext_check_rows(e);
+}
+
+// One evaluation point of the phase loop, where the resnet path calls azx_net_eval: the pending requests in
+// (slot, leaf) order out to the caller's buffers, the callback, the checked results back into ev_*.  One host
+// sync per point reads n, kmax and the previous import's error word together.
+static int ext_eval(azx_engine *e, bool timed) {
+    DevEngine &d = e->d;
+    if (timed) time_begin(e, 1);
+    azx_launch_ext_order(d, e->ext, e->stream);
+    HIPCHECK(hipGetLastError());
+    const int rc_info = ext_read_info(e);
+    if (rc_info) return rc_info;
+    const int n = e->ext_info[0], kmax = e->ext_info[1];
+    if (n < 0 || n > d.G * d.bs) return ext_fail(e, "external evaluator: %d pending rows (internal error)", n);
+    if (n > 0) {
+        azx_launch_ext_export(d, e->ext, n, e->stream);
+        HIPCHECK(hipGetLastError());
+        const int rc = e->ext_fn(e->ext_user, n, kmax, e->ext.board, e->ext.legal, e->ext.value, e->ext.prior,
+                                 (void *)e->stream);
+        if (rc) return ext_fail(e, "external evaluator returned %d on a batch of %d rows", rc, n);
+        azx_launch_ext_import(d, e->ext, n, e->stream);
+        HIPCHECK(hipGetLastError());
+    }
+    if (timed) time_end(e);
+    return AZX_OK;
+}
+
+extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *user) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    ENGINE_GUARD(e);
+    if (e->d.evaluator != AZX_EVAL_EXTERNAL)
+        return fail(AZX_EINVAL, "an external evaluator needs an AZX_EVAL_EXTERNAL engine (this one has evaluator %d)",
+                    e->d.evaluator);
+    if (fn && !e->ext.info) {
+        const size_t E = (size_t)e->d.G * e->d.bs, nc = (size_t)e->d.ncells;
+        ExtBufs x = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int rc = AZX_OK;
+        if (!rc) rc = dev_alloc(e, &x.src2ev, E);
+        if (!rc) rc = dev_alloc(e, &x.row_ev, E);
+        if (!rc) rc = dev_alloc(e, &x.info, 4);
+        if (!rc) rc = dev_alloc(e, &x.board, E * nc);
+        if (!rc) rc = dev_alloc(e, &x.legal, E * nc);
+        if (!rc) rc = dev_alloc(e, &x.value, E);
+        if (!rc) rc = dev_alloc(e, &x.prior, E * nc);
+        if (rc) return rc;
+        const int32_t init[4] = {0, 0, AZX_EXT_NO_ERROR, 0};
+        HIPCHECK(hipMemcpyAsync(x.info, init, sizeof init, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(hipStreamSynchronize(e->stream));
+        e->ext = x;
+        e->ext_dirty.assign((size_t)e->d.G, 0);
+    }
+    e->ext_fn = fn;
+    e->ext_user = fn ? user : nullptr;
+    return AZX_OK;
+}
+
+// one whole search on the stream (no host sync) for the device-side evaluators; with a registered external
+// evaluator the host takes part at every evaluation point (ext_eval) and the call returns after the last one
 static int enqueue_search(azx_engine *e, bool timed) {
     DevEngine &d = e->d;
+    if (ext_registered(e)) {
+        HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
+        if (timed) time_begin(e);
+        azx_launch_mcts(d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
+        if (timed) time_end(e);
+        TRY(ext_eval(e, timed));
+        for (int b = 0; b < e->num_batches; ++b) {
+            HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
+            if (timed) time_begin(e);
+            azx_launch_mcts(d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
+            if (timed) time_end(e);
+            TRY(ext_eval(e, timed));
+        }
+        if (timed) time_begin(e);
+        azx_launch_mcts(d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
+        if (timed) time_end(e);
+        return AZX_OK;
+    }
     if (d.evaluator == AZX_EVAL_UNIFORM || d.evaluator == AZX_EVAL_UNIFORM_HASH) {
         if (timed) time_begin(e);
         azx_launch_mcts(d, MODE_BEGIN | MODE_INLINE, e->num_batches, e->stream, e->force_generic);
@@ -636,12 +767,14 @@ extern "C" int azx_search(azx_engine *e, const double *noise, int n_select, int 
                           double noise_scale) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     ENGINE_GUARD(e);
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL)
+    TRY(ext_refuse(e));
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
         return fail(AZX_ESTATE, "AZX_EVAL_EXTERNAL: drive azx_search_begin/step instead");
     TRY(upload_noise(e, noise, n_select, noise_stride, noise_scale));
     TRY(enqueue_search(e, false));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(e->stream));
+    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
     return check_net_range(e);
 }
 
@@ -657,6 +790,7 @@ extern "C" int azx_search_begin(azx_engine *e, const double *noise, int n_select
                                 double noise_scale, int *n_pending) {
     if (!e || !n_pending) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
+    TRY(ext_refuse(e));
     if (e->d.evaluator != AZX_EVAL_EXTERNAL && e->d.evaluator != AZX_EVAL_RESNET)
         return fail(AZX_ESTATE, "phase API needs AZX_EVAL_EXTERNAL (or RESNET)");
     TRY(upload_noise(e, noise, n_select, noise_stride, noise_scale));
@@ -1115,7 +1249,9 @@ static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
 extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stats) {
     if (!e || !stats) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL) return fail(AZX_ESTATE, "play mode needs a device evaluator");
+    TRY(ext_refuse(e));
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
+        return fail(AZX_ESTATE, "play mode needs a device evaluator");
     memset(stats, 0, sizeof *stats);
     TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 16), 1));
     TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
@@ -1154,6 +1290,7 @@ extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stat
     stats->positions = (int64_t)(b.c[CTR_ROWS] - a.c[CTR_ROWS]);
     stats->seconds = ms * 1e-3;
     time_collect(e, stats);
+    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
     return check_net_range(e);
 }
 
@@ -1217,6 +1354,7 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
     stats->seconds = ms * 1e-3;
     time_collect(e, stats);
     *rows_out = rows;
+    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
     return check_net_range(e);
 }
 
@@ -1225,7 +1363,9 @@ extern "C" int azx_play(azx_engine *e, int64_t min_positions, int64_t max_plies,
                         float *reward, int64_t *game_uid, azx_play_stats *stats) {
     if (!e || !stats) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL) return fail(AZX_ESTATE, "play mode needs a device evaluator");
+    TRY(ext_refuse(e));
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
+        return fail(AZX_ESTATE, "play mode needs a device evaluator");
     DevEngine &d = e->d;
     const int64_t worst = min_positions + (int64_t)d.G * d.ncells;
     if (cap < worst)
@@ -1266,7 +1406,9 @@ extern "C" int azx_play_device(azx_engine *e, int64_t min_positions, int64_t max
                                azx_play_stats *stats) {
     if (!e || !stats || !rows_out) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL) return fail(AZX_ESTATE, "play mode needs a device evaluator");
+    TRY(ext_refuse(e));
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
+        return fail(AZX_ESTATE, "play mode needs a device evaluator");
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
     e->q_rows_valid = (int64_t)rows;
@@ -1423,7 +1565,9 @@ extern "C" int azx_replay_fill(azx_engine *e, int64_t min_positions, int64_t max
     if (!e || !stats) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
     if (e->ring_cap == 0) return fail(AZX_ESTATE, "no replay ring: call azx_replay_create first");
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL) return fail(AZX_ESTATE, "play mode needs a device evaluator");
+    TRY(ext_refuse(e));
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
+        return fail(AZX_ESTATE, "play mode needs a device evaluator");
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
     e->q_rows_valid = (int64_t)rows;

@@ -16,6 +16,14 @@ def _p(a, ctype):
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
+class _DeviceArray:
+    """A device buffer of the engine seen through the CUDA array interface: torch.as_tensor aliases it."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
 class Engine:
     def __init__(self, board_size=11, n_games=1, simulations=400, search_batch_size=10,
                  exploration_coef=0.5, exploration_depth=15, noise_alpha=0.03, noise_scale=0.25,
@@ -36,6 +44,8 @@ class Engine:
         self.num_batches = simulations // search_batch_size + 1          # mcts.py:268
         self.selects_per_search = self.num_batches * search_batch_size
         self._last_rows = 0
+        self._ext_cb = None            # the registered azx_eval_fn trampoline, kept alive with the engine
+        self._ext_exc = None           # what the user's evaluator raised inside the current call
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -48,7 +58,62 @@ class Engine:
         except Exception:
             pass
 
+    def _check(self, rc):
+        """check() for the calls that may run a registered external evaluator: an exception it raised inside the
+        call surfaces itself, chained to the engine's AzxError."""
+        exc, self._ext_exc = self._ext_exc, None
+        if rc != 0 and exc is not None:
+            try:
+                check(rc)
+            except AzxError as err:
+                raise exc from err
+        check(rc)
+
+    @property
+    def stream(self):
+        """The engine's hipStream_t (an int): every kernel of this engine runs on it."""
+        return self.L.azx_stream(self.h) or 0
+
     # ---- set-up -------------------------------------------------------------------------
+    def set_external_evaluator(self, fn):
+        """azx_set_external_evaluator (EVAL_EXTERNAL engines): fn(board, legal_moves) -> (value, prior) over torch
+        tensors on the engine's device -- board int32 [n, N, N] in the first player's view, legal_moves int32
+        [n, kmax] (tile + 1, 0-padded), value float32 [n], prior float32 [n, kmax] (entry j = legal move j) -- for
+        the whole pool's leaf batch at once.  play / play_device / replay_fill / play_steps / search then call it
+        at every evaluation point.  The inputs alias the engine's buffers and are valid during the call only; fn
+        runs under torch.no_grad() on the engine's stream, so it needs no synchronisation.  An exception it raises
+        fails the engine call and is re-raised from it.  None unregisters."""
+        if fn is None:
+            check(self.L.azx_set_external_evaluator(self.h, None, None))
+            self._ext_cb = None
+            return
+        import torch
+        dev = torch.device("cuda", self.cfg.device)
+        N, cells = self.n, self.cells
+
+        def view(ptr, shape, typestr):
+            return torch.as_tensor(_DeviceArray(ptr, shape, typestr), device=dev)
+
+        def trampoline(user, n, kmax, board_p, legal_p, value_p, prior_p, stream_p):
+            try:
+                board = view(board_p, (n, N, N), "<i4")
+                legal = view(legal_p, (n, cells), "<i4")[:, :kmax]
+                value_out = view(value_p, (n,), "<f4")
+                prior_out = view(prior_p, (n, cells), "<f4")
+                with torch.no_grad(), torch.cuda.device(dev), \
+                        torch.cuda.stream(torch.cuda.ExternalStream(stream_p, device=dev)):
+                    value, prior = fn(board, legal)
+                    value_out.copy_(torch.as_tensor(value, device=dev).reshape(n))
+                    prior_out[:, :kmax].copy_(torch.as_tensor(prior, device=dev).reshape(n, kmax))
+                return 0
+            except BaseException as exc:       # (an exception must not unwind through the C frames)
+                self._ext_exc = exc
+                return 1
+
+        cb = _lib.EVAL_FN(trampoline)
+        check(self.L.azx_set_external_evaluator(self.h, C.cast(cb, C.c_void_p), None))
+        self._ext_cb = cb
+
     def set_prior_table(self, table):
         t = np.ascontiguousarray(table, np.float32)
         check(self.L.azx_set_prior_table(self.h, _p(t, C.c_float), t.size))
@@ -130,9 +195,9 @@ class Engine:
         if noise is not None:
             nz = np.ascontiguousarray(noise, np.float64)
             assert nz.ndim == 3 and nz.shape[0] == self.G
-            check(self.L.azx_search(self.h, _p(nz, C.c_double), nz.shape[1], nz.shape[2], noise_scale))
+            self._check(self.L.azx_search(self.h, _p(nz, C.c_double), nz.shape[1], nz.shape[2], noise_scale))
         else:
-            check(self.L.azx_search(self.h, None, 0, 0, noise_scale))
+            self._check(self.L.azx_search(self.h, None, 0, 0, noise_scale))
 
     def search_begin(self, noise=None, noise_scale=0.0):
         n = C.c_int(0)
@@ -284,7 +349,7 @@ class Engine:
         reward = np.zeros(cap, np.float32)
         uid = np.zeros(cap, np.int64)
         st = PlayStats()
-        check(self.L.azx_play(self.h, int(min_positions), int(max_plies), cap,
+        self._check(self.L.azx_play(self.h, int(min_positions), int(max_plies), cap,
                               _p(board, C.c_int32), _p(color, C.c_int32), _p(nlegal, C.c_int32),
                               _p(prob, C.c_float), _p(reward, C.c_float), _p(uid, C.c_int64),
                               C.byref(st)))
@@ -339,7 +404,7 @@ class Engine:
         """azx_play_device: whole games until >= min_positions rows sit in the harvest queue (in HBM)."""
         st = PlayStats()
         rows = C.c_int64(0)
-        check(self.L.azx_play_device(self.h, int(min_positions), int(max_plies), C.byref(rows), C.byref(st)))
+        self._check(self.L.azx_play_device(self.h, int(min_positions), int(max_plies), C.byref(rows), C.byref(st)))
         self._last_rows = int(rows.value)
         return rows.value, st.as_dict()
 
@@ -400,7 +465,7 @@ class Engine:
     def replay_fill(self, min_positions, max_plies=0):
         st = PlayStats()
         rows = C.c_int64(0)
-        check(self.L.azx_replay_fill(self.h, int(min_positions), int(max_plies), C.byref(rows), C.byref(st)))
+        self._check(self.L.azx_replay_fill(self.h, int(min_positions), int(max_plies), C.byref(rows), C.byref(st)))
         self._last_rows = int(rows.value)
         return rows.value, st.as_dict()
 
@@ -441,7 +506,7 @@ class Engine:
 
     def play_steps(self, plies):
         st = PlayStats()
-        check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))
+        self._check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))
         return st.as_dict()
 
 

@@ -8,8 +8,12 @@ on the host and handed out by `read(size)` exactly as batch_examples does -- who
 rank plays its share and the rows are all-gathered (azalea_amd/distributed.py).
 
 The `pool` argument is accepted for signature compatibility (policy_trainer.py:75) and unused:
-there are no worker processes.  Random movers and duck-typed networks go through the host
-play_game loop (one game at a time), like the reference's in-process pool (num_workers=0).
+there are no worker processes.  Random movers and two-agent setups go through the host play_game
+loop (one game at a time), like the reference's in-process pool (num_workers=0).  So do duck-typed
+networks (config["network"] naming another class, policy.py:11-18) by default; with
+`external_batch=True` such a net on a CUDA (ROCm) device plays `n_games` games in one engine instead,
+the engine handing it the whole pool's leaf batch on the device at every evaluation point
+(Engine.set_external_evaluator, policy.external_evaluator).
 """
 import logging
 import os
@@ -23,7 +27,7 @@ from . import distributed as azdist
 from . import engine as _eng
 from .game.hex import HexGameState
 from .play_game import play_game
-from .policy import Policy, SearchTreeFull
+from .policy import Policy, SearchTreeFull, external_evaluator
 from .replay_buffer import ReplayDataFrame
 
 Metrics = Dict[str, float]
@@ -64,16 +68,23 @@ def rows_to_frame(rows) -> ReplayDataFrame:
 class Player:
     MAX_BARREN_PRODUCTIONS = 1000     # consecutive productions without a finished game before read() gives up
 
-    def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None):
+    def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
+                 external_batch: bool = False):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
-        the trainer's weights first; the followers are driven by policy_trainer.serve_selfplay)."""
+        the trainer's weights first; the followers are driven by policy_trainer.serve_selfplay).
+        `external_batch`: a single agent whose Policy holds a network other than HexNetwork, on a CUDA device,
+        plays `n_games` games in one engine that hands the net every leaf batch of the pool on the device
+        (instead of the host loop); a ValueError when that does not hold."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.agents = agents
         self.running = True
         self.gather = gather
+        self.external_batch = bool(external_batch)
+        if self.external_batch:
+            self._external_policy()
         self.role = role if (gather and azdist.is_distributed()) else None
         self.learner = None            # actor_learner.Learner: read() pulls the actors' backlogs instead of playing
         self.weight_syncs = 0          # broadcasts of the trainer's weights this player took part in
@@ -195,6 +206,29 @@ class Player:
         pol = getattr(self.agents[0], "policy", None)
         return pol if isinstance(pol, Policy) and pol._uses_device_net() and len(self.agents) == 1 else None
 
+    def _external_policy(self) -> Policy:
+        """The Policy whose duck-typed net evaluates the pool's leaf batches (external_batch=True); a ValueError
+        naming what does not hold otherwise -- there is no silent fall-back to the host loop."""
+        if len(self.agents) != 1:
+            raise ValueError("external_batch needs a single agent (self-play), got %d" % len(self.agents))
+        pol = getattr(self.agents[0], "policy", None)
+        if not isinstance(pol, Policy):
+            raise ValueError("external_batch needs an agent whose policy is an azalea_amd Policy")
+        if pol._uses_device_net():
+            raise ValueError("external_batch is for networks other than HexNetwork: a HexNetwork takes the "
+                             "native device path without it")
+        dev = _net_device(pol.net)
+        if dev.type != "cuda":
+            raise ValueError("external_batch needs the network on a CUDA (ROCm) device, it is on %s" % dev)
+        if self.gather and azdist.is_distributed():
+            raise ValueError("external_batch does not share reads across ranks: pass gather=False under "
+                             "torch.distributed")
+        return pol
+
+    def _engine_policy(self):
+        """The Policy whose searches run in this Player's engine (None: the host loop plays)."""
+        return self._external_policy() if self.external_batch else self._device_policy()
+
     def _agree_seed_base(self) -> None:
         """Each game draws from its own stream: seed base + GLOBAL game index.  Ranks that share
         their reads use rank 0's base (rank r of W plays the games r, r+W, ...: the set of games does not depend
@@ -203,7 +237,7 @@ class Player:
         games still queued skips.  A Player that does not gather derives its base locally."""
         if self._seed_base is not None:
             return
-        pol = self._device_policy()
+        pol = self._engine_policy()
         if pol is None:
             return
         local = int(pol.rng.randint(0, 2 ** 31 - 1))
@@ -215,6 +249,9 @@ class Player:
             self._seed_base = (local ^ (azdist.rank() * 0x9E3779B1)) & 0x7FFFFFFF
 
     def _produce(self, want: int) -> None:
+        if self.external_batch:
+            self._produce_external(self._external_policy(), want)
+            return
         pol = self._device_policy()
         if pol is None:
             self._produce_on_host()
@@ -245,15 +282,16 @@ class Player:
             rows["moves_prob"][i, :len(p)] = p
         self._games.append((rows, dict(gm)))
 
-    def _get_engine(self, pol: Policy):
+    def _get_engine(self, pol: Policy, external: bool = False):
         n = self.agents[0].game.board_size
         rank, world = ((torch.distributed.get_rank(), torch.distributed.get_world_size())
                        if (self.gather and azdist.is_distributed()) else (0, 1))
-        device = (pol.net.device.index or 0) if pol.net.device.type == "cuda" else 0
+        net_dev = _net_device(pol.net)
+        device = (net_dev.index or 0) if net_dev.type == "cuda" else 0
         key = (n, device, pol.simulations, pol.search_batch_size, float(pol.exploration_coef),
                pol.exploration_depth, pol.exploration_noise_alpha, pol.exploration_noise_scale,
                pol.exploration_temperature, pol.num_blocks, pol.base_chans,
-               bool(pol.settings.get("move_sampling")), bool(pol.settings.get("move_exploration")))
+               bool(pol.settings.get("move_sampling")), bool(pol.settings.get("move_exploration")), external)
         if self._engine is None or key != self._engine_key:
             if self._engine is not None:
                 self._engine.close()
@@ -268,7 +306,8 @@ class Player:
                 noise_alpha=pol.exploration_noise_alpha,
                 noise_scale=pol.exploration_noise_scale if explore else 0.0,
                 temperature=pol.exploration_temperature if sampling else 0.0,
-                evaluator=_eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans,
+                evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
+                num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
             self._engine_key = key
         return self._engine
@@ -277,6 +316,25 @@ class Player:
         eng = self._get_engine(pol)
         self._push_weights(eng, pol)
         rows, st = eng.play(max(1, int(want)))
+        self._harvest(eng, rows, st)
+
+    def _produce_external(self, pol: Policy, want: int) -> None:
+        """_produce_on_device with the policy's own (duck-typed) net as the evaluator of the whole pool."""
+        eng = self._get_engine(pol, external=True)
+        net = pol.net
+        if hasattr(net, "eval"):
+            net.eval()                          # parallel_player.py:64-69
+        eng.set_external_evaluator(external_evaluator(net))
+        # the forward passes run on the engine's stream: after whatever torch queued last (the trainer's step)
+        dev = _net_device(net)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+        rows, st = eng.play(max(1, int(want)))
+        self._harvest(eng, rows, st)
+
+    def _harvest(self, eng, rows, st) -> None:
+        """Whole games of one engine play call -> the read queue, with play_game's per-game metrics."""
         uid = rows["game_uid"]
         self._skipped += int(st["game_errors"])
         if len(uid) == 0:
@@ -304,3 +362,14 @@ class Player:
             eng.set_weights({k: (v.contiguous().data_ptr(), v.numel()) for k, v in sd.items()}, on_device=True)
         else:
             eng.set_weights({k: v.detach().cpu().numpy() for k, v in sd.items()})
+
+
+def _net_device(net) -> torch.device:
+    """Where a duck-typed net lives: its `device` attribute (HexNetwork, the reference's Network), else its first
+    parameter's device."""
+    dev = getattr(net, "device", None)
+    if dev is not None:
+        return torch.device(dev)
+    for p in net.parameters() if hasattr(net, "parameters") else ():
+        return p.device
+    return torch.device("cpu")

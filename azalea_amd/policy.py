@@ -43,6 +43,16 @@ def create_network(network_type, board_size, num_blocks, base_chans):
     return Net(board_size=board_size, num_blocks=num_blocks, base_chans=base_chans)
 
 
+def external_evaluator(net):
+    """mcts.evaluate_batch's network half (mcts.py:202-215) on the device, for Engine.set_external_evaluator: a
+    duck-typed net with the reference's contract (net.run(batch) -> {"value", "moves_logprob"}) evaluates the
+    engine's device tensors as they are; prior = exp(moves_logprob) as mcts.py:210 takes it."""
+    def evaluate(board, legal_moves):
+        out = net.run({"board": board, "legal_moves": legal_moves})
+        return out["value"], torch.exp(out["moves_logprob"])
+    return evaluate
+
+
 _SEARCH_KEYS = ("simulations", "search_batch_size", "exploration_coef", "exploration_depth",
                 "exploration_noise_alpha", "exploration_noise_scale", "exploration_temperature")
 _NET_KEYS = ("network_type", "board_size", "num_blocks", "base_chans")

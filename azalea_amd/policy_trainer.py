@@ -278,7 +278,11 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     config["train_mover_view"] (default False = the reference's batches): train on every position in the view the
     search evaluates it in -- the second player's rows flipped to the first player's view (mcts.py:178-181), which
     the reference's trainer does not do (policy_trainer.py:84-85 feeds the rows' absolute boards).  DESIGN 8.6 has
-    what that costs in playing strength."""
+    what that costs in playing strength.
+
+    config["selfplay_external_batch"] (default False): a network other than HexNetwork (config["network"] naming
+    another class) plays its self-play in one batched engine on the device instead of the host loop
+    (Player(external_batch=True)); its training step stays the stock PyTorch one."""
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])
     torch.manual_seed(config["seed"])
@@ -312,7 +316,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     policy.settings["move_sampling"] = True
     agent = AzaleaAgent(game_factory, policy=policy, device=config["device"])
     lockstep_role = ("leader" if leader else "follower") if mode == "lockstep" else None
-    player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role)
+    player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
+                    external_batch=bool(config.get("selfplay_external_batch", False)))
     if mode == "actor_learner" and player._device_policy() is None:
         raise ValueError("selfplay_mode 'actor_learner' needs a Policy that holds a HexNetwork; use 'lockstep'")
     from_ring = False

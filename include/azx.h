@@ -40,9 +40,11 @@ enum {
     AZX_ENOMEM = -3,
     AZX_ESTATE = -4,     /* call sequence error (e.g. apply without select) */
     AZX_ENODEV = -5,     /* no MI355X visible: there is no CPU fallback */
-    AZX_ERANGE = -6      /* a folded weight or a tower activation is outside the f16 range of the split-f16 kernels
+    AZX_ERANGE = -6,     /* a folded weight or a tower activation is outside the f16 range of the split-f16 kernels
                             (the reference computes in fp32 throughout, network.py:68-85): azx_set_weights rejects such
                             weights; a call whose evaluations overflowed reports it and its results are not valid */
+    AZX_EEXTERNAL = -7   /* the registered external evaluator (azx_set_external_evaluator) returned non-zero, or a row
+                            it produced failed the checks of mcts.py:211-213; the message names the first bad row */
 };
 
 /* evaluator = what plays the role of Network.run inside mcts.evaluate_batch (mcts.py:202-215) */
@@ -86,7 +88,9 @@ typedef struct {
 typedef struct azx_engine azx_engine;
 
 const char *azx_last_error(void);
-int azx_version(void);            /* ABI revision: 6 = azx_reserve_cus, azx_replay_put_records_async (self-play beside training);
+int azx_version(void);            /* ABI revision: 7 = azx_set_external_evaluator, AZX_EEXTERNAL (throughput self-play and
+                                   *     azx_search with a caller-supplied evaluator over device buffers);
+                                   * 6 = azx_reserve_cus, azx_replay_put_records_async (self-play beside training);
                                    * 5 = AZX_ERANGE, azx_debug_weights, weights packed on the device
                                    * (4 = 8-float row metrics, azx_kernel_info, azx_debug_set_queue_cap;
                                    *  3 = azx_config.game_index_*, azx_play_stats.sum_game_length) */
@@ -129,7 +133,8 @@ int azx_set_active(azx_engine *e, const int32_t *active);
  * noise: NULL -> no noise if noise_scale==0, else device RNG Dirichlet (throughput mode);
  * else host Dirichlet draws [n_games][n_select][noise_stride] f64, one row per select_leaf
  * (mcts.py:126-131) -- parity mode keeps numpy's RandomState on the host.
- * With AZX_EVAL_EXTERNAL this returns AZX_ESTATE: drive the phases below instead. */
+ * With AZX_EVAL_EXTERNAL this returns AZX_ESTATE -- drive the phases below instead -- unless an evaluator is
+ * registered (azx_set_external_evaluator): the search then calls it between its phases. */
 int azx_search(azx_engine *e, const double *noise, int n_select, int noise_stride,
                double noise_scale);
 
@@ -153,6 +158,33 @@ int azx_put_evals(azx_engine *e, int n, const float *value, const float *prior);
  * pending positions; read its (value, prior) back in azx_get_leaves order (call that first).
  * This is the "evaluation tape" parity tests replay through the CPU oracle. */
 int azx_get_evals(azx_engine *e, int cap, float *value, float *prior, int *n_out);
+
+/* ---- a caller-supplied evaluator on the device (custom networks, policy.py:11-18) ------------------------
+ * The reference's evaluate_batch hands net.run every leaf of a batch (mcts.py:170-215).  Registered on an
+ * AZX_EVAL_EXTERNAL engine, fn plays that role for the whole pool at once: wherever the resnet path evaluates
+ * (root requests of a search, then each selected batch) the engine calls
+ *   fn(user, n, kmax, board_dev, legal_moves_dev, value_dev, prior_dev, hip_stream)
+ * once, with every pending position of every active slot -- up to n_games * search_batch_size rows, in
+ * (slot, leaf) order (azx_get_leaves' order, whatever order the GPU queued them in):
+ *   board_dev        int32 [n][cells]  the first player's view (mcts.py:178-181), 0 empty / 1 / 2
+ *   legal_moves_dev  int32 [n][cells]  tile + 1 in the flipped frame, original order, 0-padded; kmax = the batch's
+ *                                      largest legal-move count (a network takes [:, :kmax], prep.batch_games)
+ *   value_dev        f32   [n]         out: value for the player to move
+ *   prior_dev        f32   [n][cells]  out: entry j = prior of legal move j; the first k_i entries of row i are read
+ *   hip_stream       the engine's hipStream_t: fn enqueues its work on it (or finishes it before returning).
+ * All four buffers belong to the engine and are valid during the call only.  fn returns 0, or non-zero to fail
+ * the call.  The engine checks every row as mcts.py:211-213 asserts (priors >= 0, |sum of the k priors - 1| <
+ * 1e-4) and that the value is finite.  A non-zero return or a failed check fails the call with AZX_EEXTERNAL
+ * (the message names the first bad row); the searches in flight are left half done (virtual loss applied), so
+ * the engine refuses search and play calls with AZX_ESTATE until all its slots have been azx_reset.
+ * With fn registered, azx_search, azx_play, azx_play_device, azx_replay_fill and azx_play_steps run on the
+ * engine's one stream, and azx_play_stats.net_seconds / net_launches count the hand-overs (export + fn +
+ * import).  Without it every entry point behaves as before (AZX_ESTATE for search and play on this evaluator).
+ * The phase API above is unaffected. */
+typedef int (*azx_eval_fn)(void *user, int n, int kmax, const int32_t *board_dev, const int32_t *legal_moves_dev,
+                           float *value_dev, float *prior_dev, void *hip_stream);
+/* AZX_EVAL_EXTERNAL engines only (else AZX_EINVAL); fn = NULL unregisters */
+int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *user);
 
 /* ---- results ---------------------------------------------------------------------------- */
 

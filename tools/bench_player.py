@@ -10,7 +10,11 @@ the hand-over (k_rows_export + D2H copies, or k_replay_put), and the host frame 
 state the way bench.py does it (uniform-prior self-play, positions transplanted), so every engine move
 finishes ~1 % of the games.  One JSON object on stdout.
 
-    python tools/bench_player.py [--reads 6] [--size 4000] [--games 4096] [--moves 190]
+    python tools/bench_player.py [--reads 6] [--size 4000] [--games 4096] [--moves 190] [--external] [--host-games K]
+
+--external also times Player.read(external_batch=True) with the same weights wrapped in a duck-typed module (a
+custom network: the engine hands it each leaf batch of the whole pool on the device), --host-games K the host
+play_game loop such a network takes by default, on K games.
 """
 import argparse
 import json
@@ -33,6 +37,10 @@ def main():
     ap.add_argument("--chans", type=int, default=64)
     ap.add_argument("--moves", type=int, default=190,
                     help="engine moves of the full-game-length legs (rows/s over the last 60); 0 = skip them")
+    ap.add_argument("--external", action="store_true",
+                    help="also time Player.read through a duck-typed copy of the net (external_batch=True)")
+    ap.add_argument("--host-games", type=int, default=0,
+                    help="also time the host play_game loop of a duck-typed net on this many games")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -108,9 +116,14 @@ def main():
                "host_overhead_frac": (wall - acc["play_device"]) / wall,
                "per_read_seconds": reads}}
 
-    # the HBM-resident path: consume() refills the ring on the device
     E.play = real_play
     pp.rows_to_frame = real_frame
+    if args.external:
+        out["player_read_external"] = external_leg(args, policy, start_positions, torch)
+    if args.host_games > 0:
+        out["host_loop"] = host_leg(args, policy, torch)
+
+    # the HBM-resident path: consume() refills the ring on the device
     buf = DeviceReplayBuffer(E, capacity=400000)
     buf.consume(1.0, player)
     dev_s, rows2 = 0.0, 0
@@ -146,6 +159,89 @@ def main():
                                                        start_positions, torch)
         out["device_replay_consume_full_length"] = consume_full_length(args, bargs, start_positions, torch)
     print(json.dumps(out))
+
+
+def duck_policy(policy, torch):
+    """A Policy whose net is NOT a HexNetwork: the same module behind the reference's duck-typed contract."""
+    from azalea_amd import Policy
+
+    class Wrapped(torch.nn.Module):
+        def __init__(self, inner):
+            super().__init__()
+            self.inner = inner
+            self.device = inner.device
+
+        def run(self, batch):
+            return self.inner.run(batch)
+
+    pol = Policy()
+    pol.initialize(dict(device="cuda", network="HexNetwork", board_size=policy.board_size, num_blocks=policy.num_blocks,
+                        base_chans=policy.base_chans, seed=1, **{k: getattr(policy, k) for k in (
+                            "simulations", "search_batch_size", "exploration_coef", "exploration_depth",
+                            "exploration_noise_alpha", "exploration_noise_scale", "exploration_temperature")}))
+    pol.net = Wrapped(policy.net).eval()
+    pol.settings.update(policy.settings)
+    return pol
+
+
+def external_leg(args, policy, start, torch):
+    """Player.read(external_batch=True) from the same steady-state pool: the stock PyTorch forward of the same
+    weights evaluates each whole-pool leaf batch on the device."""
+    from azalea_amd import AzaleaAgent, HexGame, Player
+    n = args.board
+    pol = duck_policy(policy, torch)
+    player = Player(None, [AzaleaAgent(lambda: HexGame(n), policy=pol, device="cuda")], n_games=args.games,
+                    external_batch=True, gather=False)
+    player._agree_seed_base()
+    E = player._get_engine(pol, external=True)
+    E.reset(moves=start)
+    tot = {"dev": 0.0, "net": 0.0, "plies": 0, "batch": 0}
+    real_play = E.play
+
+    def play(*a, **k):
+        rows, st = real_play(*a, **k)
+        tot["dev"] += st["seconds"]
+        tot["net"] += st["net_seconds"]
+        tot["plies"] += st["plies"]
+        tot["batch"] = max(tot["batch"], st["evals"] // max(1, st["net_launches"]))
+        return rows, st
+    E.play = play
+    player.read(1)
+    for k in tot:
+        tot[k] = 0 if k != "batch" else tot[k]
+    t0 = time.perf_counter()
+    rows, per_read = 0, []
+    for _ in range(args.reads):
+        t1 = time.perf_counter()
+        frame, _ = player.read(args.size)
+        per_read.append((len(frame), time.perf_counter() - t1))
+        rows += len(frame)
+    wall = time.perf_counter() - t0
+    player.stop()
+    return {"surface": "Player.read(external_batch=True), duck-typed wrapper of the same %dx%d weights" % (
+                args.blocks, args.chans),
+            "reads": args.reads, "rows": rows, "seconds": wall, "rows_per_sec": rows / wall,
+            "per_read_rows_per_sec": [r / t for r, t in per_read],
+            "engine_device_seconds": tot["dev"], "evaluator_seconds (export + callback + import)": tot["net"],
+            "evaluator_share": tot["net"] / max(1e-9, tot["dev"]), "plies": tot["plies"],
+            "mean_rows_per_evaluator_call": tot["batch"]}
+
+
+def host_leg(args, policy, torch):
+    """The host play_game loop a duck-typed net takes without external_batch (one game at a time)."""
+    from azalea_amd import AzaleaAgent, HexGame, Player
+    n = args.board
+    pol = duck_policy(policy, torch)
+    player = Player(None, [AzaleaAgent(lambda: HexGame(n), policy=pol, device="cuda")], n_games=1, gather=False)
+    t0 = time.perf_counter()
+    rows = 0
+    for _ in range(args.host_games):
+        player._produce(1)
+        while player._games:
+            rows += len(player._games.popleft()[0]["reward"])
+    wall = time.perf_counter() - t0
+    return {"surface": "Player.read host loop (play_game), duck-typed net", "games": args.host_games, "rows": rows,
+            "seconds": wall, "rows_per_sec": rows / wall}
 
 
 def consume_full_length(args, bargs, start, torch):
