@@ -55,6 +55,16 @@ class PlayStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MatchStats(C.Structure):
+    """azx_match_stats (include/azx.h)."""
+    _fields_ = [("games", C.c_int64), ("wins", C.c_int64 * 2), ("first_player_wins", C.c_int64),
+                ("voided", C.c_int64), ("plies", C.c_int64), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return dict(games=self.games, wins=[self.wins[0], self.wins[1]], first_player_wins=self.first_player_wins,
+                    voided=self.voided, plies=self.plies, seconds=self.seconds)
+
+
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
@@ -116,6 +126,10 @@ SYMBOLS = {
     "azx_debug_set_queue_cap": (C.c_int, [_vp, C.c_int64]),
     "azx_stream": (_vp, [_vp]),
     "azx_set_external_evaluator": (C.c_int, [_vp, _vp, _vp]),   # fn passed as a pointer (NULL = unregister)
+    "azx_match_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "azx_match_destroy": (None, [_vp]),
+    "azx_match_play": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int16),
+                                 C.POINTER(C.c_int16), C.POINTER(MatchStats)]),
 }
 
 class TrainConfig(C.Structure):

@@ -22,6 +22,7 @@
 #include "train.h"
 #include "replay_kernels.h"
 #include "ext_kernels.h"
+#include "match_kernels.h"
 
 #ifndef AZX_SRC_SHA
 #define AZX_SRC_SHA "unknown"      // the Makefile passes the digest of the kernel sources (profiles are keyed to it)
@@ -1772,6 +1773,175 @@ extern "C" int azx_debug_counters(azx_engine *e, uint64_t *out16) {
     TRY(snap_counters(e, &snap));
     for (int j = 0; j < CTR_COUNT; ++j) out16[j] = snap.c[j];
     return AZX_OK;
+}
+
+// ---- matches between two engines on the device (match_kernels.hip) -------------------------------------------
+// evaluation.worker + play_game (evaluation.py:60-80, play_game.py:27-52) for a whole pool of games: slot g of
+// engine a and slot g of engine b hold the two agents' trees of one game.  Per ply the host enqueues
+//   k_match_turn                      (a's stream)  whose turn it is -> GameHdr.active in both engines
+//   a's search + move draw            (a's stream)  |  b's search + move draw  (b's stream, forked / joined by events)
+//   k_match_step                      (a's stream)  hand-over, game step in both engines, settle, refill
+// and reads back ONE word, the number of games decided.
+struct azx_match {
+    azx_engine *a = nullptr, *b = nullptr;
+    MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    int64_t out_cap = 0, moves_cap = 0;          // games the outcome / length and the moves buffers hold
+    int16_t *moves_buf = nullptr;
+    unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, t0 = nullptr, t1 = nullptr;
+};
+
+static const char *match_engine_problem(const azx_engine *e) {
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL)
+        return "is an AZX_EVAL_EXTERNAL engine: matches with external evaluators are not supported";
+    if (e->d.evaluator == AZX_EVAL_RESNET && !azx_net_ready(e->net)) return "has no weights (azx_set_weights)";
+    return nullptr;
+}
+
+extern "C" void azx_match_destroy(azx_match *m) {
+    if (!m) return;
+    DevGuard guard(m->a->cfg.device);
+    if (m->m.slot_game) (void)hipFree(m->m.slot_game);
+    if (m->m.ctr) (void)hipFree(m->m.ctr);
+    if (m->m.outcome) (void)hipFree(m->m.outcome);
+    if (m->m.length) (void)hipFree(m->m.length);
+    if (m->moves_buf) (void)hipFree(m->moves_buf);
+    if (m->host_word) (void)hipHostFree(m->host_word);
+    for (hipEvent_t ev : {m->ev_fork, m->ev_join, m->t0, m->t1})
+        if (ev) (void)hipEventDestroy(ev);
+    delete m;
+}
+
+extern "C" int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out) {
+    if (!a || !b || !out) return fail(AZX_EINVAL, "null argument");
+    if (a == b) return fail(AZX_EINVAL, "a match needs two engines: every agent owns its search tree (a == b)");
+    if (a->cfg.device != b->cfg.device)
+        return fail(AZX_EINVAL, "the engines are on different devices (%d and %d)", a->cfg.device, b->cfg.device);
+    if (a->d.N != b->d.N) return fail(AZX_EINVAL, "the engines' board sizes differ (%d and %d)", a->d.N, b->d.N);
+    if (a->d.G != b->d.G) return fail(AZX_EINVAL, "the engines' n_games differ (%d and %d)", a->d.G, b->d.G);
+    if (const char *why = match_engine_problem(a)) return fail(AZX_EINVAL, "engine a %s", why);
+    if (const char *why = match_engine_problem(b)) return fail(AZX_EINVAL, "engine b %s", why);
+    DevGuard guard(a->cfg.device);
+    azx_match *m = new azx_match();
+    m->a = a;
+    m->b = b;
+    hipError_t err = hipMalloc((void **)&m->m.slot_game, sizeof(int64_t) * (size_t)a->d.G);
+    if (err == hipSuccess) err = hipMalloc((void **)&m->m.ctr, sizeof(unsigned long long) * MCTR_COUNT);
+    if (err == hipSuccess) err = hipHostMalloc((void **)&m->host_word, sizeof(unsigned long long), hipHostMallocDefault);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventCreate(&m->t0);
+    if (err == hipSuccess) err = hipEventCreate(&m->t1);
+    if (err != hipSuccess) {
+        azx_match_destroy(m);
+        return fail(AZX_ENOMEM, "allocating the match state failed: %s", hipGetErrorString(err));
+    }
+    *out = m;
+    return AZX_OK;
+}
+
+// room for n_games results (and move records when asked for)
+static int match_reserve(azx_match *m, int64_t n_games, bool want_moves) {
+    if (n_games > m->out_cap) {
+        if (m->m.outcome) (void)hipFree(m->m.outcome);
+        if (m->m.length) (void)hipFree(m->m.length);
+        m->m.outcome = nullptr; m->m.length = nullptr; m->out_cap = 0;
+        if (hipMalloc((void **)&m->m.outcome, (size_t)n_games) != hipSuccess ||
+            hipMalloc((void **)&m->m.length, sizeof(int16_t) * (size_t)n_games) != hipSuccess)
+            return fail(AZX_ENOMEM, "hipMalloc of the results of %lld games failed", (long long)n_games);
+        m->out_cap = n_games;
+    }
+    if (want_moves && n_games > m->moves_cap) {
+        if (m->moves_buf) (void)hipFree(m->moves_buf);
+        m->moves_buf = nullptr; m->moves_cap = 0;
+        if (hipMalloc((void **)&m->moves_buf, sizeof(int16_t) * (size_t)n_games * m->a->d.ncells) != hipSuccess)
+            return fail(AZX_ENOMEM, "hipMalloc of the move records of %lld games failed", (long long)n_games);
+        m->moves_cap = n_games;
+    }
+    return AZX_OK;
+}
+
+extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *outcome, int16_t *length,
+                              int16_t *moves, azx_match_stats *stats) {
+    if (!m) return fail(AZX_EINVAL, "null match");
+    if (first_game < 0 || n_games < 1) return fail(AZX_EINVAL, "first_game must be >= 0 and n_games >= 1");
+    azx_engine *a = m->a, *b = m->b;
+    ENGINE_GUARD(a);
+    if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
+    if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
+    if (stats) memset(stats, 0, sizeof *stats);
+    const int G = a->d.G, ncells = a->d.ncells;
+    const hipStream_t sa = a->stream, sb = b->stream;
+    // the move draw records a replay row per draw (choose_body): the row area must exist; a game draws at most
+    // ceil(cells / 2) times per engine and n_rows restarts with every game
+    for (azx_engine *e : {a, b}) {
+        TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
+        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
+    }
+    TRY(match_reserve(m, n_games, moves != nullptr));
+    MatchDev M = m->m;
+    M.first_game = first_game;
+    M.n_games = n_games;
+    M.moves = moves ? m->moves_buf : nullptr;
+    if (M.moves) HIPCHECK(hipMemsetAsync(M.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, sa));
+    unsigned long long ctr0[MCTR_COUNT] = {0};
+    ctr0[MCTR_NEXT] = (unsigned long long)std::min<int64_t>(G, n_games);
+    HIPCHECK(hipMemcpyAsync(M.ctr, ctr0, sizeof ctr0, hipMemcpyHostToDevice, sa));
+    // fresh games in every slot of both engines (no generation is used up: the uids are the match's)
+    azx_launch_reset(a->d, nullptr, G, nullptr, nullptr, 0, 0, sa);
+    azx_launch_reset(b->d, nullptr, G, nullptr, nullptr, 0, 0, sa);
+    azx_launch_match_init(a->d, b->d, M, sa);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(sa));                  // (ctr0 is on this frame)
+    HIPCHECK(hipEventRecord(m->t0, sa));
+
+    // every game ends within `cells` plies and a slot plays its games back to back
+    const int64_t max_plies = ((n_games + G - 1) / G + 1) * (int64_t)(ncells + 1);
+    int64_t plies = 0;
+    for (;; ++plies) {
+        if (plies > max_plies)
+            return fail(AZX_ESTATE, "match: %lld plies without deciding all %lld games (internal error)",
+                        (long long)plies, (long long)n_games);
+        azx_launch_match_turn(a->d, b->d, M, sa);
+        HIPCHECK(hipEventRecord(m->ev_fork, sa));
+        HIPCHECK(hipStreamWaitEvent(sb, m->ev_fork, 0));
+        TRY(enqueue_search(a, false));
+        azx_launch_choose(a->d, sa);
+        TRY(enqueue_search(b, false));
+        azx_launch_choose(b->d, sb);
+        HIPCHECK(hipEventRecord(m->ev_join, sb));
+        HIPCHECK(hipStreamWaitEvent(sa, m->ev_join, 0));
+        azx_launch_match_step(a->d, b->d, M, sa);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(m->host_word, M.ctr + MCTR_DECIDED, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa));
+        HIPCHECK(hipStreamSynchronize(sa));
+        if (*m->host_word >= (unsigned long long)n_games) break;
+    }
+    HIPCHECK(hipEventRecord(m->t1, sa));
+
+    unsigned long long ctr[MCTR_COUNT];
+    HIPCHECK(hipMemcpyAsync(ctr, M.ctr, sizeof ctr, hipMemcpyDeviceToHost, sa));
+    if (outcome) HIPCHECK(hipMemcpyAsync(outcome, M.outcome, (size_t)n_games, hipMemcpyDeviceToHost, sa));
+    if (length) HIPCHECK(hipMemcpyAsync(length, M.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, sa));
+    if (moves) HIPCHECK(hipMemcpyAsync(moves, M.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, sa));
+    // leave both engines as azx_reset leaves them: fresh games, all active, their own uid numbering
+    azx_launch_reset(a->d, nullptr, G, nullptr, nullptr, 0, 1, sa);
+    azx_launch_reset(b->d, nullptr, G, nullptr, nullptr, 0, 1, sa);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(sa));
+    if (stats) {
+        float ms = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms, m->t0, m->t1));
+        stats->games = (int64_t)ctr[MCTR_DECIDED];
+        stats->wins[0] = (int64_t)ctr[MCTR_WINS0];
+        stats->wins[1] = (int64_t)ctr[MCTR_WINS1];
+        stats->first_player_wins = (int64_t)ctr[MCTR_FIRST_WINS];
+        stats->voided = (int64_t)ctr[MCTR_VOIDED];
+        stats->plies = (int64_t)ctr[MCTR_PLIES];
+        stats->seconds = ms * 1e-3;
+    }
+    TRY(check_net_range(a));
+    return check_net_range(b);
 }
 
 // ---- native training step (train_kernels.hip) ----------------------------------------------------------------

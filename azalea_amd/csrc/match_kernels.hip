@@ -1,0 +1,153 @@
+// match_kernels.hip -- bookkeeping kernels of a device-resident match between two engines (azx_match_play).
+//
+// NOT a translation unit of its own: mcts_kernels.hip includes this file at its end.  The game step and subtree
+// carry are advance_body's, and the rules read the board geometry from that unit's constant memory (c_geo), which
+// a second unit could not share without relocatable device code.
+//
+// The reference plays an evaluation game with one search tree per agent: the mover's agent searches and draws,
+// then EVERY agent follows the move in its own tree (azalea/play_game.py:27-52, policy.py:170-176,
+// search_tree.py:115-132).  Here slot g of engine A and slot g of engine B hold the two agents' views of the same
+// game; these kernels decide whose turn it is, hand the drawn move over, settle finished games and refill the
+// slot, so that the host reads back one word per ply.  Plain stores and atomics only.
+#include "match_kernels.h"
+
+// agent (0 = engine A, 1 = engine B) to move in game u at `ply`: agent u & 1 moves first
+__device__ __forceinline__ int match_mover(int64_t u, int ply) { return (int)(u & 1) ^ (ply & 1); }
+
+__global__ void k_match_init(DevEngine A, DevEngine B, MatchDev M) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= A.G) return;
+    const int64_t u = g < M.n_games ? M.first_game + g : -1;
+    M.slot_game[g] = u;
+    if (u >= 0) {        // every draw of game u is keyed by (engine seed + u, ply): not by the slot
+        A.ghdr[g].uid = u;
+        B.ghdr[g].uid = u;
+    }
+}
+
+__global__ void k_match_turn(DevEngine A, DevEngine B, MatchDev M) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= A.G) return;
+    const int64_t u = M.slot_game[g];
+    int a = 0, b = 0;
+    if (u >= 0) {
+        const int mover = match_mover(u, A.ghdr[g].ply);
+        a = mover == 0;
+        b = mover == 1;
+    }
+    A.ghdr[g].active = a;
+    B.ghdr[g].active = b;
+}
+
+// fresh empty game in slot g of one engine (what advance_body's play-mode restart does, with the uid given)
+template <int SLOTS>
+__device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t uid, int lane) {
+    HexWave<SLOTS> z;
+    z.clear();
+    z.store(E.cells + (size_t)g * SLOTS * 64, lane);
+    GameHdr *gh = E.ghdr + g;
+    if (lane == 0) {
+        gh->color = 1;
+        gh->winner = 0;
+        gh->ply = 0;
+        gh->active = 0;            // k_match_turn decides
+        gh->move_id = -1;
+        gh->n_rows = 0;
+        gh->ply0 = 0;
+        gh->parked = 0;
+        if (uid >= 0) gh->uid = uid;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    tree_reset<SLOTS>(E, g, E.thdr + g, E.ncells, lane);
+}
+
+// One wave per slot, after both engines' searches and move draws of this ply.
+template <int SLOTS>
+__global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, MatchDev M) {
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x;
+    const int64_t u = M.slot_game[g];
+    if (u < 0) return;                                         // idle slot
+    GameHdr *ga = A.ghdr + g, *gb = B.ghdr + g;
+    const int ply = ga->ply;                                   // (the two slots hold the same game)
+    const int first = (int)(u & 1);
+    const int mover = match_mover(u, ply);
+    const int mid = mover ? gb->move_id : ga->move_id;
+    const int status = mover ? B.thdr[g].status : A.thdr[g].status;
+    // SearchTreeFull in the searching agent's tree voids the game (parallel_player.py:73-76 skips such a game);
+    // a search that ended without a draw cannot happen on a live game and is treated alike, so no slot can spin
+    bool voided = status != 0 || mid < 0;
+    const int64_t idx = u - M.first_game;
+    int winner = 0, len = ply;
+
+    if (!voided) {
+        // the mid-th legal move in ascending tile order (search_tree.py:306): the same tile in both engines
+        HexWave<SLOTS> h;
+        h.load(A.cells + (size_t)g * SLOTS * 64, lane);
+        h.color = ga->color;
+        h.winner = ga->winner;
+        const Masks<SLOTS> mk = make_masks<SLOTS>(h, lane, A.ncells);
+        int cell = -1;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint64_t hit = __ballot(lane_bit(mk.m[s]) && mk.base[s] + rank_below(mk.m[s]) == mid);
+            if (hit) cell = s * 64 + (int)__ffsll((long long)hit) - 1;
+        }
+        if (cell < 0 || ply >= A.ncells) {
+            voided = true;
+        } else {
+            if (lane == 0) {
+                if (M.moves) M.moves[(size_t)idx * A.ncells + ply] = (int16_t)(cell + 1);
+                ga->move_id = mid;  gb->move_id = mid;         // Policy.execute_action for every agent
+                ga->active = 1;     gb->active = 1;
+            }
+            wave_mem_sync();
+            advance_body<SLOTS>(A, nullptr, 0);
+            advance_body<SLOTS>(B, nullptr, 0);
+            wave_mem_sync();
+            winner = ga->winner;
+            len = ply + 1;
+        }
+    }
+    if (!voided && winner == 0) return;                        // the game goes on
+
+    // ---- settle: outcome by agent, tallies, the next game for this slot ----
+    long long next_u = -1;
+    if (lane == 0) {
+        int outcome = 0;
+        if (!voided) {
+            const int won = winner == 1 ? first : 1 - first;   // colour 1 = the first mover
+            outcome = won == 0 ? 1 : -1;
+            atomicAdd(M.ctr + (won == 0 ? MCTR_WINS0 : MCTR_WINS1), 1ull);
+            if (winner == 1) atomicAdd(M.ctr + MCTR_FIRST_WINS, 1ull);
+        } else {
+            atomicAdd(M.ctr + MCTR_VOIDED, 1ull);
+        }
+        M.outcome[idx] = (int8_t)outcome;
+        M.length[idx] = (int16_t)len;
+        atomicAdd(M.ctr + MCTR_PLIES, (unsigned long long)len);
+        atomicAdd(M.ctr + MCTR_DECIDED, 1ull);
+        // the lowest game index not yet started, or idle
+        const unsigned long long nx = atomicAdd(M.ctr + MCTR_NEXT, 1ull);
+        next_u = nx < (unsigned long long)M.n_games ? M.first_game + (long long)nx : -1;
+        M.slot_game[g] = next_u;
+    }
+    next_u = ((long long)__builtin_amdgcn_readfirstlane((int)(next_u >> 32)) << 32) |
+             (unsigned int)__builtin_amdgcn_readfirstlane((int)next_u);
+    match_restart<SLOTS>(A, g, next_u, lane);
+    match_restart<SLOTS>(B, g, next_u, lane);
+}
+
+void azx_launch_match_init(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
+    hipLaunchKernelGGL(k_match_init, dim3((A.G + 255) / 256), dim3(256), 0, st, A, B, M);
+}
+
+void azx_launch_match_turn(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
+    hipLaunchKernelGGL(k_match_turn, dim3((A.G + 255) / 256), dim3(256), 0, st, A, B, M);
+}
+
+void azx_launch_match_step(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
+#define CALL(S) hipLaunchKernelGGL((k_match_step<S>), dim3(A.G), dim3(64), 0, st, A, B, M)
+    DISPATCH_SLOTS(A.slots, CALL);
+#undef CALL
+}

@@ -2076,3 +2076,8 @@ void azx_launch_arith(const float *a, const float *b, float *sq, float *dv, floa
                       hipStream_t st) {
     hipLaunchKernelGGL(k_arith, dim3((n + 255) / 256), dim3(256), 0, st, a, b, sq, dv, mul, n);
 }
+
+// ============================================================================================
+// matches between two engines (azx_match_*): kernels and launchers, built as part of this unit
+// ============================================================================================
+#include "match_kernels.hip"

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EVAL_EXTERNAL, EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH,  # noqa: F401
-                   FLAG_NO_COMPACT, AzxError, Config, PlayStats, check)
+                   FLAG_NO_COMPACT, AzxError, Config, MatchStats, PlayStats, check)
 
 
 def _p(a, ctype):
@@ -508,6 +508,47 @@ class Engine:
         st = PlayStats()
         self._check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))
         return st.as_dict()
+
+
+class Match:
+    """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
+    agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
+    the games of a call do not depend on the pool size.  The engines stay the caller's (and must stay open while
+    the match is); they are reset by every play()."""
+
+    def __init__(self, engine_a, engine_b):
+        self.L = _lib.lib()
+        self.a, self.b = engine_a, engine_b
+        self.cells = engine_a.cells
+        self.h = C.c_void_p()
+        check(self.L.azx_match_create(engine_a.h, engine_b.h, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.azx_match_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def play(self, n_games, first_game=0, moves=False):
+        """Games first_game .. first_game + n_games - 1, each to its end.  Returns outcome int8[n] (+1 agent 0 won,
+        -1 agent 1 won, 0 voided by SearchTreeFull), length int16[n] (plies), with `moves` the game records
+        int16[n, cells] (tile + 1 in play order, 0-padded), and stats (azx_match_stats as a dict)."""
+        n = int(n_games)
+        outcome = np.zeros(n, np.int8)
+        length = np.zeros(n, np.int16)
+        mv = np.zeros((n, self.cells), np.int16) if moves else None
+        st = MatchStats()
+        check(self.L.azx_match_play(self.h, int(first_game), n, _p(outcome, C.c_int8), _p(length, C.c_int16),
+                                    _p(mv, C.c_int16), C.byref(st)))
+        out = dict(outcome=outcome, length=length, stats=st.as_dict())
+        if moves:
+            out["moves"] = mv
+        return out
 
 
 def hex_replay(board_size, moves, lengths, device=0):

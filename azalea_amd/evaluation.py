@@ -11,8 +11,14 @@ pair and round, task seed `10000 * round + index`, first player by a coin flip o
 searches only the slots whose turn it is (`azx_set_active`), and every game keeps the private
 RandomStates the sequential schedule would give it, so the outcomes are the same games, move for
 move.
+
+`evaluate_throughput` is the throughput form of the same round robin: a pair's games are played by two
+engines against each other entirely on the device (`engine.Match`, azx_match_*), the move draws come from
+the device RNG, and the first mover alternates instead of following a coin flip -- the reference's
+algorithm as a distribution, not game for game.
 """
 import logging
+import os
 from collections import defaultdict
 from typing import Dict, List, Tuple
 
@@ -187,4 +193,88 @@ def evaluate_batched(agents, num_rounds: int, *, game_max_length: int = 300) -> 
         return outcomes
     finally:
         for eng, _ in engines:
+            eng.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# the tournament in throughput mode: every pair's games played on the device, no host in the ply loop
+# ---------------------------------------------------------------------------------------------
+def _throughput_policy(agent):
+    from .policy import Policy
+    pol = getattr(agent, "policy", None)
+    if not isinstance(pol, Policy) or not pol._uses_device_net():
+        raise TypeError("evaluate_throughput needs agents whose Policy holds a HexNetwork")
+    return pol
+
+
+def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
+                        games=None) -> Dict[Pair, OutcomeCounts]:
+    """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
+    pair's games played by the two agents' engines against each other on the device (azx_match_play):
+    returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
+    (default min(num_rounds, AZX_GAMES or 4096), rounded up to even); agent a's engine seed is derived from
+    `seed` and a, and every pair plays its own range of game indices, so no two games of a call share a
+    random stream.  The policies' `settings` are honoured as Policy.choose_action does (policy.py:132-149).
+    `games`: optional dict that receives per pair dict(outcome, length, moves).  A game voided by a full
+    search tree raises policy.SearchTreeFull (a policy attribute `nodes_per_game`, if set, sizes its engine's
+    per-game arena; the engine's default otherwise)."""
+    import torch
+    from . import engine as _eng
+    from .policy import SearchTreeFull
+
+    pols = [_throughput_policy(a) for a in agents]
+    num_rounds = int(num_rounds)
+    if num_rounds < 1:
+        raise ValueError("num_rounds must be >= 1")
+    pairs = gen_pairs(len(agents))
+    if len(agents) > 256 or len(pairs) * num_rounds >= 1 << 32 or not 0 <= int(seed) < 1 << 24:
+        raise ValueError("evaluate_throughput: at most 256 agents, 2^32 games and a seed below 2^24")
+    n = agents[0].game.board_size
+    if n_slots is None:
+        n_slots = min(num_rounds, int(os.environ.get("AZX_GAMES", "4096")))
+    n_slots = max(2, int(n_slots) + (int(n_slots) & 1))
+    engines = []
+    try:
+        for a, pol in enumerate(pols):
+            # Policy.choose_action's schedule (policy.py:132-149); the depth gate is the engine's
+            temperature = noise_scale = 0.0
+            if pol.settings["move_sampling"]:
+                temperature = pol.exploration_temperature
+                if pol.settings["move_exploration"]:
+                    noise_scale = pol.exploration_noise_scale
+            dev = pol.net.device
+            # game_rng keys on seed + uid: agent a's streams are [base_a, base_a + 2^32), disjoint between agents
+            eng = _eng.Engine(board_size=n, n_games=n_slots, simulations=pol.simulations,
+                              search_batch_size=pol.search_batch_size, exploration_coef=pol.exploration_coef,
+                              exploration_depth=pol.exploration_depth, noise_alpha=pol.exploration_noise_alpha,
+                              noise_scale=noise_scale, temperature=temperature,
+                              evaluator=_eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans,
+                              device=(dev.index or 0) if dev.type == "cuda" else 0,
+                              nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),   # 0: the engine's default
+                              seed=((int(seed) << 8) + a) << 32)
+            engines.append(eng)
+            pol.net.eval()
+            sd = {k: v for k, v in pol.net.state_dict().items() if v.dtype == torch.float32}
+            if dev.type == "cuda":
+                eng.set_weights({k: (v.contiguous().data_ptr(), v.numel()) for k, v in sd.items()}, on_device=True)
+            else:
+                eng.set_weights({k: v.detach().cpu().numpy() for k, v in sd.items()})
+        outcomes: Dict[Pair, OutcomeCounts] = defaultdict(lambda: [0, 0, 0])
+        for s, (i, j) in enumerate(pairs):
+            match = _eng.Match(engines[i], engines[j])
+            try:
+                res = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None)
+            finally:
+                match.close()
+            st = res["stats"]
+            if st["voided"]:
+                raise SearchTreeFull("too many nodes")
+            outcomes[(i, j)] = [int(st["wins"][0]), 0, int(st["wins"][1])]
+            if games is not None:
+                games[(i, j)] = {k: res[k] for k in ("outcome", "length", "moves")}
+            logging.info("pair %s: outcomes %s (%.1f games/s on the device)", (i, j), outcomes[(i, j)],
+                         num_rounds / max(st["seconds"], 1e-9))
+        return outcomes
+    finally:
+        for eng in engines:
             eng.close()

@@ -89,7 +89,8 @@ typedef struct azx_engine azx_engine;
 
 const char *azx_last_error(void);
 int azx_version(void);            /* ABI revision: 7 = azx_set_external_evaluator, AZX_EEXTERNAL (throughput self-play and
-                                   *     azx_search with a caller-supplied evaluator over device buffers);
+                                   *     azx_search with a caller-supplied evaluator over device buffers); the azx_match_*
+                                   *     entry points were added within revision 7 -- callers detect them by symbol;
                                    * 6 = azx_reserve_cus, azx_replay_put_records_async (self-play beside training);
                                    * 5 = AZX_ERANGE, azx_debug_weights, weights packed on the device
                                    * (4 = 8-float row metrics, azx_kernel_info, azx_debug_set_queue_cap;
@@ -389,6 +390,53 @@ int azx_kernel_info(azx_engine *e, char *buf, int cap);
 /* tests: bound the harvest queue of the following azx_play* calls to `rows` rows (0 = no bound) so that finished
  * games find it full and park (parallel_player.py has no counterpart: its pipes block instead). */
 int azx_debug_set_queue_cap(azx_engine *e, int64_t rows);
+
+/* ---- evaluation matches between two engines, entirely on the device -------------------------
+ * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_match_create).
+ * Replaces, in throughput form, the reference's tournament games (azalea/evaluation.py:17-80 -> play_game.py ->
+ * policy.py:132-176): two agents play each other, the mover's agent searches and draws a move, EVERY agent then
+ * follows that move in its own search tree (play_game.py calls each agent's execute_action; search_tree.py:115-132).
+ * A match joins two existing engines, one per agent: slot g of engine a and slot g of engine b are the two agents'
+ * trees of the same game.  The engines must be on the same device with the same board_size and the same n_games
+ * (= G slots), a != b, evaluator AZX_EVAL_RESNET (weights set), AZX_EVAL_UNIFORM or AZX_EVAL_UNIFORM_HASH -- anything
+ * else is AZX_EINVAL (AZX_EVAL_EXTERNAL engines are not supported).  Everything else may differ per agent:
+ * simulations, search batch, c_puct, temperature, exploration depth, noise, seed, nodes_per_game, network shape.
+ * The engines must outlive the match; while azx_match_play runs both belong to the calling thread.
+ *
+ * azx_match_play plays exactly the games u = first_game .. first_game + n_games - 1, each to its end: slot g starts
+ * with game first_game + g, a slot whose game has ended takes the lowest game index not yet started, and goes idle
+ * when none is left (n_games may be smaller or much larger than G).  Game u:
+ *   - agent u & 1 moves first (colour 1).  DEVIATION: the reference flips a coin per game (evaluation.py:70-72);
+ *     alternating has the same expectation and no variance in the colour balance.
+ *   - at every ply only the mover's engine searches the slot, with ITS OWN configuration, and draws the move on the
+ *     device exactly as throughput-mode self-play does (azx_play: temperature while ply < exploration_depth, then
+ *     the most-visited child; noise at every ply when noise_scale != 0 -- policy.py:142-160); then BOTH engines step
+ *     the game and move their trees to that child (same board, same ascending legal list, same move_id).
+ *   - both engines use uid = u for game u: every draw of the game depends on (that engine's seed, u, ply) only, not
+ *     on the slot, on G or on the games in flight beside it.  The same games come out of any pool size.
+ *   - outcome +1: agent 0 (engine a) won; -1: agent 1 won; 0: voided.  Hex has no draws.
+ *   - SearchTreeFull (azx_get_status) in the searching engine voids the game: outcome 0, length = the plies played
+ *     so far, the slot takes the next game; the call goes on and returns AZX_OK.
+ * Outputs, indexed by u - first_game, any may be NULL: outcome[n_games], length[n_games] (plies),
+ * moves[n_games][cells] (tile + 1 in play order, 0-padded: the game record).
+ * The call resets all slots of both engines at entry and leaves them as azx_reset leaves them (fresh games, all
+ * active, the engine's own uid numbering); it writes no replay rows to the harvest queue.  It blocks.  Per ply the
+ * host reads back one counter; nothing it transfers grows with G.  a's searches run on a's stream and b's on b's,
+ * concurrently.  A call that fails (AZX_EHIP, AZX_ERANGE, ...) leaves the engines where the failure found them:
+ * azx_reset both before using them again. */
+typedef struct {
+    int64_t games;              /* games decided (= n_games) */
+    int64_t wins[2];            /* by agent: 0 = engine a, 1 = engine b */
+    int64_t first_player_wins;
+    int64_t voided;             /* SearchTreeFull in the searching agent's tree: outcome 0 */
+    int64_t plies;              /* moves played over all games */
+    double  seconds;            /* device time of the call */
+} azx_match_stats;
+typedef struct azx_match azx_match;
+int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out);
+void azx_match_destroy(azx_match *m);
+int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *outcome, int16_t *length,
+                   int16_t *moves, azx_match_stats *stats);
 
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
