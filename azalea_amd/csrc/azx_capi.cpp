@@ -78,6 +78,7 @@ struct azx_engine {
     void *ext_user = nullptr;
     ExtBufs ext = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int32_t ext_info[4] = {0, 0, AZX_EXT_NO_ERROR, 0};
+    int32_t *ext_info_host = nullptr;           // pinned landing place of ext.info (a copy into it never blocks the host)
     std::vector<char> ext_dirty;
     bool ext_failed = false;
     // play mode
@@ -284,6 +285,7 @@ extern "C" void azx_destroy(azx_engine *e) {
     for (void *p : e->ring_allocs) (void)hipFree(p);
     if (e->export_board) (void)hipFree(e->export_board);
     if (e->export_prob) (void)hipFree(e->export_prob);
+    if (e->ext_info_host) (void)hipHostFree(e->ext_info_host);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -650,21 +652,38 @@ static int ext_check_rows(azx_engine *e) {
                                  : "has prior probabilities whose sum is not 1 within 1e-4 (mcts.py:211-213)");
 }
 
-static int ext_read_info(azx_engine *e) {
-    HIPCHECK(hipMemcpyAsync(e->ext_info, e->ext.info, sizeof e->ext_info, hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
+// ext.info -> the pinned host words, enqueued on `s` (not waited for); ext_info_take after that stream was waited for
+static int ext_info_enqueue(azx_engine *e, hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(e->ext_info_host, e->ext.info, sizeof e->ext_info, hipMemcpyDeviceToHost, s));
+    return AZX_OK;
+}
+
+static int ext_info_take(azx_engine *e) {
+    memcpy(e->ext_info, e->ext_info_host, sizeof e->ext_info);
     return ext_check_rows(e);
 }
 
-// One evaluation point of the phase loop, where the resnet path calls azx_net_eval: the pending requests in
-// (slot, leaf) order out to the caller's buffers, the callback, the checked results back into ev_*.  One host
-// sync per point reads n, kmax and the previous import's error word together.
-static int ext_eval(azx_engine *e, bool timed) {
-    DevEngine &d = e->d;
+static int ext_read_info(azx_engine *e) {
+    TRY(ext_info_enqueue(e, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return ext_info_take(e);
+}
+
+// One evaluation point of the phase loop, where the resnet path calls azx_net_eval, in two halves.  The first needs
+// no host: the pending requests are put in (slot, leaf) order and n, kmax and the previous import's error word are
+// sent to the host.  The second waits for those words (the one host sync of the point), then: the rows out to the
+// caller's buffers, the callback, the checked results back into ev_*.
+static int ext_point_enqueue(azx_engine *e, bool timed) {
     if (timed) time_begin(e, 1);
-    azx_launch_ext_order(d, e->ext, e->stream);
+    azx_launch_ext_order(e->d, e->ext, e->stream);
     HIPCHECK(hipGetLastError());
-    const int rc_info = ext_read_info(e);
+    return ext_info_enqueue(e, e->stream);
+}
+
+static int ext_point_finish(azx_engine *e, bool timed) {
+    DevEngine &d = e->d;
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    const int rc_info = ext_info_take(e);
     if (rc_info) return rc_info;
     const int n = e->ext_info[0], kmax = e->ext_info[1];
     if (n < 0 || n > d.G * d.bs) return ext_fail(e, "external evaluator: %d pending rows (internal error)", n);
@@ -678,6 +697,45 @@ static int ext_eval(azx_engine *e, bool timed) {
         HIPCHECK(hipGetLastError());
     }
     if (timed) time_end(e);
+    return AZX_OK;
+}
+
+// The search of an engine with a registered evaluator as a cursor over its num_batches + 1 evaluation points.
+// begin: the first tree phase and its point's first half are on the stream.  resume: the point's second half (host
+// sync, callback), then the next tree phase with its point's first half -- or, after the last point, the final
+// APPLY, which ends the search.  enqueue_search runs the cursor to its end on the one stream; azx_match_play
+// advances two engines' cursors in turn.
+struct ExtCursor {
+    int points = 0;         // evaluation points after the first whose tree phase has been enqueued
+    bool done = true;
+    bool timed = false;
+};
+
+static int ext_search_begin(azx_engine *e, ExtCursor *c, bool timed) {
+    c->points = 0;
+    c->done = false;
+    c->timed = timed;
+    HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
+    if (timed) time_begin(e);
+    azx_launch_mcts(e->d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
+    if (timed) time_end(e);
+    return ext_point_enqueue(e, timed);
+}
+
+static int ext_search_resume(azx_engine *e, ExtCursor *c) {
+    TRY(ext_point_finish(e, c->timed));
+    if (c->points < e->num_batches) {
+        HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
+        if (c->timed) time_begin(e);
+        azx_launch_mcts(e->d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
+        if (c->timed) time_end(e);
+        c->points += 1;
+        return ext_point_enqueue(e, c->timed);
+    }
+    if (c->timed) time_begin(e);
+    azx_launch_mcts(e->d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
+    if (c->timed) time_end(e);
+    c->done = true;
     return AZX_OK;
 }
 
@@ -699,6 +757,9 @@ extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *u
         if (!rc) rc = dev_alloc(e, &x.value, E);
         if (!rc) rc = dev_alloc(e, &x.prior, E * nc);
         if (rc) return rc;
+        if (!e->ext_info_host &&
+            hipHostMalloc((void **)&e->ext_info_host, sizeof e->ext_info, hipHostMallocDefault) != hipSuccess)
+            return fail(AZX_ENOMEM, "hipHostMalloc of the evaluator's info words failed");
         const int32_t init[4] = {0, 0, AZX_EXT_NO_ERROR, 0};
         HIPCHECK(hipMemcpyAsync(x.info, init, sizeof init, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(hipStreamSynchronize(e->stream));
@@ -711,25 +772,13 @@ extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *u
 }
 
 // one whole search on the stream (no host sync) for the device-side evaluators; with a registered external
-// evaluator the host takes part at every evaluation point (ext_eval) and the call returns after the last one
+// evaluator the host takes part at every evaluation point (the ExtCursor run to its end) and the call returns after the last one
 static int enqueue_search(azx_engine *e, bool timed) {
     DevEngine &d = e->d;
     if (ext_registered(e)) {
-        HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
-        if (timed) time_begin(e);
-        azx_launch_mcts(d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
-        if (timed) time_end(e);
-        TRY(ext_eval(e, timed));
-        for (int b = 0; b < e->num_batches; ++b) {
-            HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
-            if (timed) time_begin(e);
-            azx_launch_mcts(d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
-            if (timed) time_end(e);
-            TRY(ext_eval(e, timed));
-        }
-        if (timed) time_begin(e);
-        azx_launch_mcts(d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
-        if (timed) time_end(e);
+        ExtCursor c;
+        TRY(ext_search_begin(e, &c, timed));
+        while (!c.done) TRY(ext_search_resume(e, &c));
         return AZX_OK;
     }
     if (d.evaluator == AZX_EVAL_UNIFORM || d.evaluator == AZX_EVAL_UNIFORM_HASH) {
@@ -1781,7 +1830,10 @@ extern "C" int azx_debug_counters(azx_engine *e, uint64_t *out16) {
 //   k_match_turn                      (a's stream)  whose turn it is -> GameHdr.active in both engines
 //   a's search + move draw            (a's stream)  |  b's search + move draw  (b's stream, forked / joined by events)
 //   k_match_step                      (a's stream)  hand-over, game step in both engines, settle, refill
-// and reads back ONE word, the number of games decided.
+// and reads back ONE word, the number of games decided.  An engine with a registered external evaluator cannot be
+// enqueued whole: the host takes part at each of its evaluation points.  Its search is then a cursor (ExtCursor)
+// that the ply advances point by point, after everything that needs no host is on the streams and in turn with the
+// other engine's cursor when both are external (match_ply_searches).
 struct azx_match {
     azx_engine *a = nullptr, *b = nullptr;
     MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
@@ -1789,11 +1841,12 @@ struct azx_match {
     int16_t *moves_buf = nullptr;
     unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, t0 = nullptr, t1 = nullptr;
+    bool interleave = true;                      // AZX_MATCH_INTERLEAVE=0: a's whole search, then b's (diagnostic)
 };
 
 static const char *match_engine_problem(const azx_engine *e) {
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL)
-        return "is an AZX_EVAL_EXTERNAL engine: matches with external evaluators are not supported";
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !e->ext_fn)
+        return "is an AZX_EVAL_EXTERNAL engine with no evaluator registered (azx_set_external_evaluator)";
     if (e->d.evaluator == AZX_EVAL_RESNET && !azx_net_ready(e->net)) return "has no weights (azx_set_weights)";
     return nullptr;
 }
@@ -1825,6 +1878,7 @@ extern "C" int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out) {
     azx_match *m = new azx_match();
     m->a = a;
     m->b = b;
+    { const char *v = getenv("AZX_MATCH_INTERLEAVE"); m->interleave = !(v && atoi(v) == 0); }
     hipError_t err = hipMalloc((void **)&m->m.slot_game, sizeof(int64_t) * (size_t)a->d.G);
     if (err == hipSuccess) err = hipMalloc((void **)&m->m.ctr, sizeof(unsigned long long) * MCTR_COUNT);
     if (err == hipSuccess) err = hipHostMalloc((void **)&m->host_word, sizeof(unsigned long long), hipHostMallocDefault);
@@ -1861,6 +1915,49 @@ static int match_reserve(azx_match *m, int64_t n_games, bool want_moves) {
     return AZX_OK;
 }
 
+// a failure inside a ply: nothing either engine has queued is left running, and the message says whose engine it was
+static int match_fail(azx_match *m, const azx_engine *e, int rc) {
+    (void)hipStreamSynchronize(m->a->stream);
+    (void)hipStreamSynchronize(m->b->stream);
+    if (rc == AZX_EEXTERNAL) g_err = std::string("engine ") + (e == m->a ? "a" : "b") + ": " + g_err;
+    return rc;
+}
+#define MATCH_TRY(e, expr)                           \
+    do {                                             \
+        int _rc = (expr);                            \
+        if (_rc) return match_fail(m, (e), _rc);     \
+    } while (0)
+
+// Both engines' searches and move draws of one ply, each on its engine's stream (b's stream has been forked).
+// Interleaved: first what needs no host -- the whole search and draw of a device-evaluated engine -- then the
+// external engines' cursors in turn, so that each engine's next tree phase is on its stream before the host waits
+// for the other engine's evaluation point.  Plain order: a's whole search, then b's.  The streams' contents, and so
+// the games, are the same either way.
+static int match_ply_searches(azx_match *m) {
+    azx_engine *eng[2] = {m->a, m->b};
+    if (!m->interleave) {
+        for (azx_engine *e : eng) {
+            MATCH_TRY(e, enqueue_search(e, false));
+            azx_launch_choose(e->d, e->stream);
+        }
+        return AZX_OK;
+    }
+    ExtCursor cur[2];
+    for (azx_engine *e : eng)
+        if (!ext_registered(e)) {
+            MATCH_TRY(e, enqueue_search(e, false));
+            azx_launch_choose(e->d, e->stream);
+        }
+    for (int i = 0; i < 2; ++i)
+        if (ext_registered(eng[i])) MATCH_TRY(eng[i], ext_search_begin(eng[i], &cur[i], false));
+    while (!cur[0].done || !cur[1].done)
+        for (int i = 0; i < 2; ++i)
+            if (!cur[i].done) MATCH_TRY(eng[i], ext_search_resume(eng[i], &cur[i]));
+    for (azx_engine *e : eng)
+        if (ext_registered(e)) azx_launch_choose(e->d, e->stream);
+    return AZX_OK;
+}
+
 extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *outcome, int16_t *length,
                               int16_t *moves, azx_match_stats *stats) {
     if (!m) return fail(AZX_EINVAL, "null match");
@@ -1869,6 +1966,8 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
+    TRY(ext_refuse(a));
+    TRY(ext_refuse(b));
     if (stats) memset(stats, 0, sizeof *stats);
     const int G = a->d.G, ncells = a->d.ncells;
     const hipStream_t sa = a->stream, sb = b->stream;
@@ -1905,16 +2004,18 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
         azx_launch_match_turn(a->d, b->d, M, sa);
         HIPCHECK(hipEventRecord(m->ev_fork, sa));
         HIPCHECK(hipStreamWaitEvent(sb, m->ev_fork, 0));
-        TRY(enqueue_search(a, false));
-        azx_launch_choose(a->d, sa);
-        TRY(enqueue_search(b, false));
-        azx_launch_choose(b->d, sb);
+        TRY(match_ply_searches(m));
         HIPCHECK(hipEventRecord(m->ev_join, sb));
         HIPCHECK(hipStreamWaitEvent(sa, m->ev_join, 0));
         azx_launch_match_step(a->d, b->d, M, sa);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpyAsync(m->host_word, M.ctr + MCTR_DECIDED, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa));
+        // the error word of each external search's last import rides on the same read-back (a's stream has joined b's)
+        for (azx_engine *e : {a, b})
+            if (ext_registered(e)) TRY(ext_info_enqueue(e, sa));
         HIPCHECK(hipStreamSynchronize(sa));
+        for (azx_engine *e : {a, b})
+            if (ext_registered(e)) MATCH_TRY(e, ext_info_take(e));
         if (*m->host_word >= (unsigned long long)n_games) break;
     }
     HIPCHECK(hipEventRecord(m->t1, sa));

@@ -80,7 +80,7 @@ class Engine:
         tensors on the engine's device -- board int32 [n, N, N] in the first player's view, legal_moves int32
         [n, kmax] (tile + 1, 0-padded), value float32 [n], prior float32 [n, kmax] (entry j = legal move j) -- for
         the whole pool's leaf batch at once.  play / play_device / replay_fill / play_steps / search then call it
-        at every evaluation point.  The inputs alias the engine's buffers and are valid during the call only; fn
+        at every evaluation point, and so does Match.play for the slots in which this engine is the mover.  The inputs alias the engine's buffers and are valid during the call only; fn
         runs under torch.no_grad() on the engine's stream, so it needs no synchronisation.  An exception it raises
         fails the engine call and is re-raised from it.  None unregisters."""
         if fn is None:
@@ -514,7 +514,9 @@ class Match:
     """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
     agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
     the games of a call do not depend on the pool size.  The engines stay the caller's (and must stay open while
-    the match is); they are reset by every play()."""
+    the match is); they are reset by every play().  An EVAL_EXTERNAL engine takes part once its evaluator is
+    registered (Engine.set_external_evaluator): it is called at every evaluation point with the rows of the slots in
+    which its engine is the mover, and an exception it raises is re-raised from play()."""
 
     def __init__(self, engine_a, engine_b):
         self.L = _lib.lib()
@@ -543,8 +545,18 @@ class Match:
         length = np.zeros(n, np.int16)
         mv = np.zeros((n, self.cells), np.int16) if moves else None
         st = MatchStats()
-        check(self.L.azx_match_play(self.h, int(first_game), n, _p(outcome, C.c_int8), _p(length, C.c_int16),
-                                    _p(mv, C.c_int16), C.byref(st)))
+        self.a._ext_exc = self.b._ext_exc = None
+        rc = self.L.azx_match_play(self.h, int(first_game), n, _p(outcome, C.c_int8), _p(length, C.c_int16),
+                                   _p(mv, C.c_int16), C.byref(st))
+        # what an engine's evaluator raised inside the call surfaces itself, chained to the AzxError (Engine._check)
+        exc = self.a._ext_exc if self.a._ext_exc is not None else self.b._ext_exc
+        self.a._ext_exc = self.b._ext_exc = None
+        if rc != 0 and exc is not None:
+            try:
+                check(rc)
+            except AzxError as err:
+                raise exc from err
+        check(rc)
         out = dict(outcome=outcome, length=length, stats=st.as_dict())
         if moves:
             out["moves"] = mv

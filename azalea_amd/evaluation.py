@@ -199,16 +199,25 @@ def evaluate_batched(agents, num_rounds: int, *, game_max_length: int = 300) -> 
 # ---------------------------------------------------------------------------------------------
 # the tournament in throughput mode: every pair's games played on the device, no host in the ply loop
 # ---------------------------------------------------------------------------------------------
-def _throughput_policy(agent):
+def _throughput_policy(agent, external_batch=False):
     from .policy import Policy
     pol = getattr(agent, "policy", None)
-    if not isinstance(pol, Policy) or not pol._uses_device_net():
-        raise TypeError("evaluate_throughput needs agents whose Policy holds a HexNetwork")
+    if not isinstance(pol, Policy):
+        raise TypeError("evaluate_throughput needs agents whose policy is an azalea_amd Policy")
+    if pol._uses_device_net():
+        return pol
+    if not external_batch:
+        raise TypeError("evaluate_throughput needs agents whose Policy holds a HexNetwork "
+                        "(external_batch=True takes other networks)")
+    from .parallel_player import _net_device
+    dev = _net_device(pol.net)
+    if dev.type != "cuda":
+        raise ValueError("external_batch needs the network on a CUDA (ROCm) device, it is on %s" % dev)
     return pol
 
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
-                        games=None) -> Dict[Pair, OutcomeCounts]:
+                        games=None, external_batch: bool = False) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -217,12 +226,16 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     random stream.  The policies' `settings` are honoured as Policy.choose_action does (policy.py:132-149).
     `games`: optional dict that receives per pair dict(outcome, length, moves).  A game voided by a full
     search tree raises policy.SearchTreeFull (a policy attribute `nodes_per_game`, if set, sizes its engine's
-    per-game arena; the engine's default otherwise)."""
+    per-game arena; the engine's default otherwise).
+    `external_batch`: an agent whose Policy holds a network other than HexNetwork, on a CUDA (ROCm) device, plays
+    through an EVAL_EXTERNAL engine with policy.external_evaluator(net) registered: its net gets the leaf batches
+    of all the slots in which it is the mover, on the device, at every evaluation point (ValueError when the
+    network is not on such a device).  Agents with a HexNetwork keep the device tower, so fields may be mixed."""
     import torch
     from . import engine as _eng
-    from .policy import SearchTreeFull
+    from .policy import SearchTreeFull, external_evaluator
 
-    pols = [_throughput_policy(a) for a in agents]
+    pols = [_throughput_policy(a, external_batch) for a in agents]
     num_rounds = int(num_rounds)
     if num_rounds < 1:
         raise ValueError("num_rounds must be >= 1")
@@ -242,18 +255,33 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                 temperature = pol.exploration_temperature
                 if pol.settings["move_exploration"]:
                     noise_scale = pol.exploration_noise_scale
-            dev = pol.net.device
+            external = not pol._uses_device_net()
+            if external:
+                from .parallel_player import _net_device
+                dev = _net_device(pol.net)
+            else:
+                dev = pol.net.device
             # game_rng keys on seed + uid: agent a's streams are [base_a, base_a + 2^32), disjoint between agents
             eng = _eng.Engine(board_size=n, n_games=n_slots, simulations=pol.simulations,
                               search_batch_size=pol.search_batch_size, exploration_coef=pol.exploration_coef,
                               exploration_depth=pol.exploration_depth, noise_alpha=pol.exploration_noise_alpha,
                               noise_scale=noise_scale, temperature=temperature,
-                              evaluator=_eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans,
+                              evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
+                              num_blocks=getattr(pol, "num_blocks", 0) if external else pol.num_blocks,
+                              base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
                               device=(dev.index or 0) if dev.type == "cuda" else 0,
                               nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),   # 0: the engine's default
                               seed=((int(seed) << 8) + a) << 32)
             engines.append(eng)
-            pol.net.eval()
+            if hasattr(pol.net, "eval"):
+                pol.net.eval()
+            if external:
+                eng.set_external_evaluator(external_evaluator(pol.net))
+                # the forward passes run on the engine's stream: after whatever torch queued last on the net's device
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))
+                torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+                continue
             sd = {k: v for k, v in pol.net.state_dict().items() if v.dtype == torch.float32}
             if dev.type == "cuda":
                 eng.set_weights({k: (v.contiguous().data_ptr(), v.numel()) for k, v in sd.items()}, on_device=True)

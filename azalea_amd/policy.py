@@ -43,13 +43,31 @@ def create_network(network_type, board_size, num_blocks, base_chans):
     return Net(board_size=board_size, num_blocks=num_blocks, base_chans=base_chans)
 
 
-def external_evaluator(net):
+def _row_bucket(n: int) -> int:
+    """The smallest of 64, 96, 128, 192, 256, 384, ... (2^k and 3 * 2^(k-1)) that holds n rows."""
+    b = 64
+    while b < n:
+        b = b + b // 2 if b & (b - 1) == 0 else (b // 3) * 4
+    return b
+
+
+def external_evaluator(net, pad_rows=True):
     """mcts.evaluate_batch's network half (mcts.py:202-215) on the device, for Engine.set_external_evaluator: a
     duck-typed net with the reference's contract (net.run(batch) -> {"value", "moves_logprob"}) evaluates the
-    engine's device tensors as they are; prior = exp(moves_logprob) as mcts.py:210 takes it."""
+    engine's device tensors as they are; prior = exp(moves_logprob) as mcts.py:210 takes it.
+    `pad_rows`: the number of pending rows differs from one evaluation point to the next, and a convolution library
+    that prepares its kernels per input shape (MIOpen does, for seconds, at every batch size it has not seen) would
+    spend the run doing that.  The batch is therefore padded with empty boards that have no legal move up to the
+    next of a few sizes (_row_bucket: at most a third more rows), and the results are cut back to the rows asked
+    for; a row's result does not depend on the rows beside it (the net is in eval mode)."""
     def evaluate(board, legal_moves):
+        n = int(board.shape[0])
+        extra = _row_bucket(n) - n if pad_rows else 0
+        if extra:
+            board = torch.cat([board, board.new_zeros((extra,) + tuple(board.shape[1:]))])
+            legal_moves = torch.cat([legal_moves, legal_moves.new_zeros((extra, legal_moves.shape[1]))])
         out = net.run({"board": board, "legal_moves": legal_moves})
-        return out["value"], torch.exp(out["moves_logprob"])
+        return out["value"][:n], torch.exp(out["moves_logprob"][:n])
     return evaluate
 
 

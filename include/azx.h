@@ -180,8 +180,10 @@ int azx_get_evals(azx_engine *e, int cap, float *value, float *prior, int *n_out
  * the engine refuses search and play calls with AZX_ESTATE until all its slots have been azx_reset.
  * With fn registered, azx_search, azx_play, azx_play_device, azx_replay_fill and azx_play_steps run on the
  * engine's one stream, and azx_play_stats.net_seconds / net_launches count the hand-overs (export + fn +
- * import).  Without it every entry point behaves as before (AZX_ESTATE for search and play on this evaluator).
- * The phase API above is unaffected. */
+ * import).  azx_match_play calls fn as well, for the slots in which this engine is the mover, and there advances
+ * two such engines' searches in turn (the match section below); fn still gets its own engine's stream.
+ * Without fn every entry point behaves as before (AZX_ESTATE for search and play on this evaluator; azx_match_create
+ * refuses the engine).  The phase API above is unaffected. */
 typedef int (*azx_eval_fn)(void *user, int n, int kmax, const int32_t *board_dev, const int32_t *legal_moves_dev,
                            float *value_dev, float *prior_dev, void *hip_stream);
 /* AZX_EVAL_EXTERNAL engines only (else AZX_EINVAL); fn = NULL unregisters */
@@ -398,8 +400,12 @@ int azx_debug_set_queue_cap(azx_engine *e, int64_t rows);
  * follows that move in its own search tree (play_game.py calls each agent's execute_action; search_tree.py:115-132).
  * A match joins two existing engines, one per agent: slot g of engine a and slot g of engine b are the two agents'
  * trees of the same game.  The engines must be on the same device with the same board_size and the same n_games
- * (= G slots), a != b, evaluator AZX_EVAL_RESNET (weights set), AZX_EVAL_UNIFORM or AZX_EVAL_UNIFORM_HASH -- anything
- * else is AZX_EINVAL (AZX_EVAL_EXTERNAL engines are not supported).  Everything else may differ per agent:
+ * (= G slots), a != b, evaluator AZX_EVAL_RESNET (weights set), AZX_EVAL_UNIFORM, AZX_EVAL_UNIFORM_HASH, or
+ * AZX_EVAL_EXTERNAL with an evaluator registered (azx_set_external_evaluator), in any combination -- anything else
+ * is AZX_EINVAL (an AZX_EVAL_EXTERNAL engine with no evaluator registered among them).  If the evaluator has been
+ * unregistered by the time of azx_match_play, that call fails with AZX_ESTATE before it touches either engine; so
+ * does a match with an engine whose earlier external evaluation failed, until all its slots have been azx_reset.
+ * Everything else may differ per agent:
  * simulations, search batch, c_puct, temperature, exploration depth, noise, seed, nodes_per_game, network shape.
  * The engines must outlive the match; while azx_match_play runs both belong to the calling thread.
  *
@@ -423,7 +429,19 @@ int azx_debug_set_queue_cap(azx_engine *e, int64_t rows);
  * active, the engine's own uid numbering); it writes no replay rows to the harvest queue.  It blocks.  Per ply the
  * host reads back one counter; nothing it transfers grows with G.  a's searches run on a's stream and b's on b's,
  * concurrently.  A call that fails (AZX_EHIP, AZX_ERANGE, ...) leaves the engines where the failure found them:
- * azx_reset both before using them again. */
+ * azx_reset both before using them again.
+ *
+ * An engine with a registered evaluator takes the host at each of its simulations / search_batch_size + 1 evaluation
+ * points per search: fn gets the pending rows of the slots in which that engine is the mover only (about
+ * G / 2 * search_batch_size rows at most times), in (slot, leaf) order, on that engine's stream.  Per ply the host
+ * first enqueues whatever needs no host (the whole search and draw of a device-evaluated engine), then advances the
+ * external engines point by point in turn, so that each engine's next tree phase is on its stream before the host
+ * waits for the other's rows; host syncs per ply = the external engines' evaluation points + 1.  The games do not
+ * depend on that order, nor on G.  AZX_MATCH_INTERLEAVE=0 in the environment at azx_match_create selects the plain
+ * order (a's whole search, then b's): a diagnostic.  A non-zero return of fn or a row that fails the checks fails
+ * the call with AZX_EEXTERNAL before the next ply's searches are enqueued (the message names engine a or b, and the
+ * first bad row); the error word of a search's last hand-over comes with the per-ply read-back.  The failing engine
+ * then refuses search, play and match calls with AZX_ESTATE until all its slots have been azx_reset. */
 typedef struct {
     int64_t games;              /* games decided (= n_games) */
     int64_t wins[2];            /* by agent: 0 = engine a, 1 = engine b */

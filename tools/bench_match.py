@@ -12,7 +12,22 @@ tools/bench_evaluation.py).
       path plays its three pairs of 100 one after the other)
 
     python tools/bench_match.py [--sims 400] [--rounds 300] [--big-rounds 16384] [--big-slots 4096] [--rr-rounds 100]
-One JSON line (profiles/match_bench.json)."""
+One JSON line (profiles/match_bench.json).
+
+`--external`: the match with a custom network instead -- a torch.nn.Module that is not a HexNetwork and whose `run` is
+the PyTorch forward of a 6x64 HexNetwork -- and nothing of the above:
+  (i)   evaluate_throughput(external_batch=True): the custom network against a 6x64 HexNetwork on the device tower,
+        `--ext-games` games in `--ext-slots` slots
+  (ii)  the same two agents through evaluation.evaluate, the host loop, `--host-games` games (once: it is slow)
+  (iii) two custom agents under AZX_MATCH_INTERLEAVE=1 and =0 (read at azx_match_create)
+  (iv)  self-play of the custom network at the same slot count, in plies/s: the EVAL_EXTERNAL engine with
+        policy.external_evaluator registered that Player(external_batch=True) plays with, driven by play_steps from a
+        pool started out of phase as (d) above
+(i), (iii) and (iv) `--repeats` times, alternating, medians of the wall time with the set-up included.
+
+    python tools/bench_match.py --external [--ext-games 256] [--ext-slots 256] [--host-games 2] [--repeats 3]
+One JSON line (profiles/match_external_bench.json).  `--external --trace-run`: two matches of the two custom agents and
+nothing else, for `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_match.py ...`."""
 import argparse
 import json
 import os
@@ -48,6 +63,21 @@ def agents(sims):
     return out
 
 
+class CustomNet(torch.nn.Module):
+    """Not a HexNetwork: evaluates with the PyTorch forward of one, behind the reference's duck-typed contract."""
+
+    def __init__(self, inner):
+        super().__init__()
+        self.inner = inner
+
+    @property
+    def device(self):               # (the reference's Network has it; Policy's host loop sends its batches there)
+        return self.inner.device
+
+    def run(self, batch):
+        return self.inner.run(batch)
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -78,8 +108,90 @@ def selfplay(pol, slots, sims, steps):
                 mean_game_length=st["sum_game_length"] / max(1, st["games"]), kernel_info=info)
 
 
+def selfplay_external(pol, slots, sims, steps):
+    """selfplay() for a custom network: the engine Player(external_batch=True) plays with."""
+    from azalea_amd.policy import external_evaluator
+    E = eng.Engine(board_size=BOARD, n_games=slots, simulations=sims, search_batch_size=10, exploration_coef=0.5,
+                   exploration_depth=15, noise_alpha=0.03, noise_scale=0.0, temperature=1.0, evaluator=eng.EVAL_EXTERNAL)
+    pol.net.eval()
+    E.set_external_evaluator(external_evaluator(pol.net))
+    E.reset(moves=eng.random_prefixes(BOARD, np.arange(slots, dtype=np.int64), 92, 1))
+    E.play_steps(1)
+    st = E.play_steps(steps)
+    E.close()
+    return dict(seconds=st["seconds"], plies=st["plies"], plies_per_sec=st["plies"] / st["seconds"])
+
+
+def external_main(args):
+    ag = agents(args.sims)
+    for a in (ag[0], ag[2]):
+        a.policy.net = CustomNet(a.policy.net)
+    custom, tower, custom2 = ag
+    res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
+           "device": torch.cuda.get_device_name(0), "games": args.ext_games, "slots": args.ext_slots,
+           "repeats": args.repeats}
+    G, S = args.ext_games, args.ext_slots
+
+    def match(field, interleave):
+        os.environ["AZX_MATCH_INTERLEAVE"] = str(interleave)
+        games = {}
+        t, out = timed(lambda: evaluation.evaluate_throughput(field, G, n_slots=S, games=games, external_batch=True))
+        print("match of %d games, interleave %s: %.2f s, %d plies" % (G, interleave, t, games[(0, 1)]["length"].sum()),
+              file=sys.stderr, flush=True)
+        return t, float(games[(0, 1)]["length"].sum()), out
+
+    if args.trace_run:      # the program to put behind `rocprofv3 --kernel-trace --stats --`: two matches of two custom agents
+        match([custom, custom2], 1)
+        t, plies, _ = match([custom, custom2], 1)
+        print(json.dumps({"games": G, "slots": S, "seconds": t, "plies": plies}))
+        return
+    # warm every path once: the convolution library prepares its kernels per batch size
+    t_warm, _, _ = match([custom, tower], 1)
+    res["warm_up_match_seconds"] = t_warm
+    match([custom, custom2], 1)
+    selfplay_external(custom.policy, S, args.sims, 1)
+
+    t_i, t_on, t_off, sp = [], [], [], []
+    plies_i = plies_on = plies_off = 0.0
+    for _ in range(args.repeats):
+        t, plies_i, out_i = match([custom, tower], 1)
+        t_i.append(t)
+        t, plies_on, _ = match([custom, custom2], 1)
+        t_on.append(t)
+        t, plies_off, _ = match([custom, custom2], 0)
+        t_off.append(t)
+        sp.append(selfplay_external(custom.policy, S, args.sims, args.selfplay_steps))
+        print("self-play: %s" % sp[-1], file=sys.stderr, flush=True)
+    os.environ.pop("AZX_MATCH_INTERLEAVE", None)
+    med = statistics.median
+    res["custom_vs_tower"] = {"seconds": t_i, "games_per_sec": G / med(t_i), "plies_per_sec": plies_i / med(t_i),
+                              "tallies": tallies(out_i)}
+    # (ii) the parent's path for the same two agents
+    t_h, out_h = timed(lambda: evaluation.evaluate([custom, tower], args.host_games))
+    print("host loop, %d games: %.2f s" % (args.host_games, t_h), file=sys.stderr, flush=True)
+    res["host_loop"] = {"games": args.host_games, "seconds": t_h, "games_per_sec": args.host_games / t_h,
+                        "tallies": tallies(out_h)}
+    res["throughput_over_host_loop_games_per_sec"] = res["custom_vs_tower"]["games_per_sec"] / res["host_loop"]["games_per_sec"]
+    res["custom_vs_custom"] = {"interleaved_seconds": t_on, "plain_seconds": t_off,
+                               "interleaved_plies_per_sec": plies_on / med(t_on),
+                               "plain_plies_per_sec": plies_off / med(t_off),
+                               "plain_over_interleaved_seconds": med(t_off) / med(t_on),
+                               "spread_interleaved": (max(t_on) - min(t_on)) / med(t_on),
+                               "spread_plain": (max(t_off) - min(t_off)) / med(t_off)}
+    res["selfplay_external"] = {"steps": args.selfplay_steps, "plies_per_sec": [x["plies_per_sec"] for x in sp],
+                                "median_plies_per_sec": med([x["plies_per_sec"] for x in sp])}
+    res["match_over_selfplay_plies_per_sec"] = (res["custom_vs_tower"]["plies_per_sec"] /
+                                                res["selfplay_external"]["median_plies_per_sec"])
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--external", action="store_true")
+    ap.add_argument("--ext-games", type=int, default=256)
+    ap.add_argument("--ext-slots", type=int, default=256)
+    ap.add_argument("--host-games", type=int, default=2)
+    ap.add_argument("--trace-run", action="store_true", help="--external: only two custom-vs-custom matches (for a profiler)")
     ap.add_argument("--sims", type=int, default=400)
     ap.add_argument("--rounds", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=3)
@@ -88,6 +200,8 @@ def main():
     ap.add_argument("--selfplay-steps", type=int, default=30)
     ap.add_argument("--rr-rounds", type=int, default=100)
     args = ap.parse_args()
+    if args.external:
+        return external_main(args)
     ag = agents(args.sims)
     two = ag[:2]
     res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
