@@ -130,6 +130,11 @@ SYMBOLS = {
     "azx_match_destroy": (None, [_vp]),
     "azx_match_play": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int16),
                                  C.POINTER(C.c_int16), C.POINTER(MatchStats)]),
+    "azx_tournament_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(_vp)]),
+    "azx_tournament_destroy": (None, [_vp]),
+    "azx_tournament_play": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32,
+                                      C.POINTER(C.c_int8), C.POINTER(C.c_int16), C.POINTER(C.c_int16),
+                                      C.POINTER(MatchStats)]),
 }
 
 class TrainConfig(C.Structure):

@@ -2045,6 +2045,265 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     return check_net_range(b);
 }
 
+// ---- tournaments: P matches side by side in one ply loop, sharing K engines (match_kernels.hip) ----------------
+// evaluation.evaluate hands every round's pairs to its pool at once (evaluation.py:29-58); here every pair gets
+// `tables_per_pair` tables, a table being slot sa of the pair's first engine and slot sb of its second (an engine's
+// pool is partitioned among its opponents, so no engine holds a slot for a pair it is not part of).  Per ply:
+//   k_tour_turn                    (engine 0's stream)   whose turn it is at every table -> GameHdr.active
+//   engine k's search + move draw  (engine k's stream)   over the active slots of ALL its pairs; forked / joined by events
+//   k_tour_step                    (engine 0's stream)   hand-over, game step in both slots, settle per pair, refill
+// and ONE word read back: the games decided over all pairs.  Game numbering is the round robin's: round r of pair s is
+// game first_game + s * rounds + r, with that uid in both engines, so a pair plays exactly the games of
+// azx_match_play(first_game + s * rounds, rounds) between its two engines.
+struct azx_tournament {
+    std::vector<azx_engine *> eng;
+    TourDev t = {};
+    DevEngine *eng_dev = nullptr;                // [K]
+    TourTable *tab_dev = nullptr;
+    int64_t tab_cap = 0, game_cap = 0, ctr_cap = 0, out_cap = 0, len_cap = 0, moves_cap = 0;   // elements held
+    unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
+    hipEvent_t ev_fork = nullptr, t0 = nullptr, t1 = nullptr;
+    std::vector<hipEvent_t> ev_join;             // [K - 1]: engine k's stream back into engine 0's
+};
+
+extern "C" void azx_tournament_destroy(azx_tournament *t) {
+    if (!t) return;
+    DevGuard guard(t->eng[0]->cfg.device);
+    for (void *p : {(void *)t->eng_dev, (void *)t->tab_dev, (void *)t->t.tab_game, (void *)t->t.ctr,
+                    (void *)t->t.outcome, (void *)t->t.length, (void *)t->t.moves})
+        if (p) (void)hipFree(p);
+    if (t->host_word) (void)hipHostFree(t->host_word);
+    for (hipEvent_t ev : {t->ev_fork, t->t0, t->t1})
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : t->ev_join)
+        if (ev) (void)hipEventDestroy(ev);
+    delete t;
+}
+
+extern "C" int azx_tournament_create(azx_engine *const *engines, int n_engines, azx_tournament **out) {
+    if (!engines || !out) return fail(AZX_EINVAL, "null argument");
+    if (n_engines < 2) return fail(AZX_EINVAL, "a tournament needs at least two engines (n_engines = %d)", n_engines);
+    for (int i = 0; i < n_engines; ++i) {
+        azx_engine *e = engines[i];
+        if (!e) return fail(AZX_EINVAL, "engine %d is null", i);
+        for (int j = 0; j < i; ++j)
+            if (engines[j] == e)
+                return fail(AZX_EINVAL, "engines %d and %d are the same engine: every agent owns its search tree", j, i);
+        if (e->cfg.device != engines[0]->cfg.device)
+            return fail(AZX_EINVAL, "engines 0 and %d are on different devices (%d and %d)", i, engines[0]->cfg.device,
+                        e->cfg.device);
+        if (e->d.N != engines[0]->d.N)
+            return fail(AZX_EINVAL, "the board sizes of engines 0 and %d differ (%d and %d)", i, engines[0]->d.N, e->d.N);
+        if (const char *why = match_engine_problem(e)) return fail(AZX_EINVAL, "engine %d %s", i, why);
+    }
+    DevGuard guard(engines[0]->cfg.device);
+    azx_tournament *t = new azx_tournament();
+    t->eng.assign(engines, engines + n_engines);
+    t->ev_join.assign((size_t)n_engines - 1, nullptr);
+    hipError_t err = hipMalloc((void **)&t->eng_dev, sizeof(DevEngine) * (size_t)n_engines);
+    if (err == hipSuccess) err = hipHostMalloc((void **)&t->host_word, sizeof(unsigned long long), hipHostMallocDefault);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming);
+    for (hipEvent_t &ev : t->ev_join)
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventCreate(&t->t0);
+    if (err == hipSuccess) err = hipEventCreate(&t->t1);
+    if (err != hipSuccess) {
+        azx_tournament_destroy(t);
+        return fail(AZX_ENOMEM, "allocating the tournament state failed: %s", hipGetErrorString(err));
+    }
+    *out = t;
+    return AZX_OK;
+}
+
+// a device buffer of at least `count` elements (grown, never shrunk; the contents are not kept)
+template <typename T>
+static int tour_grow(T **p, int64_t *cap, int64_t count, const char *what) {
+    if (count <= *cap) return AZX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc((void **)p, sizeof(T) * (size_t)count) != hipSuccess)
+        return fail(AZX_ENOMEM, "hipMalloc of the tournament's %s (%lld) failed", what, (long long)count);
+    *cap = count;
+    return AZX_OK;
+}
+
+// a failure inside a ply: nothing any engine has queued is left running, and the message says whose engine it was
+static int tour_fail(azx_tournament *t, int k, int rc) {
+    for (azx_engine *e : t->eng) (void)hipStreamSynchronize(e->stream);
+    if (rc == AZX_EEXTERNAL) g_err = "engine " + std::to_string(k) + ": " + g_err;
+    return rc;
+}
+#define TOUR_TRY(k, expr)                           \
+    do {                                            \
+        int _rc = (expr);                           \
+        if (_rc) return tour_fail(t, (k), _rc);     \
+    } while (0)
+
+// match_ply_searches for K engines, each on its own stream (all forked from engine 0's): first what needs no host
+// -- the whole search and draw of every device-evaluated engine -- then the external engines' cursors in turn, so
+// that each one's next tree phase is on its stream before the host waits for another's evaluation point.
+static int tour_ply_searches(azx_tournament *t) {
+    const int K = (int)t->eng.size();
+    std::vector<ExtCursor> cur((size_t)K);
+    for (int k = 0; k < K; ++k)
+        if (!ext_registered(t->eng[k])) {
+            TOUR_TRY(k, enqueue_search(t->eng[k], false));
+            azx_launch_choose(t->eng[k]->d, t->eng[k]->stream);
+        }
+    for (int k = 0; k < K; ++k)
+        if (ext_registered(t->eng[k])) TOUR_TRY(k, ext_search_begin(t->eng[k], &cur[k], false));
+    for (bool busy = true; busy;) {
+        busy = false;
+        for (int k = 0; k < K; ++k)
+            if (!cur[k].done) {
+                TOUR_TRY(k, ext_search_resume(t->eng[k], &cur[k]));
+                busy = true;
+            }
+    }
+    for (int k = 0; k < K; ++k)
+        if (ext_registered(t->eng[k])) azx_launch_choose(t->eng[k]->d, t->eng[k]->stream);
+    return AZX_OK;
+}
+
+extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                                   int64_t first_game, int64_t rounds, int32_t tables_per_pair, int8_t *outcome,
+                                   int16_t *length, int16_t *moves, azx_match_stats *stats) {
+    if (!t) return fail(AZX_EINVAL, "null tournament");
+    if (!pair_a || !pair_b || n_pairs < 1) return fail(AZX_EINVAL, "a tournament needs at least one pair (pair_a, pair_b, n_pairs)");
+    if (first_game < 0 || rounds < 1 || tables_per_pair < 1)
+        return fail(AZX_EINVAL, "first_game must be >= 0, rounds >= 1 and tables_per_pair >= 1");
+    const int K = (int)t->eng.size(), P = n_pairs, T = tables_per_pair;
+    // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
+    std::vector<int> deg((size_t)K, 0);
+    std::vector<TourTable> tab((size_t)P * T);
+    for (int s = 0; s < P; ++s) {
+        const int a = pair_a[s], b = pair_b[s];
+        if (a < 0 || a >= K || b < 0 || b >= K)
+            return fail(AZX_EINVAL, "pair %d = (%d, %d): engine index out of range (%d engines)", s, a, b, K);
+        if (a == b) return fail(AZX_EINVAL, "pair %d = (%d, %d): an engine cannot play itself (a == b)", s, a, b);
+        for (int r = 0; r < s; ++r)
+            if ((pair_a[r] == a && pair_b[r] == b) || (pair_a[r] == b && pair_b[r] == a))
+                return fail(AZX_EINVAL, "pair %d = (%d, %d) repeats pair %d = (%d, %d)", s, a, b, r, pair_a[r], pair_b[r]);
+        for (int l = 0; l < T; ++l)
+            tab[(size_t)s * T + l] = TourTable{a, deg[a] * T + l, b, deg[b] * T + l, s, l};
+        deg[a] += 1;
+        deg[b] += 1;
+    }
+    int max_g = 0;
+    for (int k = 0; k < K; ++k) {
+        if ((int64_t)deg[k] * T > t->eng[k]->d.G)
+            return fail(AZX_EINVAL, "engine %d has n_games = %d slots, its %d pairs at %d tables each need %lld", k,
+                        t->eng[k]->d.G, deg[k], T, (long long)deg[k] * T);
+        max_g = std::max(max_g, t->eng[k]->d.G);
+    }
+    const int64_t n_games = (int64_t)P * rounds, n_tables = (int64_t)P * T;
+    if (n_tables > (1 << 24)) return fail(AZX_EINVAL, "%lld tables are more than a tournament takes", (long long)n_tables);
+    azx_engine *e0 = t->eng[0];
+    ENGINE_GUARD(e0);
+    for (int k = 0; k < K; ++k) {
+        if (const char *why = match_engine_problem(t->eng[k])) return fail(AZX_ESTATE, "engine %d %s", k, why);
+        TRY(ext_refuse(t->eng[k]));
+    }
+    if (stats) memset(stats, 0, sizeof *stats * (size_t)P);
+    const int ncells = e0->d.ncells;
+    const hipStream_t s0 = e0->stream;
+    // the move draw records a replay row per draw (choose_body): the row area must exist (as in azx_match_play)
+    for (azx_engine *e : t->eng) {
+        TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
+        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
+    }
+    TRY(tour_grow(&t->tab_dev, &t->tab_cap, n_tables, "tables"));
+    TRY(tour_grow(&t->t.tab_game, &t->game_cap, n_tables, "table games"));
+    TRY(tour_grow(&t->t.ctr, &t->ctr_cap, (int64_t)(P + 1) * MCTR_COUNT, "counters"));
+    TRY(tour_grow(&t->t.outcome, &t->out_cap, n_games, "outcomes"));
+    TRY(tour_grow(&t->t.length, &t->len_cap, n_games, "lengths"));
+    int16_t *moves_dev = nullptr;
+    if (moves) {
+        TRY(tour_grow(&t->t.moves, &t->moves_cap, n_games * ncells, "move records"));
+        moves_dev = t->t.moves;
+    }
+    TourDev D = t->t;
+    D.eng = t->eng_dev;
+    D.tab = t->tab_dev;
+    D.n_engines = K;
+    D.n_pairs = P;
+    D.n_tables = (int32_t)n_tables;
+    D.max_g = max_g;
+    D.first_game = first_game;
+    D.rounds = rounds;
+    D.moves = moves_dev;
+    std::vector<DevEngine> devs;
+    for (azx_engine *e : t->eng) devs.push_back(e->d);
+    std::vector<unsigned long long> ctr0((size_t)(P + 1) * MCTR_COUNT, 0ull);
+    for (int s = 0; s < P; ++s) ctr0[(size_t)s * MCTR_COUNT + MCTR_NEXT] = (unsigned long long)std::min<int64_t>(T, rounds);
+    HIPCHECK(hipMemcpyAsync(t->eng_dev, devs.data(), sizeof(DevEngine) * (size_t)K, hipMemcpyHostToDevice, s0));
+    HIPCHECK(hipMemcpyAsync(t->tab_dev, tab.data(), sizeof(TourTable) * tab.size(), hipMemcpyHostToDevice, s0));
+    HIPCHECK(hipMemcpyAsync(D.ctr, ctr0.data(), sizeof(unsigned long long) * ctr0.size(), hipMemcpyHostToDevice, s0));
+    if (D.moves) HIPCHECK(hipMemsetAsync(D.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, s0));
+    // fresh games in every slot of every engine (no generation is used up: the uids are the tournament's)
+    for (azx_engine *e : t->eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 0, s0);
+    azx_launch_tour_init(D, s0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s0));                  // (the uploads are from this frame)
+    HIPCHECK(hipEventRecord(t->t0, s0));
+
+    // every game ends within `cells` plies and a table plays its pair's games back to back
+    const int64_t max_plies = ((rounds + T - 1) / T + 1) * (int64_t)(ncells + 1);
+    int64_t plies = 0;
+    for (;; ++plies) {
+        if (plies > max_plies)
+            return fail(AZX_ESTATE, "tournament: %lld plies without deciding all %lld games (internal error)",
+                        (long long)plies, (long long)n_games);
+        azx_launch_tour_turn(D, s0);
+        HIPCHECK(hipEventRecord(t->ev_fork, s0));
+        for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(t->eng[k]->stream, t->ev_fork, 0));
+        TRY(tour_ply_searches(t));
+        for (int k = 1; k < K; ++k) {
+            HIPCHECK(hipEventRecord(t->ev_join[k - 1], t->eng[k]->stream));
+            HIPCHECK(hipStreamWaitEvent(s0, t->ev_join[k - 1], 0));
+        }
+        azx_launch_tour_step(D, e0->d.slots, s0);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(t->host_word, D.ctr + (size_t)P * MCTR_COUNT + MCTR_DECIDED, sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, s0));
+        // the error word of each external search's last import rides on the same read-back (every stream has joined)
+        for (azx_engine *e : t->eng)
+            if (ext_registered(e)) TRY(ext_info_enqueue(e, s0));
+        HIPCHECK(hipStreamSynchronize(s0));
+        for (int k = 0; k < K; ++k)
+            if (ext_registered(t->eng[k])) TOUR_TRY(k, ext_info_take(t->eng[k]));
+        if (*t->host_word >= (unsigned long long)n_games) break;
+    }
+    HIPCHECK(hipEventRecord(t->t1, s0));
+
+    std::vector<unsigned long long> ctr((size_t)P * MCTR_COUNT);
+    HIPCHECK(hipMemcpyAsync(ctr.data(), D.ctr, sizeof(unsigned long long) * ctr.size(), hipMemcpyDeviceToHost, s0));
+    if (outcome) HIPCHECK(hipMemcpyAsync(outcome, D.outcome, (size_t)n_games, hipMemcpyDeviceToHost, s0));
+    if (length) HIPCHECK(hipMemcpyAsync(length, D.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, s0));
+    if (moves) HIPCHECK(hipMemcpyAsync(moves, D.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, s0));
+    // leave every engine as azx_reset leaves it: fresh games, all active, its own uid numbering
+    for (azx_engine *e : t->eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 1, s0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s0));
+    if (stats) {
+        float ms = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms, t->t0, t->t1));
+        for (int s = 0; s < P; ++s) {
+            const unsigned long long *c = ctr.data() + (size_t)s * MCTR_COUNT;
+            stats[s].games = (int64_t)c[MCTR_DECIDED];
+            stats[s].wins[0] = (int64_t)c[MCTR_WINS0];
+            stats[s].wins[1] = (int64_t)c[MCTR_WINS1];
+            stats[s].first_player_wins = (int64_t)c[MCTR_FIRST_WINS];
+            stats[s].voided = (int64_t)c[MCTR_VOIDED];
+            stats[s].plies = (int64_t)c[MCTR_PLIES];
+            stats[s].seconds = ms * 1e-3;
+        }
+    }
+    for (azx_engine *e : t->eng) TRY(check_net_range(e));
+    return AZX_OK;
+}
+
 // ---- native training step (train_kernels.hip) ----------------------------------------------------------------
 struct azx_trainer {
     AzxTrain *t = nullptr;

@@ -27,3 +27,34 @@ void azx_launch_match_init(const DevEngine &A, const DevEngine &B, const MatchDe
 void azx_launch_match_turn(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st);
 // hand the mover's drawn move over, step both engines' slots, settle finished / voided games and refill
 void azx_launch_match_step(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st);
+
+// ---- tournaments (azx_tournament_*): P matches side by side in one ply loop, sharing K engines ----------------
+// A table plays one game of its pair at a time: slot sa of engine ea and slot sb of engine eb hold the two agents'
+// trees (ea is the pair's first engine, "agent 0").  The layout is static and computed on the host: an engine's
+// pool is partitioned among its opponents, so a table's two slots generally have different indices.
+struct TourTable {
+    int32_t ea, sa, eb, sb;        // engine index and slot of agent 0 / agent 1
+    int32_t pair, local;           // the pair the table plays for, and its index among that pair's tables
+};
+
+struct TourDev {
+    const DevEngine *eng;          // [n_engines] the engines' device structs, in device memory
+    const TourTable *tab;          // [n_tables], pair-major
+    int64_t *tab_game;             // [n_tables] game index u the table is playing, -1 = idle
+    int32_t n_engines, n_pairs, n_tables, max_g;   // max_g: the largest n_games of the engines
+    int64_t first_game, rounds;    // round r of pair s is game first_game + s * rounds + r
+    unsigned long long *ctr;       // [n_pairs + 1][MCTR_COUNT]: per pair, then the totals row (MCTR_DECIDED over all
+                                   // pairs: the one word the host reads back per ply)
+    int8_t *outcome;               // [n_pairs * rounds] by u - first_game, as MatchDev's
+    int16_t *length;               // [n_pairs * rounds]
+    int16_t *moves;                // [n_pairs * rounds][ncells]; null = not recorded
+};
+
+// every table takes its pair's round `local` (idle beyond `rounds`) and both its slots that game's uid; every slot
+// of every engine gets active = 0, so the slots no table owns are never searched
+void azx_launch_tour_init(const TourDev &T, hipStream_t st);
+// whose turn: GameHdr.active of each table's two slots (mover's 1, the other 0; idle tables 0 in both)
+void azx_launch_tour_turn(const TourDev &T, hipStream_t st);
+// k_match_step for a table: hand-over, game step in both slots, settle into the pair's tallies, refill from the
+// pair's own round counter.  `slots` is the engines' common cell-slot count (DevEngine::slots)
+void azx_launch_tour_step(const TourDev &T, int slots, hipStream_t st);

@@ -9,6 +9,8 @@
 // search_tree.py:115-132).  Here slot g of engine A and slot g of engine B hold the two agents' views of the same
 // game; these kernels decide whose turn it is, hand the drawn move over, settle finished games and refill the
 // slot, so that the host reads back one word per ply.  Plain stores and atomics only.
+// A tournament (azx_tournament_play, second half of this file) is P such matches side by side in one ply loop: the
+// same bookkeeping per table, a table's two slots being any slot of any two of K engines.
 #include "match_kernels.h"
 
 // agent (0 = engine A, 1 = engine B) to move in game u at `ply`: agent u & 1 moves first
@@ -102,8 +104,8 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
                 ga->active = 1;     gb->active = 1;
             }
             wave_mem_sync();
-            advance_body<SLOTS>(A, nullptr, 0);
-            advance_body<SLOTS>(B, nullptr, 0);
+            advance_body<SLOTS>(A, g, nullptr, 0);
+            advance_body<SLOTS>(B, g, nullptr, 0);
             wave_mem_sync();
             winner = ga->winner;
             len = ply + 1;
@@ -149,5 +151,135 @@ void azx_launch_match_turn(const DevEngine &A, const DevEngine &B, const MatchDe
 void azx_launch_match_step(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
 #define CALL(S) hipLaunchKernelGGL((k_match_step<S>), dim3(A.G), dim3(64), 0, st, A, B, M)
     DISPATCH_SLOTS(A.slots, CALL);
+#undef CALL
+}
+
+// ============================================================================================
+// tournaments (azx_tournament_play): the same bookkeeping per TABLE.  The K engines' structs are read from a device
+// array (a kernel argument indexed by a table's engine number would live in scratch), and a table's two slots are
+// its descriptor's, not the block index.
+// ============================================================================================
+__global__ void k_tour_init(TourDev T) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    // no slot is searched unless k_tour_turn says so (k_reset left every slot active)
+    const int e = t / T.max_g, g = t - e * T.max_g;
+    if (e < T.n_engines && g < T.eng[e].G) T.eng[e].ghdr[g].active = 0;
+    if (t >= T.n_tables) return;
+    const TourTable tb = T.tab[t];
+    const int64_t u = tb.local < T.rounds ? T.first_game + (int64_t)tb.pair * T.rounds + tb.local : -1;
+    T.tab_game[t] = u;
+    if (u >= 0) {
+        T.eng[tb.ea].ghdr[tb.sa].uid = u;
+        T.eng[tb.eb].ghdr[tb.sb].uid = u;
+    }
+}
+
+__global__ void k_tour_turn(TourDev T) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T.n_tables) return;
+    const TourTable tb = T.tab[t];
+    GameHdr *ga = T.eng[tb.ea].ghdr + tb.sa, *gb = T.eng[tb.eb].ghdr + tb.sb;
+    const int64_t u = T.tab_game[t];
+    int a = 0, b = 0;
+    if (u >= 0) {
+        const int mover = match_mover(u, ga->ply);
+        a = mover == 0;
+        b = mover == 1;
+    }
+    ga->active = a;
+    gb->active = b;
+}
+
+// One wave per table, after all engines' searches and move draws of this ply.
+template <int SLOTS>
+__global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
+    const int lane = threadIdx.x;
+    const int t = blockIdx.x;
+    const int64_t u = T.tab_game[t];
+    if (u < 0) return;                                         // idle table
+    const TourTable tb = T.tab[t];
+    const DevEngine &A = T.eng[tb.ea], &B = T.eng[tb.eb];
+    const int sa = tb.sa, sb = tb.sb;
+    GameHdr *ga = A.ghdr + sa, *gb = B.ghdr + sb;
+    const int ply = ga->ply;                                   // (the two slots hold the same game)
+    const int ncells = A.ncells;
+    const int first = (int)(u & 1);
+    const int mover = match_mover(u, ply);
+    const int mid = mover ? gb->move_id : ga->move_id;
+    const int status = mover ? B.thdr[sb].status : A.thdr[sa].status;
+    bool voided = status != 0 || mid < 0;                      // as k_match_step
+    const int64_t idx = u - T.first_game;
+    int winner = 0, len = ply;
+
+    if (!voided) {
+        HexWave<SLOTS> h;
+        h.load(A.cells + (size_t)sa * SLOTS * 64, lane);
+        h.color = ga->color;
+        h.winner = ga->winner;
+        const Masks<SLOTS> mk = make_masks<SLOTS>(h, lane, ncells);
+        int cell = -1;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint64_t hit = __ballot(lane_bit(mk.m[s]) && mk.base[s] + rank_below(mk.m[s]) == mid);
+            if (hit) cell = s * 64 + (int)__ffsll((long long)hit) - 1;
+        }
+        if (cell < 0 || ply >= ncells) {
+            voided = true;
+        } else {
+            if (lane == 0) {
+                if (T.moves) T.moves[(size_t)idx * ncells + ply] = (int16_t)(cell + 1);
+                ga->move_id = mid;  gb->move_id = mid;
+                ga->active = 1;     gb->active = 1;
+            }
+            wave_mem_sync();
+            advance_body<SLOTS>(A, sa, nullptr, 0);
+            advance_body<SLOTS>(B, sb, nullptr, 0);
+            wave_mem_sync();
+            winner = ga->winner;
+            len = ply + 1;
+        }
+    }
+    if (!voided && winner == 0) return;                        // the game goes on
+
+    // ---- settle into the pair's tallies; the pair's next round for this table ----
+    long long next_u = -1;
+    if (lane == 0) {
+        unsigned long long *ctr = T.ctr + (size_t)tb.pair * MCTR_COUNT;
+        int outcome = 0;
+        if (!voided) {
+            const int won = winner == 1 ? first : 1 - first;   // colour 1 = the first mover
+            outcome = won == 0 ? 1 : -1;
+            atomicAdd(ctr + (won == 0 ? MCTR_WINS0 : MCTR_WINS1), 1ull);
+            if (winner == 1) atomicAdd(ctr + MCTR_FIRST_WINS, 1ull);
+        } else {
+            atomicAdd(ctr + MCTR_VOIDED, 1ull);
+        }
+        T.outcome[idx] = (int8_t)outcome;
+        T.length[idx] = (int16_t)len;
+        atomicAdd(ctr + MCTR_PLIES, (unsigned long long)len);
+        atomicAdd(ctr + MCTR_DECIDED, 1ull);
+        atomicAdd(T.ctr + (size_t)T.n_pairs * MCTR_COUNT + MCTR_DECIDED, 1ull);
+        const unsigned long long nx = atomicAdd(ctr + MCTR_NEXT, 1ull);
+        next_u = nx < (unsigned long long)T.rounds ? T.first_game + (long long)tb.pair * T.rounds + (long long)nx : -1;
+        T.tab_game[t] = next_u;
+    }
+    next_u = ((long long)__builtin_amdgcn_readfirstlane((int)(next_u >> 32)) << 32) |
+             (unsigned int)__builtin_amdgcn_readfirstlane((int)next_u);
+    match_restart<SLOTS>(A, sa, next_u, lane);
+    match_restart<SLOTS>(B, sb, next_u, lane);
+}
+
+void azx_launch_tour_init(const TourDev &T, hipStream_t st) {
+    const int n = T.n_tables > T.n_engines * T.max_g ? T.n_tables : T.n_engines * T.max_g;
+    hipLaunchKernelGGL(k_tour_init, dim3((n + 255) / 256), dim3(256), 0, st, T);
+}
+
+void azx_launch_tour_turn(const TourDev &T, hipStream_t st) {
+    hipLaunchKernelGGL(k_tour_turn, dim3((T.n_tables + 255) / 256), dim3(256), 0, st, T);
+}
+
+void azx_launch_tour_step(const TourDev &T, int slots, hipStream_t st) {
+#define CALL(S) hipLaunchKernelGGL((k_tour_step<S>), dim3(T.n_tables), dim3(64), 0, st, T)
+    DISPATCH_SLOTS(slots, CALL);
 #undef CALL
 }

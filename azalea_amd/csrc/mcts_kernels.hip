@@ -375,19 +375,20 @@ __device__ __forceinline__ void compact_tree(const DevEngine &E, int g, TreeHdr 
             const int total = kL * np;
             const float inv_k = 1.0f / (float)kL;
             for (int t0 = 0; t0 < total; t0 += 256) {
-                Node v[4];
+                uint4 v[4];      // (a Node as one 16-byte word: the compiler keeps an array of the struct in scratch and LDS)
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int t = t0 + u * 64 + lane;
+                    v[u] = make_uint4(0u, 0u, 0u, 0u);
                     if (t < total) {
                         const int pp = (int)(((float)t + 0.5f) * inv_k);   // t / kL (exact: t < 2^14)
-                        v[u] = src[sh_old[pp] + (t - pp * kL)];
+                        v[u] = *reinterpret_cast<const uint4 *>(src + sh_old[pp] + (t - pp * kL));
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int t = t0 + u * 64 + lane;
-                    if (t < total) dst[n_new + t] = v[u];
+                    if (t < total) *reinterpret_cast<uint4 *>(dst + n_new + t) = v[u];
                 }
             }
             lds_sync();
@@ -1450,10 +1451,9 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
 // In play mode a finished game is appended to the output queue and the slot restarts.
 // ============================================================================================
 template <int SLOTS>
-__device__ __forceinline__ void advance_body(const DevEngine &E, const int32_t *move_ids, int play_mode) {
+__device__ __forceinline__ void advance_body(const DevEngine &E, int g, const int32_t *move_ids, int play_mode) {
     __shared__ int sh_old[64];         // compaction: old first-child ids of a group's parents, by rank
     const int lane = threadIdx.x;
-    const int g = blockIdx.x;
     GameHdr *gh = E.ghdr + g;
     TreeHdr *th = E.thdr + g;
     // play_mode 2 = unpark: only the slots whose finished game found the harvest queue full take part,
@@ -1633,7 +1633,7 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, const int32_t *
 // ============================================================================================
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_advance(DevEngine E, const int32_t *move_ids, int play_mode) {
-    advance_body<SLOTS>(E, move_ids, play_mode);
+    advance_body<SLOTS>(E, blockIdx.x, move_ids, play_mode);
 }
 
 template <int SLOTS>
@@ -1828,7 +1828,7 @@ __global__ __launch_bounds__(64) AZX_MCTS_ATTR void k_play(DevEngine E, int num_
 #endif
         TP(1, choose_body<SLOTS>(*Ec))
         wave_mem_sync();
-        TP(2, advance_body<SLOTS>(*Ec, nullptr, 1))
+        TP(2, advance_body<SLOTS>(*Ec, blockIdx.x, nullptr, 1))
         wave_mem_sync();
     }
 #ifdef AZX_STAMP_PLAY

@@ -563,6 +563,75 @@ class Match:
         return out
 
 
+class Tournament:
+    """azx_tournament_*: several matches side by side in ONE ply loop on the device, sharing engines.  `pairs` names
+    engines by their index in `engines`; pair s = (i, j) plays, bit for bit, the games of
+    Match(engines[i], engines[j]).play(rounds, first_game=first_game + s * rounds) -- engine i is its agent 0 -- while
+    every engine searches the slots of all its pairs together.  Every pair gets `tables_per_pair` tables (games in
+    flight); an engine that is in d pairs needs n_games >= d * tables_per_pair slots.  The engines stay the caller's,
+    as with Match; an exception raised by an engine's external evaluator is re-raised from play()."""
+
+    def __init__(self, engines):
+        self.L = _lib.lib()
+        self.engines = list(engines)
+        self.h = C.c_void_p()
+        arr = (C.c_void_p * max(len(self.engines), 1))(*[e.h for e in self.engines])
+        check(self.L.azx_tournament_create(arr, len(self.engines), C.byref(self.h)))
+        self.cells = self.engines[0].cells
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.azx_tournament_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def play(self, pairs, rounds, first_game=0, tables_per_pair=None, moves=False):
+        """`rounds` games of every pair, each to its end.  Returns {pair: dict(outcome int8[rounds], length
+        int16[rounds], stats[, moves int16[rounds, cells]])} in the order of `pairs`, each as Match.play returns it
+        (stats['seconds'] is the whole call's device time).  tables_per_pair defaults to the most every engine has
+        room for, at most `rounds`."""
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        P, rounds = len(pairs), int(rounds)
+        if tables_per_pair is None:
+            deg = [sum(k in p for p in pairs) for k in range(len(self.engines))]
+            room = [e.G // d for e, d in zip(self.engines, deg) if d]
+            tables_per_pair = max(1, min([rounds] + room))
+        n = max(P * rounds, 0)
+        outcome = np.zeros(n, np.int8)
+        length = np.zeros(n, np.int16)
+        mv = np.zeros((n, self.cells), np.int16) if moves else None
+        st = (MatchStats * max(P, 1))()
+        pa = np.array([p[0] for p in pairs], np.int32)
+        pb = np.array([p[1] for p in pairs], np.int32)
+        for e in self.engines:
+            e._ext_exc = None
+        rc = self.L.azx_tournament_play(self.h, P, _p(pa, C.c_int32), _p(pb, C.c_int32), int(first_game), rounds,
+                                        int(tables_per_pair), _p(outcome, C.c_int8), _p(length, C.c_int16),
+                                        _p(mv, C.c_int16), st)
+        # what an engine's evaluator raised inside the call surfaces itself, chained to the AzxError (as Match.play)
+        exc = next((e._ext_exc for e in self.engines if e._ext_exc is not None), None)
+        for e in self.engines:
+            e._ext_exc = None
+        if rc != 0 and exc is not None:
+            try:
+                check(rc)
+            except AzxError as err:
+                raise exc from err
+        check(rc)
+        out = {}
+        for s, pair in enumerate(pairs):
+            sl = slice(s * rounds, (s + 1) * rounds)
+            out[pair] = dict(outcome=outcome[sl], length=length[sl], stats=st[s].as_dict())
+            if moves:
+                out[pair]["moves"] = mv[sl]
+        return out
+
+
 def hex_replay(board_size, moves, lengths, device=0):
     """azx_hex_replay: per-ply result / legal count / empties mask for many move lists."""
     mv = np.ascontiguousarray(moves, np.int32)

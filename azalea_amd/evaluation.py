@@ -217,7 +217,7 @@ def _throughput_policy(agent, external_batch=False):
 
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
-                        games=None, external_batch: bool = False) -> Dict[Pair, OutcomeCounts]:
+                        games=None, external_batch: bool = False, pooled: bool = False) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -230,7 +230,11 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     `external_batch`: an agent whose Policy holds a network other than HexNetwork, on a CUDA (ROCm) device, plays
     through an EVAL_EXTERNAL engine with policy.external_evaluator(net) registered: its net gets the leaf batches
     of all the slots in which it is the mover, on the device, at every evaluation point (ValueError when the
-    network is not on such a device).  Agents with a HexNetwork keep the device tower, so fields may be mixed."""
+    network is not on such a device).  Agents with a HexNetwork keep the device tower, so fields may be mixed.
+    `pooled`: play all pairs in ONE ply loop (engine.Tournament, azx_tournament_play) instead of one match per pair
+    after the other: the same games, tallies and `games` records, bit for bit.  `n_slots` stays "slots per engine"
+    (default min((K - 1) * num_rounds, AZX_GAMES or 4096), rounded up to even): every engine's pool is shared out
+    among its K - 1 opponents, max(1, n_slots // (K - 1)) tables per pair."""
     import torch
     from . import engine as _eng
     from .policy import SearchTreeFull, external_evaluator
@@ -243,9 +247,13 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     if len(agents) > 256 or len(pairs) * num_rounds >= 1 << 32 or not 0 <= int(seed) < 1 << 24:
         raise ValueError("evaluate_throughput: at most 256 agents, 2^32 games and a seed below 2^24")
     n = agents[0].game.board_size
+    opponents = max(1, len(agents) - 1)
     if n_slots is None:
-        n_slots = min(num_rounds, int(os.environ.get("AZX_GAMES", "4096")))
+        n_slots = min((opponents if pooled else 1) * num_rounds, int(os.environ.get("AZX_GAMES", "4096")))
     n_slots = max(2, int(n_slots) + (int(n_slots) & 1))
+    if pooled:
+        tables_per_pair = max(1, n_slots // opponents)
+        n_slots = max(n_slots, tables_per_pair * opponents)      # (fewer slots than opponents: one table per pair)
     engines = []
     try:
         for a, pol in enumerate(pols):
@@ -288,12 +296,21 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
             else:
                 eng.set_weights({k: v.detach().cpu().numpy() for k, v in sd.items()})
         outcomes: Dict[Pair, OutcomeCounts] = defaultdict(lambda: [0, 0, 0])
-        for s, (i, j) in enumerate(pairs):
-            match = _eng.Match(engines[i], engines[j])
+        results = {}
+        if pooled:
+            tour = _eng.Tournament(engines)
             try:
-                res = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None)
+                results = tour.play(pairs, num_rounds, tables_per_pair=tables_per_pair, moves=games is not None)
             finally:
-                match.close()
+                tour.close()
+        for s, (i, j) in enumerate(pairs):
+            if not pooled:
+                match = _eng.Match(engines[i], engines[j])
+                try:
+                    results[(i, j)] = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None)
+                finally:
+                    match.close()
+            res = results[(i, j)]
             st = res["stats"]
             if st["voided"]:
                 raise SearchTreeFull("too many nodes")
@@ -301,7 +318,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
             if games is not None:
                 games[(i, j)] = {k: res[k] for k in ("outcome", "length", "moves")}
             logging.info("pair %s: outcomes %s (%.1f games/s on the device)", (i, j), outcomes[(i, j)],
-                         num_rounds / max(st["seconds"], 1e-9))
+                         (len(pairs) if pooled else 1) * num_rounds / max(st["seconds"], 1e-9))
         return outcomes
     finally:
         for eng in engines:

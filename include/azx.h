@@ -456,6 +456,48 @@ void azx_match_destroy(azx_match *m);
 int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *outcome, int16_t *length,
                    int16_t *moves, azx_match_stats *stats);
 
+/* ---- tournaments: several matches side by side in one ply loop, sharing engines ----------------------------------
+ * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_tournament_create).
+ * The reference hands every round's pairs to its pool at once (azalea/evaluation.py:29-58).  A tournament joins
+ * n_engines >= 2 existing engines; azx_tournament_play then plays a list of n_pairs pairs of them -- a round robin, a
+ * gauntlet of one candidate against N others, any list without a repeated pair -- as n_pairs matches that share ONE
+ * ply loop.  A small match is latency-bound (a ply costs about simulations / search_batch_size + 1 dependent tree ->
+ * tower -> heads rounds however few rows they carry); here each engine searches the slots of ALL its pairs together,
+ * one leaf batch per engine per evaluation point, and the K engines' searches run side by side on their own streams.
+ * azx_tournament_create checks what azx_match_create checks -- same device, same board_size, evaluator ready, no engine
+ * given twice (AZX_EINVAL) -- but NOT equal n_games: every engine needs room for its own pairs only.
+ *
+ * Layout: every pair gets tables_per_pair tables; a table plays one game of its pair at a time and refills from that
+ * pair's own round counter.  An engine's pool is partitioned among its opponents: engine i, in d_i pairs, uses slots
+ * 0 .. d_i * tables_per_pair - 1 -- the table `l` of its r-th pair (in list order) is its slot r * tables_per_pair + l
+ * -- and its other slots stay idle (never searched).  The two slots of a table generally have different indices.
+ *
+ * Games: round r of pair s = (pair_a[s], pair_b[s]) is game u = first_game + s * rounds + r; both engines use uid = u;
+ * engine pair_a[s] is agent 0 of the rules under azx_match_play above (agent u & 1 moves first, outcome +1 = agent 0
+ * won, SearchTreeFull in the searching engine voids the game).  So pair s plays, bit for bit, the games of
+ * azx_match_play(match of its two engines, first_game + s * rounds, rounds): they depend neither on tables_per_pair,
+ * nor on the other pairs, nor on how many slots the engines have.
+ * Outputs, indexed by u - first_game = s * rounds + r, any may be NULL: outcome[n_pairs * rounds],
+ * length[n_pairs * rounds], moves[n_pairs * rounds][cells]; stats[n_pairs], per pair as azx_match_stats (wins[0] =
+ * engine pair_a[s]), except that `seconds` is the whole call's device time in every entry.
+ * AZX_EINVAL: a pair with a == b, a pair that repeats (in either order), an index out of range, rounds < 1,
+ * tables_per_pair < 1, or an engine whose n_games < d_i * tables_per_pair (the message names the engine and both
+ * numbers).  AZX_ESTATE as for azx_match_play (evaluator unregistered since, an earlier external failure).
+ * The call resets all slots of all engines at entry and leaves them as azx_reset leaves them; it writes no replay
+ * rows.  It blocks.  Per ply the host reads back one counter (the games decided over all pairs), plus the info words
+ * of each engine with a registered evaluator; nothing it transfers grows with the slot count.  Engines with a
+ * registered evaluator take part as in a match: per ply the host first enqueues every device-evaluated engine's whole
+ * search and draw, then advances all external engines' searches point by point in turn.  A failure of an evaluator
+ * fails the call with AZX_EEXTERNAL (the message names the engine's index); that engine then refuses search, play,
+ * match and tournament calls until all its slots have been azx_reset.  The engines must outlive the tournament;
+ * while azx_tournament_play runs they all belong to the calling thread. */
+typedef struct azx_tournament azx_tournament;
+int azx_tournament_create(azx_engine *const *engines, int n_engines, azx_tournament **out);
+void azx_tournament_destroy(azx_tournament *t);
+int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                        int64_t first_game, int64_t rounds, int32_t tables_per_pair,
+                        int8_t *outcome, int16_t *length, int16_t *moves, azx_match_stats *stats);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

@@ -27,7 +27,19 @@ the PyTorch forward of a 6x64 HexNetwork -- and nothing of the above:
 
     python tools/bench_match.py --external [--ext-games 256] [--ext-slots 256] [--host-games 2] [--repeats 3]
 One JSON line (profiles/match_external_bench.json).  `--external --trace-run`: two matches of the two custom agents and
-nothing else, for `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_match.py ...`."""
+nothing else, for `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_match.py ...`.
+
+`--tournament`: the round robin as ONE device-resident tournament (evaluate_throughput(pooled=True): engine.Tournament,
+azx_tournament_*) against the pairs played one after the other (pooled=False), and nothing of the above:
+  (f) three agents, `--rr-rounds` rounds: 100 slots per engine for the pairs loop, 200 (100 tables per pair) pooled
+  (g) `--tour-agents` agents, `--tour-rounds` rounds (8 and 20: 28 pairs, 560 games; 20 slots per engine for the pairs
+      loop, 140 -- 20 tables per pair -- pooled)
+each `--repeats` times, alternating, medians of the wall time with the set-up included, and the spread (max - min) /
+median of either.  The tallies of the two schedules are the same games, and are checked to be.
+
+    python tools/bench_match.py --tournament [--rr-rounds 100] [--tour-agents 8] [--tour-rounds 20] [--repeats 3]
+One JSON line (profiles/tournament_bench.json).  `--tournament --trace-run`: two pooled runs of (g) and nothing else,
+for the profiler as above."""
 import argparse
 import json
 import os
@@ -49,9 +61,9 @@ from azalea_amd.policy import Policy
 BOARD = 11
 
 
-def agents(sims):
+def agents(sims, count=3):
     out = []
-    for seed in (1, 2, 3):
+    for seed in range(1, count + 1):
         torch.manual_seed(seed)
         p = Policy()
         p.initialize(dict(device="cuda:0", network="HexNetwork", board_size=BOARD, num_blocks=6, base_chans=64,
@@ -185,6 +197,52 @@ def external_main(args):
     print(json.dumps(res))
 
 
+def tournament_main(args):
+    K, R = args.tour_agents, args.tour_rounds
+    ag = agents(args.sims, max(3, K))
+    res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
+           "device": torch.cuda.get_device_name(0), "repeats": args.repeats}
+
+    def run(field, rounds, pooled):
+        k = len(field)
+        n_slots = (k - 1) * rounds if pooled else rounds
+        t, out = timed(lambda: evaluation.evaluate_throughput(field, rounds, n_slots=n_slots, pooled=pooled))
+        print("%d agents, %d rounds, %s: %.2f s" % (k, rounds, "pooled" if pooled else "pairs", t), file=sys.stderr, flush=True)
+        return t, tallies(out)
+
+    if args.trace_run:      # the program to put behind `rocprofv3 --kernel-trace --stats --`
+        run(ag[:K], R, True)
+        t, _ = run(ag[:K], R, True)
+        print(json.dumps({"agents": K, "rounds": R, "games": K * (K - 1) // 2 * R, "seconds": t}))
+        return
+    # warm both paths once (allocator, kernel load) on a handful of games
+    run(ag[:3], 4, False)
+    run(ag[:3], 4, True)
+
+    def leg(field, rounds):
+        k = len(field)
+        n = k * (k - 1) // 2 * rounds
+        t_pairs, t_pooled = [], []
+        for _ in range(args.repeats):
+            t, out_pairs = run(field, rounds, False)
+            t_pairs.append(t)
+            t, out_pooled = run(field, rounds, True)
+            t_pooled.append(t)
+            assert out_pooled == out_pairs, "the pooled schedule played other games"
+        med = statistics.median
+        return {"agents": k, "rounds": rounds, "games": n, "slots_per_engine_pairs": rounds,
+                "slots_per_engine_pooled": (k - 1) * rounds, "tables_per_pair": rounds,
+                "pairs_seconds": t_pairs, "pooled_seconds": t_pooled,
+                "pairs_games_per_sec": n / med(t_pairs), "pooled_games_per_sec": n / med(t_pooled),
+                "spread_pairs": (max(t_pairs) - min(t_pairs)) / med(t_pairs),
+                "spread_pooled": (max(t_pooled) - min(t_pooled)) / med(t_pooled),
+                "pairs_over_pooled_seconds": med(t_pairs) / med(t_pooled), "tallies": out_pooled}
+
+    res["round_robin_3"] = leg(ag[:3], args.rr_rounds)        # (f)
+    res["ladder"] = leg(ag[:K], R)                            # (g)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--external", action="store_true")
@@ -199,9 +257,14 @@ def main():
     ap.add_argument("--big-slots", type=int, default=4096)
     ap.add_argument("--selfplay-steps", type=int, default=30)
     ap.add_argument("--rr-rounds", type=int, default=100)
+    ap.add_argument("--tournament", action="store_true")
+    ap.add_argument("--tour-agents", type=int, default=8)
+    ap.add_argument("--tour-rounds", type=int, default=20)
     args = ap.parse_args()
     if args.external:
         return external_main(args)
+    if args.tournament:
+        return tournament_main(args)
     ag = agents(args.sims)
     two = ag[:2]
     res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
