@@ -124,6 +124,7 @@ SYMBOLS = {
     "azx_debug_counters_raw": (C.c_int, [_vp, _u64p, C.c_int64]),
     "azx_kernel_info": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "azx_debug_set_queue_cap": (C.c_int, [_vp, C.c_int64]),
+    "azx_debug_stagger": (C.c_int, [_vp, _i32p]),
     "azx_stream": (_vp, [_vp]),
     "azx_set_external_evaluator": (C.c_int, [_vp, _vp, _vp]),   # fn passed as a pointer (NULL = unregister)
     "azx_match_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -152,6 +153,10 @@ SYMBOLS.update({
     "azx_train_step": (C.c_int, [_vp, C.c_float, C.c_float, C.c_float, _vp]),
     "azx_train_debug": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, _i64p]),
 })
+
+# entry points that a library may lack without lib() refusing it.  Empty for the package itself: a tool that loads an
+# older build in this package's place (tools/lib_bench.py) names the later additions here before the first lib().
+OPTIONAL = set()
 
 _lib = None
 
@@ -188,6 +193,8 @@ def lib():
                 logging.getLogger(__name__).debug("torch pre-initialisation skipped: %r", exc)
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
+            if name in OPTIONAL and not hasattr(L, name):
+                continue
             fn = getattr(L, name)   # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

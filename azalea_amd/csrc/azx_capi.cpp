@@ -118,10 +118,12 @@ struct azx_engine {
     bool force_generic = false;         // AZX_MCTS_GENERIC: every tree launch on the generic instantiation
     bool no_persistent = false;         // AZX_NO_PERSISTENT: per-move launches instead of k_play
     bool pipeline = true;               // AZX_PIPELINE=0: the resnet play loop on one stream (no half-pools)
+    bool stagger = true;                // AZX_PIPELINE_STAGGER=0: half B's evaluations never wait for half A's
     // pipelined play: the second half-pool's stream, made on first use on the engine stream's CU mask
     hipStream_t stream_b = nullptr;
     std::vector<uint32_t> cu_mask;      // azx_reserve_cus's mask (empty = all CUs)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
+    int32_t *stagger_ctr = nullptr;     // azx_net_eval_rows_behind's count and azx_debug_stagger's counters (4 ints)
     int64_t dbg_qcap = 0;               // azx_debug_set_queue_cap
 };
 
@@ -194,6 +196,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     { const char *v = getenv("AZX_MCTS_GENERIC"); e->force_generic = v && atoi(v) != 0; }
     { const char *v = getenv("AZX_NO_PERSISTENT"); e->no_persistent = v && atoi(v) != 0; }
     { const char *v = getenv("AZX_PIPELINE"); e->pipeline = !(v && atoi(v) == 0); }
+    { const char *v = getenv("AZX_PIPELINE_STAGGER"); e->stagger = !(v && atoi(v) == 0); }
     HIPCHECK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     DevEngine &d = e->d;
     memset(&d, 0, sizeof d);
@@ -289,6 +292,7 @@ extern "C" void azx_destroy(azx_engine *e) {
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+    if (e->ev_stagger) (void)hipEventDestroy(e->ev_stagger);
     if (e->stream_b) { (void)hipStreamSynchronize(e->stream_b); (void)hipStreamDestroy(e->stream_b); }
     for (int i = 0; i < 8; ++i) {
         if (e->cidx_ev[i]) { (void)hipEventSynchronize(e->cidx_ev[i]); (void)hipEventDestroy(e->cidx_ev[i]); }
@@ -387,6 +391,8 @@ static int pipeline_streams(azx_engine *e) {
     }
     if (!e->ev_fork) HIPCHECK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     if (!e->ev_join) HIPCHECK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+    if (!e->ev_stagger) HIPCHECK(hipEventCreateWithFlags(&e->ev_stagger, hipEventDisableTiming));
+    if (!e->stagger_ctr) TRY(dev_alloc(e, &e->stagger_ctr, 4));     // (zeroed on the engine stream, where half A uses it)
     return AZX_OK;
 }
 
@@ -394,7 +400,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
     if (!e || !buf || cap < 1) return fail(AZX_EINVAL, "null argument");
     const DevEngine &d = e->d;
     const int S = d.slots <= 2 ? 2 : 3;
-    char tree[96], play[128];
+    char tree[96], play[160];
     if (d.evaluator == AZX_EVAL_UNIFORM || d.evaluator == AZX_EVAL_UNIFORM_HASH) {
         // the FAST instantiation also needs the default prior table and device (or no) noise: decided per launch
         DevEngine probe = d;
@@ -405,18 +411,30 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                                                                        : "k_mcts + k_choose + k_advance per move");
     } else {
         snprintf(tree, sizeof tree, "k_mcts<%d,generic> (BEGIN / APPLY|SELECT / APPLY phases)", S);
-        snprintf(play, sizeof play, "%s", use_pipeline(e) ? "phases + k_choose + k_advance per move, two half-pools on two streams"
-                                                          : "phases + k_choose + k_advance per move, one stream");
+        snprintf(play, sizeof play, "%s", !use_pipeline(e) ? "phases + k_choose + k_advance per move, one stream"
+                                          : e->stagger     ? "phases + k_choose + k_advance per move, two half-pools on two streams half an evaluation apart (any tower)"
+                                                           : "phases + k_choose + k_advance per move, two half-pools on two streams");
     }
     std::string text = std::string("tree=") + tree + "; play=" + play + "; net=" +
                        (e->net ? azx_net_kernel_info(e->net) : "none") +
                        "; switches: AZX_MCTS_GENERIC=" + (e->force_generic ? "1" : "0") +
                        " AZX_NO_PERSISTENT=" + (e->no_persistent ? "1" : "0") +
                        " AZX_PIPELINE=" + (e->pipeline ? "1" : "0") +
+                       " AZX_PIPELINE_STAGGER=" + (e->stagger ? "1" : "0") +
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
+}
+
+extern "C" int azx_debug_stagger(azx_engine *e, int32_t *out4) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    memset(out4, 0, 4 * sizeof(int32_t));
+    if (!e->stagger_ctr) return AZX_OK;
+    HIPCHECK(hipMemcpyAsync(out4, e->stagger_ctr, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
 }
 
 extern "C" int azx_debug_set_queue_cap(azx_engine *e, int64_t rows) {
@@ -1252,8 +1270,17 @@ static int enqueue_ply(azx_engine *e) {
 // `plies` moves of the resnet play loop as two half-pools (use_pipeline): half A on the engine stream, half B on
 // stream_b.  Each half's phases follow each other on its own stream only; the host issues them phase by phase,
 // alternating the halves, so that one half's tower is queued while the other half runs its search phases.  Half B
-// starts after half A's first tree launch (everything queued on the engine stream before it included), which puts the
-// halves one phase apart from the start; the engine stream waits for half B at the end.
+// starts after half A's first tree launch (everything queued on the engine stream before it included), about 0.15 ms
+// behind: left alone, the halves' towers then start and end together phase after phase (two queues share the block
+// slots about equally), and so do their tail rounds, heads and tree launches.
+// The stagger (default; AZX_PIPELINE_STAGGER=0 leaves the start as above): in every move, half B's phase-1 evaluation
+// waits until the first `split` rows -- half -- of half A's phase-1 evaluation are done.  Phase 1's is a move's first
+// evaluation with a full batch of leaves (phase 0 evaluates fresh roots only: at most one row per game, none for a root
+// kept from the last move).  Half A's is issued as two launches, rows [0, split) and [split, rows), with the event
+// between them; every other phase is one launch per half.  The halves' towers then run about half a phase period
+// apart: one half's tail round, heads and tree launch fall into the middle of the other half's tower,
+// which has thousands of blocks waiting.  A half that is already further behind does not wait at all.
+// The engine stream waits for half B at the end.
 static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
     TRY(pipeline_streams(e));
     if (!azx_net_ready(e->net)) return fail(AZX_ESTATE, "azx_set_weights has not been called");
@@ -1262,6 +1289,8 @@ static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
     const DevEngine hv[2] = {pool_view(d, 0, half, d.n_eval), pool_view(d, half, half, d.n_eval + 1)};
     const hipStream_t hs[2] = {e->stream, e->stream_b};
     const int nb = e->num_batches;
+    const int split = rows / 2 / AZX_NET_ROW_ALIGN * AZX_NET_ROW_ALIGN;     // whole blocks of every tower and heads kernel
+    const bool stagger = e->stagger && split > 0;
     // the launch statistics count one phase's two half-pool launches as one launch of the whole pool
     const int ref = time_mark(e, hs[0]);
     for (int64_t p = 0; p < plies; ++p) {
@@ -1277,9 +1306,17 @@ static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
                     HIPCHECK(hipEventRecord(e->ev_fork, hs[0]));
                     HIPCHECK(hipStreamWaitEvent(hs[1], e->ev_fork, 0));
                 }
+                const bool cut = stagger && ph == 1;
+                if (cut && h == 1) HIPCHECK(hipStreamWaitEvent(hs[1], e->ev_stagger, 0));   // (recorded just below, for h == 0)
                 time_begin(e, 1, hs[h], g_net, ref);
-                azx_net_eval_rows(e->net, hv[h], h * rows, rows, hs[h]);
+                azx_net_eval_rows(e->net, hv[h], h * rows, cut && h == 0 ? split : rows, hs[h]);
                 time_end(e, 1, hs[h]);
+                if (cut && h == 0) {
+                    HIPCHECK(hipEventRecord(e->ev_stagger, hs[0]));
+                    time_begin(e, 1, hs[h], g_net, ref);        // (the same group: the phase still counts as one launch)
+                    azx_net_eval_rows_behind(e->net, hv[h], h * rows, split, rows, e->stagger_ctr, hs[h]);
+                    time_end(e, 1, hs[h]);
+                }
             }
         }
         const int g_tree = ++e->ev_groups;

@@ -28,6 +28,14 @@ void azx_net_eval(AzxNet *net, const DevEngine &d, hipStream_t st);
 // azx_net_rows_splittable (every tower but the wide one, whose layer launches run on side streams of their own)
 bool azx_net_rows_splittable(const AzxNet *net);
 void azx_net_eval_rows(AzxNet *net, const DevEngine &d, int row0, int max_n, hipStream_t st);
+// the requests at and behind row `first` of that view (first < max_n), as a launch of its own after
+// azx_net_eval_rows(net, d, row0, first, st) on the same stream: the two together evaluate what one call over max_n
+// rows evaluates.  The kernels are the same ones on offset pointers; their count max(0, *d.n_eval - first) is written
+// to ctr[0] by a one-thread kernel first (ctr: 4 ints of device scratch; [1..3] are azx_debug_stagger's), so the launch
+// does nothing when fewer than `first` requests are queued.
+// `first` must be a multiple of this: whole blocks of every tower and heads kernel (asserted in net_kernels.hip)
+constexpr int AZX_NET_ROW_ALIGN = 16;
+void azx_net_eval_rows_behind(AzxNet *net, const DevEngine &d, int row0, int first, int max_n, int32_t *ctr, hipStream_t st);
 // Network.run on host arrays (network.py:87-105): value[B], moves_logprob[B][K]
 int azx_net_forward_host(AzxNet *net, int B, int K, const int32_t *boards,
                          const int32_t *legal_moves, float *value, float *logprob, hipStream_t st);

@@ -1273,8 +1273,8 @@ __global__ __launch_bounds__(256, 2) void k_stem_wide_f16x3(NetDev P, const uint
 // generic VALU fallback (any channel count): one thread per output element, activations in HBM
 // ============================================================================================
 __global__ void k_stem_generic(NetDev P, const uint8_t *ev_board, const int32_t *n_eval_ptr,
-                               int n_eval_host, float *out) {
-    const int n_eval = n_eval_ptr ? *n_eval_ptr : n_eval_host;
+                               int n_eval_host, int max_n, float *out) {
+    const int n_eval = min(n_eval_ptr ? *n_eval_ptr : n_eval_host, max_n);     // (the launch's rows only: run_net)
     const int C = P.C, N = P.N, ncells = P.ncells;
     const size_t total = (size_t)n_eval * ncells * C;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -1295,8 +1295,8 @@ __global__ void k_stem_generic(NetDev P, const uint8_t *ev_board, const int32_t 
 }
 
 __global__ void k_conv_generic(NetDev P, int layer, const float *in, const float *residual,
-                               const int32_t *n_eval_ptr, int n_eval_host, float *out) {
-    const int n_eval = n_eval_ptr ? *n_eval_ptr : n_eval_host;
+                               const int32_t *n_eval_ptr, int n_eval_host, int max_n, float *out) {
+    const int n_eval = min(n_eval_ptr ? *n_eval_ptr : n_eval_host, max_n);
     const int C = P.C, N = P.N, ncells = P.ncells;
     const float *w = P.Wg + (size_t)layer * 9 * C * C;
     const size_t total = (size_t)n_eval * ncells * C;
@@ -1990,18 +1990,18 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
         }
     } else {
         const int grid = 2048;
-        hipLaunchKernelGGL(k_stem_generic, dim3(grid), dim3(256), 0, st, d, boards, n_eval_ptr, n_host, act);
+        hipLaunchKernelGGL(k_stem_generic, dim3(grid), dim3(256), 0, st, d, boards, n_eval_ptr, n_host, max_n, act);
         float *x = act, *y = act2, *z = act3;
         for (int b = 0; b < d.blocks; ++b) {
-            hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b, x, (const float *)nullptr, n_eval_ptr, n_host, y);
-            hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b + 1, y, x, n_eval_ptr, n_host, z);
+            hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b, x, (const float *)nullptr, n_eval_ptr, n_host, max_n, y);
+            hipLaunchKernelGGL(k_conv_generic, dim3(grid), dim3(256), 0, st, d, 2 * b + 1, y, x, n_eval_ptr, n_host, max_n, z);
             std::swap(x, z);
         }
         if (x != act)   // heads read act
             (void)hipMemcpyAsync(act, x, (size_t)max_n * d.ncells * d.C * sizeof(float), hipMemcpyDeviceToDevice, st);
     }
     if (hfeat != nullptr && net->opt_heads_mfma && d.ncells <= 128) {
-        // the fused tower left the six head planes: the FC layers run as fp32 MFMA GEMMs over tiles of 32 boards
+        // the fused tower left the six head planes: the FC layers run as fp32 MFMA GEMMs over tiles of HM_MB boards
         const size_t hl = std::max((size_t)HM_MB * d.hm_lda, (size_t)HM_MB * AZX_CELL_STRIDE + (size_t)HM_MB * 64) * sizeof(float);
         hipLaunchKernelGGL(k_heads_mfma, dim3((max_n + HM_MB - 1) / HM_MB), dim3(256), hl, st, d, hfeat, boards, flip, n_eval_ptr, n_host, logit, value, prior);
     } else {
@@ -2036,6 +2036,31 @@ bool azx_net_rows_splittable(const AzxNet *net) { return net && !(net->use_mfma 
 void azx_net_eval_rows(AzxNet *net, const DevEngine &e, int row0, int max_n, hipStream_t st) {
     run_net(net, e.ev_board, e.ev_flip, e.n_eval, 0, max_n, net->logit + (size_t)row0 * AZX_CELL_STRIDE, e.ev_value,
             e.ev_prior, st, (size_t)row0);
+}
+
+// ctr[0] = how many of the *n_eval requests lie at or behind row `first`; ctr[1..3]: the count seen, calls so far and
+// calls that found none (azx_debug_stagger; only tests read them).  One thread, plain loads and stores: the calls follow
+// each other on one stream.  Once per move, 0.004 ms in the kernel trace: nothing measurable next to a 310 ms move.
+__global__ void k_rows_behind(const int32_t *__restrict__ n_eval_ptr, int first, int32_t *__restrict__ ctr) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int n = *n_eval_ptr;
+    const int rest = n > first ? n - first : 0;
+    ctr[0] = rest;
+    ctr[1] = n;
+    ctr[2] = ctr[2] + 1;
+    ctr[3] = ctr[3] + (rest == 0 ? 1 : 0);
+}
+
+// a cut inside a block would let the first launch's last heads block read tower rows the second has yet to compute
+static_assert(AZX_NET_ROW_ALIGN % HM_MB == 0 && AZX_NET_ROW_ALIGN % HEADS_BPB == 0 && AZX_NET_ROW_ALIGN % F16X3_BPB == 0 &&
+              AZX_NET_ROW_ALIGN % 2 == 0, "AZX_NET_ROW_ALIGN: whole blocks of k_tower_f16x3_s16, k_tower_mfma (1 or 2 boards), k_heads_mfma, k_heads");
+void azx_net_eval_rows_behind(AzxNet *net, const DevEngine &e, int row0, int first, int max_n, int32_t *ctr, hipStream_t st) {
+    if (first <= 0 || first >= max_n) return;
+    hipLaunchKernelGGL(k_rows_behind, dim3(1), dim3(64), 0, st, (const int32_t *)e.n_eval, first, ctr);
+    const size_t f = (size_t)first;
+    run_net(net, e.ev_board + f * AZX_CELL_STRIDE, e.ev_flip + f, ctr, 0, max_n - first,
+            net->logit + ((size_t)row0 + f) * AZX_CELL_STRIDE, e.ev_value + f, e.ev_prior + f * AZX_CELL_STRIDE, st,
+            (size_t)row0 + f);
 }
 
 int azx_net_forward_host(AzxNet *net, int B, int K, const int32_t *boards, const int32_t *legal_moves,

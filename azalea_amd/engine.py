@@ -400,6 +400,14 @@ class Engine:
         """tests: bound the harvest queue of the following play calls (0 = no bound)."""
         check(self.L.azx_debug_set_queue_cap(self.h, int(rows)))
 
+    def debug_stagger(self):
+        """azx_debug_stagger: the pipelined play loop's staggered starts since creation, as a dict (rows_behind: rows the
+        last second sub-launch evaluated, rows_queued: rows queued for that evaluation, starts, empty: starts whose
+        second sub-launch found nothing to do)."""
+        out = np.zeros(4, np.int32)
+        check(self.L.azx_debug_stagger(self.h, _p(out, C.c_int32)))
+        return dict(zip(("rows_behind", "rows_queued", "starts", "empty"), out.tolist()))
+
     def play_device(self, min_positions, max_plies=0):
         """azx_play_device: whole games until >= min_positions rows sit in the harvest queue (in HBM)."""
         st = PlayStats()

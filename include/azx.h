@@ -392,6 +392,11 @@ int azx_kernel_info(azx_engine *e, char *buf, int cap);
 /* tests: bound the harvest queue of the following azx_play* calls to `rows` rows (0 = no bound) so that finished
  * games find it full and park (parallel_player.py has no counterpart: its pipes block instead). */
 int azx_debug_set_queue_cap(azx_engine *e, int64_t rows);
+/* tests: the staggered start of the pipelined play loop (AZX_PIPELINE_STAGGER) since engine creation.
+ * out4[0] = rows the last second sub-launch evaluated, [1] = rows that were queued for that evaluation, [2] = staggered
+ * moves so far, [3] = those whose second sub-launch found no row to evaluate.  All 0 before the first pipelined play.
+ * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_stagger). */
+int azx_debug_stagger(azx_engine *e, int32_t *out4);
 
 /* ---- evaluation matches between two engines, entirely on the device -------------------------
  * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_match_create).
