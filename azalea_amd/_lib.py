@@ -136,6 +136,14 @@ SYMBOLS = {
     "azx_tournament_play": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32,
                                       C.POINTER(C.c_int8), C.POINTER(C.c_int16), C.POINTER(C.c_int16),
                                       C.POINTER(MatchStats)]),
+    # replay rows from matches / tournaments (additions within revision 7)
+    "azx_match_set_harvest": (C.c_int, [_vp, C.c_int]),
+    "azx_match_set_first_mover": (C.c_int, [_vp, C.c_int]),
+    "azx_match_rows": (C.c_int, [_vp, _i64p]),
+    "azx_tournament_set_harvest": (C.c_int, [_vp, C.c_int]),
+    "azx_tournament_set_first_mover": (C.c_int, [_vp, C.c_int]),
+    "azx_tournament_rows": (C.c_int, [_vp, _i64p]),
+    "azx_rows_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _i32p, _i32p, _i32p, _f32p, _f32p, _i64p]),
 }
 
 class TrainConfig(C.Structure):

@@ -1203,6 +1203,7 @@ static int play_setup(azx_engine *e, int64_t q_rows, int ring) {
         (void)hipStreamSynchronize(e->stream);
         for (void *p : e->q_allocs) (void)hipFree(p);
         e->q_allocs.clear();
+        e->q_alloc = 0;                                  // (nothing is held should one of the allocations below fail)
         auto qa = [&](void **p, size_t bytes) -> int {
             hipError_t err = hipMalloc(p, bytes);
             if (err != hipSuccess) return fail(AZX_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
@@ -1445,6 +1446,39 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
     return check_net_range(e);
 }
 
+// rows [first, first + n) of the harvest queue to the host in azx_play's layout (any pointer may be null): widen /
+// densify on the device (k_rows_export), then one copy per output array
+static int rows_read(azx_engine *e, int64_t first, int64_t n_rows, int32_t *board, int32_t *color, int32_t *nlegal,
+                     float *moves_prob, float *reward, int64_t *game_uid) {
+    if (n_rows == 0) return AZX_OK;
+    DevEngine &d = e->d;
+    const size_t n = (size_t)n_rows, f = (size_t)first;
+    if (board || moves_prob) {
+        const size_t need = n * d.ncells;
+        if (need > e->export_cap) {
+            (void)hipStreamSynchronize(e->stream);
+            if (e->export_board) (void)hipFree(e->export_board);
+            if (e->export_prob) (void)hipFree(e->export_prob);
+            e->export_board = nullptr; e->export_prob = nullptr; e->export_cap = 0;
+            if (hipMalloc((void **)&e->export_board, need * sizeof(int32_t)) != hipSuccess ||
+                hipMalloc((void **)&e->export_prob, need * sizeof(float)) != hipSuccess)
+                return fail(AZX_ENOMEM, "hipMalloc of the export staging (%zu rows) failed", n);
+            e->export_cap = need;
+        }
+        azx_launch_rows_export(d.q_board + f * AZX_CELL_STRIDE, d.q_prob + f * AZX_CELL_STRIDE, (long long)n, d.ncells,
+                               e->export_board, e->export_prob, e->stream);
+        HIPCHECK(hipGetLastError());
+        if (board) HIPCHECK(hipMemcpyAsync(board, e->export_board, need * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        if (moves_prob) HIPCHECK(hipMemcpyAsync(moves_prob, e->export_prob, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    }
+    if (color) HIPCHECK(hipMemcpyAsync(color, d.q_color + f, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (nlegal) HIPCHECK(hipMemcpyAsync(nlegal, d.q_k + f, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (reward) HIPCHECK(hipMemcpyAsync(reward, d.q_reward + f, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (game_uid) HIPCHECK(hipMemcpyAsync(game_uid, d.q_uid + f, n * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
+}
+
 extern "C" int azx_play(azx_engine *e, int64_t min_positions, int64_t max_plies, int64_t cap,
                         int32_t *board, int32_t *color, int32_t *nlegal, float *moves_prob,
                         float *reward, int64_t *game_uid, azx_play_stats *stats) {
@@ -1461,32 +1495,7 @@ extern "C" int azx_play(azx_engine *e, int64_t min_positions, int64_t max_plies,
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
     e->q_rows_valid = (int64_t)rows;
-    if (rows == 0) return AZX_OK;
-    const size_t n = (size_t)rows;
-    // widen / densify on the device (k_rows_export), then one copy per output array
-    if (board || moves_prob) {
-        const size_t need = n * d.ncells;
-        if (need > e->export_cap) {
-            (void)hipStreamSynchronize(e->stream);
-            if (e->export_board) (void)hipFree(e->export_board);
-            if (e->export_prob) (void)hipFree(e->export_prob);
-            e->export_board = nullptr; e->export_prob = nullptr; e->export_cap = 0;
-            if (hipMalloc((void **)&e->export_board, need * sizeof(int32_t)) != hipSuccess ||
-                hipMalloc((void **)&e->export_prob, need * sizeof(float)) != hipSuccess)
-                return fail(AZX_ENOMEM, "hipMalloc of the export staging (%zu rows) failed", n);
-            e->export_cap = need;
-        }
-        azx_launch_rows_export(d.q_board, d.q_prob, (long long)n, d.ncells, e->export_board, e->export_prob, e->stream);
-        HIPCHECK(hipGetLastError());
-        if (board) HIPCHECK(hipMemcpyAsync(board, e->export_board, need * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        if (moves_prob) HIPCHECK(hipMemcpyAsync(moves_prob, e->export_prob, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    }
-    if (color) HIPCHECK(hipMemcpyAsync(color, d.q_color, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (nlegal) HIPCHECK(hipMemcpyAsync(nlegal, d.q_k, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (reward) HIPCHECK(hipMemcpyAsync(reward, d.q_reward, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    if (game_uid) HIPCHECK(hipMemcpyAsync(game_uid, d.q_uid, n * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    return AZX_OK;
+    return rows_read(e, 0, (int64_t)rows, board, color, nlegal, moves_prob, reward, game_uid);
 }
 
 extern "C" int azx_play_device(azx_engine *e, int64_t min_positions, int64_t max_plies, int64_t *rows_out,
@@ -1513,6 +1522,16 @@ extern "C" int azx_play_row_metrics(azx_engine *e, int64_t cap, float *metrics, 
     HIPCHECK(hipMemcpyAsync(metrics, e->d.q_meta, (size_t)n * AZX_ROW_METRICS * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(hipStreamSynchronize(e->stream));
     return AZX_OK;
+}
+
+extern "C" int azx_rows_read(azx_engine *e, int64_t first, int64_t n, int32_t *board, int32_t *color, int32_t *nlegal,
+                             float *moves_prob, float *reward, int64_t *game_uid) {
+    if (!e) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    if (first < 0 || n < 0 || first + n > e->q_rows_valid)
+        return fail(AZX_EINVAL, "rows [%lld, %lld) outside the %lld rows queued", (long long)first,
+                    (long long)(first + n), (long long)e->q_rows_valid);
+    return rows_read(e, first, n, board, color, nlegal, moves_prob, reward, game_uid);
 }
 
 extern "C" int azx_rows_pack(azx_engine *e, int64_t first, int64_t n, void *records_dev) {
@@ -1873,12 +1892,15 @@ extern "C" int azx_debug_counters(azx_engine *e, uint64_t *out16) {
 // other engine's cursor when both are external (match_ply_searches).
 struct azx_match {
     azx_engine *a = nullptr, *b = nullptr;
-    MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, -1};
     int64_t out_cap = 0, moves_cap = 0;          // games the outcome / length and the moves buffers hold
     int16_t *moves_buf = nullptr;
     unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, t0 = nullptr, t1 = nullptr;
     bool interleave = true;                      // AZX_MATCH_INTERLEAVE=0: a's whole search, then b's (diagnostic)
+    bool harvest = false;                        // azx_match_set_harvest: won games' replay rows go to a's harvest queue
+    int first_mode = -1;                         // azx_match_set_first_mover
+    int64_t rows_last = 0;                       // rows the last azx_match_play harvested
 };
 
 static const char *match_engine_problem(const azx_engine *e) {
@@ -1928,6 +1950,40 @@ extern "C" int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out) {
         return fail(AZX_ENOMEM, "allocating the match state failed: %s", hipGetErrorString(err));
     }
     *out = m;
+    return AZX_OK;
+}
+
+extern "C" int azx_match_set_harvest(azx_match *m, int on) {
+    if (!m) return fail(AZX_EINVAL, "null match");
+    m->harvest = on != 0;
+    return AZX_OK;
+}
+
+extern "C" int azx_match_set_first_mover(azx_match *m, int mode) {
+    if (mode < -1 || mode > 1) return fail(AZX_EINVAL, "first mover mode %d: -1 (agent u & 1), 0 or 1", mode);
+    if (!m) return fail(AZX_EINVAL, "null match");
+    m->first_mode = mode;
+    return AZX_OK;
+}
+
+extern "C" int azx_match_rows(azx_match *m, int64_t *rows_out) {
+    if (!m || !rows_out) return fail(AZX_EINVAL, "null argument");
+    *rows_out = m->rows_last;
+    return AZX_OK;
+}
+
+// the harvest queue of a harvesting match / tournament: no ring, room for every game at its longest (`cells` plies)
+static int harvest_setup(azx_engine *sink, int64_t n_games) {
+    const int64_t rows = n_games * sink->d.ncells;
+    const size_t row_bytes = AZX_CELL_STRIDE + AZX_CELL_STRIDE * sizeof(float) + 2 * sizeof(int32_t) + sizeof(float) +
+                             sizeof(int64_t) + AZX_ROW_METRICS * sizeof(float);
+    const int rc = play_setup(sink, rows, 0);
+    if (rc == AZX_ENOMEM)
+        return fail(AZX_ENOMEM, "the harvest queue of %lld games needs %lld rows = %zu bytes of device memory: %s",
+                    (long long)n_games, (long long)rows, (size_t)rows * row_bytes, std::string(g_err).c_str());
+    if (rc) return rc;
+    if (sink->dbg_qcap > 0)                              // tests (azx_debug_set_queue_cap): a queue too small
+        sink->d.q_cap = std::max<int64_t>(1, std::min<int64_t>(sink->d.q_cap, sink->dbg_qcap));
     return AZX_OK;
 }
 
@@ -2010,14 +2066,18 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     const hipStream_t sa = a->stream, sb = b->stream;
     // the move draw records a replay row per draw (choose_body): the row area must exist; a game draws at most
     // ceil(cells / 2) times per engine and n_rows restarts with every game
+    m->rows_last = 0;
     for (azx_engine *e : {a, b}) {
-        TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
+        if (m->harvest && e == a) TRY(harvest_setup(e, n_games));
+        else TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
         TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
     }
     TRY(match_reserve(m, n_games, moves != nullptr));
     MatchDev M = m->m;
     M.first_game = first_game;
     M.n_games = n_games;
+    M.harvest = m->harvest ? 1 : 0;
+    M.first_mode = m->first_mode;
     M.moves = moves ? m->moves_buf : nullptr;
     if (M.moves) HIPCHECK(hipMemsetAsync(M.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, sa));
     unsigned long long ctr0[MCTR_COUNT] = {0};
@@ -2057,8 +2117,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     }
     HIPCHECK(hipEventRecord(m->t1, sa));
 
-    unsigned long long ctr[MCTR_COUNT];
+    unsigned long long ctr[MCTR_COUNT], rows = 0;
     HIPCHECK(hipMemcpyAsync(ctr, M.ctr, sizeof ctr, hipMemcpyDeviceToHost, sa));
+    if (m->harvest) HIPCHECK(hipMemcpyAsync(&rows, a->d.q_count, sizeof rows, hipMemcpyDeviceToHost, sa));
     if (outcome) HIPCHECK(hipMemcpyAsync(outcome, M.outcome, (size_t)n_games, hipMemcpyDeviceToHost, sa));
     if (length) HIPCHECK(hipMemcpyAsync(length, M.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, sa));
     if (moves) HIPCHECK(hipMemcpyAsync(moves, M.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, sa));
@@ -2077,6 +2138,13 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
         stats->voided = (int64_t)ctr[MCTR_VOIDED];
         stats->plies = (int64_t)ctr[MCTR_PLIES];
         stats->seconds = ms * 1e-3;
+    }
+    if (ctr[MCTR_ROWS_LOST])
+        return fail(AZX_ESTATE, "match: %llu replay rows of finished games did not fit the harvest queue of %lld rows "
+                    "or did not add up to their games (internal error)", ctr[MCTR_ROWS_LOST], (long long)a->d.q_cap);
+    if (m->harvest) {                                    // the rows stay readable until a's next play call
+        m->rows_last = (int64_t)rows;
+        a->q_rows_valid = (int64_t)rows;
     }
     TRY(check_net_range(a));
     return check_net_range(b);
@@ -2101,6 +2169,9 @@ struct azx_tournament {
     unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
     hipEvent_t ev_fork = nullptr, t0 = nullptr, t1 = nullptr;
     std::vector<hipEvent_t> ev_join;             // [K - 1]: engine k's stream back into engine 0's
+    int sink = -1;                               // azx_tournament_set_harvest: the engine whose queue takes the rows
+    int first_mode = -1;                         // azx_tournament_set_first_mover
+    int64_t rows_last = 0;                       // rows the last azx_tournament_play harvested
 };
 
 extern "C" void azx_tournament_destroy(azx_tournament *t) {
@@ -2149,6 +2220,27 @@ extern "C" int azx_tournament_create(azx_engine *const *engines, int n_engines, 
         return fail(AZX_ENOMEM, "allocating the tournament state failed: %s", hipGetErrorString(err));
     }
     *out = t;
+    return AZX_OK;
+}
+
+extern "C" int azx_tournament_set_harvest(azx_tournament *t, int sink_engine) {
+    if (!t) return fail(AZX_EINVAL, "null tournament");
+    if (sink_engine < -1 || sink_engine >= (int)t->eng.size())
+        return fail(AZX_EINVAL, "sink engine %d: -1 (off) or an engine index below %d", sink_engine, (int)t->eng.size());
+    t->sink = sink_engine;
+    return AZX_OK;
+}
+
+extern "C" int azx_tournament_set_first_mover(azx_tournament *t, int mode) {
+    if (mode < -1 || mode > 1) return fail(AZX_EINVAL, "first mover mode %d: -1 (agent u & 1), 0 or 1", mode);
+    if (!t) return fail(AZX_EINVAL, "null tournament");
+    t->first_mode = mode;
+    return AZX_OK;
+}
+
+extern "C" int azx_tournament_rows(azx_tournament *t, int64_t *rows_out) {
+    if (!t || !rows_out) return fail(AZX_EINVAL, "null argument");
+    *rows_out = t->rows_last;
     return AZX_OK;
 }
 
@@ -2246,8 +2338,11 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     const int ncells = e0->d.ncells;
     const hipStream_t s0 = e0->stream;
     // the move draw records a replay row per draw (choose_body): the row area must exist (as in azx_match_play)
+    t->rows_last = 0;
+    azx_engine *sink = t->sink >= 0 ? t->eng[(size_t)t->sink] : nullptr;
     for (azx_engine *e : t->eng) {
-        TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
+        if (e == sink) TRY(harvest_setup(e, n_games));
+        else TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
         TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
     }
     TRY(tour_grow(&t->tab_dev, &t->tab_cap, n_tables, "tables"));
@@ -2270,6 +2365,8 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     D.first_game = first_game;
     D.rounds = rounds;
     D.moves = moves_dev;
+    D.sink = t->sink;
+    D.first_mode = t->first_mode;
     std::vector<DevEngine> devs;
     for (azx_engine *e : t->eng) devs.push_back(e->d);
     std::vector<unsigned long long> ctr0((size_t)(P + 1) * MCTR_COUNT, 0ull);
@@ -2315,7 +2412,9 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     HIPCHECK(hipEventRecord(t->t1, s0));
 
     std::vector<unsigned long long> ctr((size_t)P * MCTR_COUNT);
+    unsigned long long rows = 0, lost = 0;
     HIPCHECK(hipMemcpyAsync(ctr.data(), D.ctr, sizeof(unsigned long long) * ctr.size(), hipMemcpyDeviceToHost, s0));
+    if (sink) HIPCHECK(hipMemcpyAsync(&rows, sink->d.q_count, sizeof rows, hipMemcpyDeviceToHost, s0));
     if (outcome) HIPCHECK(hipMemcpyAsync(outcome, D.outcome, (size_t)n_games, hipMemcpyDeviceToHost, s0));
     if (length) HIPCHECK(hipMemcpyAsync(length, D.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, s0));
     if (moves) HIPCHECK(hipMemcpyAsync(moves, D.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, s0));
@@ -2336,6 +2435,14 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
             stats[s].plies = (int64_t)c[MCTR_PLIES];
             stats[s].seconds = ms * 1e-3;
         }
+    }
+    for (int s = 0; s < P; ++s) lost += ctr[(size_t)s * MCTR_COUNT + MCTR_ROWS_LOST];
+    if (lost)
+        return fail(AZX_ESTATE, "tournament: %llu replay rows of finished games did not fit the harvest queue of %lld "
+                    "rows or did not add up to their games (internal error)", lost, (long long)(sink ? sink->d.q_cap : 0));
+    if (sink) {                                          // the rows stay readable until the sink's next play call
+        t->rows_last = (int64_t)rows;
+        sink->q_rows_valid = (int64_t)rows;
     }
     for (azx_engine *e : t->eng) TRY(check_net_range(e));
     return AZX_OK;

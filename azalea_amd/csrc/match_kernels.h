@@ -9,7 +9,10 @@
 enum {   // MatchDev::ctr slots
     MCTR_NEXT = 0,      // game indices handed out so far, relative to first_game (the refill claims the next one)
     MCTR_DECIDED,       // games settled (won or voided): the one word the host reads back per ply
-    MCTR_WINS0, MCTR_WINS1, MCTR_FIRST_WINS, MCTR_VOIDED, MCTR_PLIES, MCTR_COUNT = 8
+    MCTR_WINS0, MCTR_WINS1, MCTR_FIRST_WINS, MCTR_VOIDED, MCTR_PLIES,
+    MCTR_ROWS_LOST,     // harvest: replay rows of won games that could NOT be queued (queue too small, or the two
+                        // engines' row counts do not add up to the game's length): the host turns > 0 into AZX_ESTATE
+    MCTR_COUNT = 8
 };
 
 struct MatchDev {
@@ -19,6 +22,9 @@ struct MatchDev {
     int8_t *outcome;               // [n_games] +1 agent 0 won, -1 agent 1 won, 0 voided
     int16_t *length;               // [n_games] plies played
     int16_t *moves;                // [n_games][ncells] tile + 1 in play order, 0-padded; null = not recorded
+    int32_t harvest;               // 1: every won game's replay rows are appended to the harvest queue (q_*, q_count) of
+                                   // engine A when the game settles (match_harvest); 0 = off
+    int32_t first_mode;            // -1: agent u & 1 moves first in game u; 0 / 1: that agent moves first in every game
 };
 
 // slot g takes game first_game + g (idle beyond n_games); both engines' slots get uid = game index
@@ -48,6 +54,9 @@ struct TourDev {
     int8_t *outcome;               // [n_pairs * rounds] by u - first_game, as MatchDev's
     int16_t *length;               // [n_pairs * rounds]
     int16_t *moves;                // [n_pairs * rounds][ncells]; null = not recorded
+    int32_t sink;                  // harvest target: -1 = off, else the index in eng[] of the engine whose harvest queue
+                                   // takes the won games' replay rows of ALL pairs (as MatchDev::harvest)
+    int32_t first_mode;            // as MatchDev::first_mode
 };
 
 // every table takes its pair's round `local` (idle beyond `rounds`) and both its slots that game's uid; every slot

@@ -13,8 +13,11 @@
 // same bookkeeping per table, a table's two slots being any slot of any two of K engines.
 #include "match_kernels.h"
 
-// agent (0 = engine A, 1 = engine B) to move in game u at `ply`: agent u & 1 moves first
-__device__ __forceinline__ int match_mover(int64_t u, int ply) { return (int)(u & 1) ^ (ply & 1); }
+// agent (0 = engine A, 1 = engine B) that moves first in game u: agent u & 1, or the one first_mode 0 / 1 fixes for
+// every game (the reference's play_game always starts with agents[0], play_game.py:47)
+__device__ __forceinline__ int match_first(int64_t u, int mode) { return mode < 0 ? (int)(u & 1) : mode; }
+// agent to move in game u at `ply`
+__device__ __forceinline__ int match_mover(int64_t u, int ply, int mode) { return match_first(u, mode) ^ (ply & 1); }
 
 __global__ void k_match_init(DevEngine A, DevEngine B, MatchDev M) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -33,7 +36,7 @@ __global__ void k_match_turn(DevEngine A, DevEngine B, MatchDev M) {
     const int64_t u = M.slot_game[g];
     int a = 0, b = 0;
     if (u >= 0) {
-        const int mover = match_mover(u, A.ghdr[g].ply);
+        const int mover = match_mover(u, A.ghdr[g].ply, M.first_mode);
         a = mover == 0;
         b = mover == 1;
     }
@@ -63,6 +66,102 @@ __device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t
     tree_reset<SLOTS>(E, g, E.thdr + g, E.ncells, lane);
 }
 
+// ---- settle-time harvest: a won game's replay rows into a harvest queue (play_game.py:59-67 for two agents) ----
+// Each engine's move draw (choose_body) has written the rows of the plies IT moved at into its own slot's row area, at
+// row index GameHdr.n_rows: the first mover holds plies 0, 2, 4, ... at rows 0, 1, 2, ..., the other agent plies 1, 3,
+// 5, ....  Row p of the game is therefore row p >> 1 of the engine that moved at ply p.  `src` rows of PIECES 16-byte
+// pieces each go to every second row of `dst` (which points at the game's first or second queue row), eight pieces
+// in flight per lane.
+template <int PIECES>
+__device__ __forceinline__ void match_copy_rows(uint4 *dst, const uint4 *src, int n_rows, int lane) {
+    // eight named registers, not an array: an indexed array of sixteen stayed in scratch memory in these kernels
+    const int n16 = n_rows * PIECES;
+#define MATCH_LD(k) const uint4 v##k = src[min(i0 + k * 64 + lane, n16 - 1)];     /* (the tail repeats the last piece) */
+#define MATCH_ST(k)                                                       \
+    {                                                                     \
+        const int i = i0 + k * 64 + lane;                                 \
+        if (i < n16) {                                                    \
+            const int r = i / PIECES;                                     \
+            dst[(size_t)(2 * r) * PIECES + (i - r * PIECES)] = v##k;      \
+        }                                                                 \
+    }
+    for (int i0 = 0; i0 < n16; i0 += 64 * 8) {
+        MATCH_LD(0) MATCH_LD(1) MATCH_LD(2) MATCH_LD(3) MATCH_LD(4) MATCH_LD(5) MATCH_LD(6) MATCH_LD(7)
+        MATCH_ST(0) MATCH_ST(1) MATCH_ST(2) MATCH_ST(3) MATCH_ST(4) MATCH_ST(5) MATCH_ST(6) MATCH_ST(7)
+    }
+#undef MATCH_LD
+#undef MATCH_ST
+}
+
+// the harvest queue of an engine, by value (a reference picked among kernel arguments would put them in scratch)
+struct MatchSink {
+    uint8_t *q_board;
+    float *q_prob;
+    int32_t *q_color, *q_k;
+    float *q_reward;
+    int64_t *q_uid;
+    float *q_meta;
+    unsigned long long *q_count;
+    int64_t q_cap;
+};
+__device__ __forceinline__ MatchSink match_sink(const DevEngine &E) {
+    return MatchSink{E.q_board, E.q_prob, E.q_color, E.q_k, E.q_reward, E.q_uid, E.q_meta, E.q_count, E.q_cap};
+}
+
+// the `n` rows of slot `slot` of engine E are the game's plies off, off + 2, ...: queue rows pos + off, pos + off + 2, ...
+__device__ __forceinline__ void match_harvest_rows(const DevEngine &E, int slot, int n, int off, const MatchSink &Q,
+                                                   unsigned long long pos, int64_t u, int winner, int lane) {
+    const size_t sr = (size_t)slot * E.ncells;                     // the slot's first row
+    const size_t q0 = (size_t)pos + off;
+    match_copy_rows<AZX_CELL_STRIDE / 16>(reinterpret_cast<uint4 *>(Q.q_board + q0 * AZX_CELL_STRIDE),
+                                          reinterpret_cast<const uint4 *>(E.row_board + sr * AZX_CELL_STRIDE), n, lane);
+    match_copy_rows<AZX_CELL_STRIDE / 4>(reinterpret_cast<uint4 *>(Q.q_prob + q0 * AZX_CELL_STRIDE),
+                                         reinterpret_cast<const uint4 *>(E.row_prob + sr * AZX_CELL_STRIDE), n, lane);
+    for (int r = lane; r < n; r += 64) {
+        const int p = 2 * r + off;
+        const size_t q = (size_t)pos + p;
+        Q.q_color[q] = p & 1;
+        Q.q_k[q] = E.row_k[sr + r];
+        float rew = winner == 1 ? 1.0f : -1.0f;                    // play_game.py:64-65
+        if (p & 1) rew = -rew;
+        Q.q_reward[q] = rew;
+        Q.q_uid[q] = u;
+        const float4 *ms = reinterpret_cast<const float4 *>(E.row_meta) + (sr + r) * 2;
+        float4 mt = ms[0];
+        mt.w = p == 0 ? 1.0f : 0.0f;                               // marks the first row of a game
+        reinterpret_cast<float4 *>(Q.q_meta)[q * 2] = mt;
+        reinterpret_cast<float4 *>(Q.q_meta)[q * 2 + 1] = ms[1];
+    }
+}
+
+// One wave.  Slots sa of A and sb of B hold the finished game u (`len` plies, colour `winner` won, agent `first` moved
+// first); Q is the engine whose queue takes the rows.  The game's rows are reserved with one atomicAdd and stay
+// contiguous, plies ascending.  The queue is no ring here and the host sizes it for the worst case; should the rows
+// not fit after all, or the two engines' row counts not add up to the game, the reservation is given back, nothing
+// is written and `lost` counts the rows (the host reports that as an internal error).
+__device__ __forceinline__ void match_harvest(const DevEngine &A, int sa, const DevEngine &B, int sb, const MatchSink &Q,
+                                              unsigned long long *lost, int64_t u, int first, int winner, int len,
+                                              int lane) {
+    const int nA = A.ghdr[sa].n_rows, nB = B.ghdr[sb].n_rows;
+    bool ok = nA + nB == len && (first ? nB : nA) == (len + 1) >> 1;
+    unsigned long long pos = 0;
+    if (ok) {
+        if (lane == 0) pos = atomicAdd(Q.q_count, (unsigned long long)len);
+        pos = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(pos >> 32)) << 32) |
+              (unsigned int)__builtin_amdgcn_readfirstlane((int)pos);
+        if (pos + (unsigned long long)len > (unsigned long long)Q.q_cap) {
+            if (lane == 0) atomicAdd(Q.q_count, (unsigned long long)(-(long long)len));
+            ok = false;
+        }
+    }
+    if (!ok) {
+        if (lane == 0) atomicAdd(lost, (unsigned long long)len);
+        return;
+    }
+    match_harvest_rows(A, sa, nA, first, Q, pos, u, winner, lane);       // agent 0 moved at the even plies iff it moved first
+    match_harvest_rows(B, sb, nB, 1 - first, Q, pos, u, winner, lane);
+}
+
 // One wave per slot, after both engines' searches and move draws of this ply.
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, MatchDev M) {
@@ -72,8 +171,8 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
     if (u < 0) return;                                         // idle slot
     GameHdr *ga = A.ghdr + g, *gb = B.ghdr + g;
     const int ply = ga->ply;                                   // (the two slots hold the same game)
-    const int first = (int)(u & 1);
-    const int mover = match_mover(u, ply);
+    const int first = match_first(u, M.first_mode);
+    const int mover = first ^ (ply & 1);
     const int mid = mover ? gb->move_id : ga->move_id;
     const int status = mover ? B.thdr[g].status : A.thdr[g].status;
     // SearchTreeFull in the searching agent's tree voids the game (parallel_player.py:73-76 skips such a game);
@@ -112,6 +211,8 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
         }
     }
     if (!voided && winner == 0) return;                        // the game goes on
+
+    if (M.harvest && !voided) match_harvest(A, g, B, g, match_sink(A), M.ctr + MCTR_ROWS_LOST, u, first, winner, len, lane);
 
     // ---- settle: outcome by agent, tallies, the next game for this slot ----
     long long next_u = -1;
@@ -182,7 +283,7 @@ __global__ void k_tour_turn(TourDev T) {
     const int64_t u = T.tab_game[t];
     int a = 0, b = 0;
     if (u >= 0) {
-        const int mover = match_mover(u, ga->ply);
+        const int mover = match_mover(u, ga->ply, T.first_mode);
         a = mover == 0;
         b = mover == 1;
     }
@@ -203,8 +304,8 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
     GameHdr *ga = A.ghdr + sa, *gb = B.ghdr + sb;
     const int ply = ga->ply;                                   // (the two slots hold the same game)
     const int ncells = A.ncells;
-    const int first = (int)(u & 1);
-    const int mover = match_mover(u, ply);
+    const int first = match_first(u, T.first_mode);
+    const int mover = first ^ (ply & 1);
     const int mid = mover ? gb->move_id : ga->move_id;
     const int status = mover ? B.thdr[sb].status : A.thdr[sa].status;
     bool voided = status != 0 || mid < 0;                      // as k_match_step
@@ -240,6 +341,10 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
         }
     }
     if (!voided && winner == 0) return;                        // the game goes on
+
+    if (T.sink >= 0 && !voided)
+        match_harvest(A, sa, B, sb, match_sink(T.eng[T.sink]), T.ctr + (size_t)tb.pair * MCTR_COUNT + MCTR_ROWS_LOST, u, first, winner,
+                      len, lane);
 
     // ---- settle into the pair's tallies; the pair's next round for this table ----
     long long next_u = -1;

@@ -416,6 +416,20 @@ class Engine:
         self._last_rows = int(rows.value)
         return rows.value, st.as_dict()
 
+    def rows_read(self, first, n):
+        """azx_rows_read: rows [first, first + n) of the harvest queue as the dict play() returns -- whatever filled
+        the queue last: play() / play_device(), or a collecting Match / Tournament that has this engine as its sink."""
+        first, n = int(first), int(n)
+        board = np.zeros((n, self.n, self.n), np.int32)
+        color = np.zeros(n, np.int32)
+        nlegal = np.zeros(n, np.int32)
+        prob = np.zeros((n, self.cells), np.float32)
+        reward = np.zeros(n, np.float32)
+        uid = np.zeros(n, np.int64)
+        check(self.L.azx_rows_read(self.h, first, n, _p(board, C.c_int32), _p(color, C.c_int32), _p(nlegal, C.c_int32),
+                                   _p(prob, C.c_float), _p(reward, C.c_float), _p(uid, C.c_int64)))
+        return dict(board=board, color=color, nlegal=nlegal, moves_prob=prob, reward=reward, game_uid=uid)
+
     def rows_pack(self, first, n, records_ptr):
         """queue rows [first, first+n) -> fixed-size records in the device buffer at records_ptr."""
         check(self.L.azx_rows_pack(self.h, int(first), int(n), C.c_void_p(int(records_ptr))))
@@ -518,6 +532,15 @@ class Engine:
         return st.as_dict()
 
 
+def _collected(out, sink, n_rows, collect):
+    """What a collecting Match / Tournament play adds to its result: the rows now in `sink`'s harvest queue."""
+    out["n_rows"] = int(n_rows)
+    sink._last_rows = int(n_rows)
+    if collect is True:
+        out["rows"] = sink.rows_read(0, n_rows)
+        out["row_metrics"] = sink.play_row_metrics(n_rows)
+
+
 class Match:
     """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
     agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
@@ -532,6 +555,7 @@ class Match:
         self.cells = engine_a.cells
         self.h = C.c_void_p()
         check(self.L.azx_match_create(engine_a.h, engine_b.h, C.byref(self.h)))
+        self._mode = (0, -1)          # (harvest, first mover) as set in the library
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -544,10 +568,27 @@ class Match:
         except Exception:
             pass
 
-    def play(self, n_games, first_game=0, moves=False):
+    def play(self, n_games, first_game=0, moves=False, collect=False, first_mover=None):
         """Games first_game .. first_game + n_games - 1, each to its end.  Returns outcome int8[n] (+1 agent 0 won,
         -1 agent 1 won, 0 voided by SearchTreeFull), length int16[n] (plies), with `moves` the game records
-        int16[n, cells] (tile + 1 in play order, 0-padded), and stats (azx_match_stats as a dict)."""
+        int16[n, cells] (tile + 1 in play order, 0-padded), and stats (azx_match_stats as a dict).
+        `collect`: harvest the replay rows of every won game -- row p from the agent that moved at ply p, as
+        play_game(agents, collect_data=True) records them -- into engine a's harvest queue.  True: the result gains
+        "rows" (the dict Engine.play returns; games in the order they settled, a game's rows contiguous with plies
+        ascending, game_uid = the game index) and "row_metrics" ([rows, ROW_METRICS], Engine.play_row_metrics);
+        "device": the rows stay in engine a's queue for rows_pack / replay_put_records and only their count is
+        returned, as "n_rows" (either way).  `first_mover`: None -- agent u & 1 moves first in game u; 0 / 1 -- that
+        agent moves first in every game (play_game always starts with agents[0])."""
+        if collect not in (False, True, "device"):
+            raise ValueError("collect must be False, True or 'device'")
+        # (set only when they change: a plain play touches none of the later entry points of the library)
+        want = (1 if collect else 0, -1 if first_mover is None else int(first_mover))
+        if want[0] != self._mode[0]:
+            check(self.L.azx_match_set_harvest(self.h, want[0]))
+            self._mode = (want[0], self._mode[1])
+        if want[1] != self._mode[1]:
+            check(self.L.azx_match_set_first_mover(self.h, want[1]))
+        self._mode = want
         n = int(n_games)
         outcome = np.zeros(n, np.int8)
         length = np.zeros(n, np.int16)
@@ -568,6 +609,10 @@ class Match:
         out = dict(outcome=outcome, length=length, stats=st.as_dict())
         if moves:
             out["moves"] = mv
+        if collect:
+            rows = C.c_int64(0)
+            check(self.L.azx_match_rows(self.h, C.byref(rows)))
+            _collected(out, self.a, rows.value, collect)
         return out
 
 
@@ -586,6 +631,7 @@ class Tournament:
         arr = (C.c_void_p * max(len(self.engines), 1))(*[e.h for e in self.engines])
         check(self.L.azx_tournament_create(arr, len(self.engines), C.byref(self.h)))
         self.cells = self.engines[0].cells
+        self._mode = (-1, -1)         # (sink, first mover) as set in the library
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -598,11 +644,24 @@ class Tournament:
         except Exception:
             pass
 
-    def play(self, pairs, rounds, first_game=0, tables_per_pair=None, moves=False):
+    def play(self, pairs, rounds, first_game=0, tables_per_pair=None, moves=False, collect=False, sink=0,
+             first_mover=None):
         """`rounds` games of every pair, each to its end.  Returns {pair: dict(outcome int8[rounds], length
         int16[rounds], stats[, moves int16[rounds, cells]])} in the order of `pairs`, each as Match.play returns it
         (stats['seconds'] is the whole call's device time).  tables_per_pair defaults to the most every engine has
-        room for, at most `rounds`."""
+        room for, at most `rounds`.
+        `collect`, `first_mover`: as Match.play; the rows of ALL pairs go to the harvest queue of engines[sink], and
+        the result gains the keys "rows" / "row_metrics" (collect=True) and "n_rows" beside the pairs.  Pair s owns
+        the rows with game_uid in [first_game + s * rounds, first_game + (s + 1) * rounds)."""
+        if collect not in (False, True, "device"):
+            raise ValueError("collect must be False, True or 'device'")
+        want = (int(sink) if collect else -1, -1 if first_mover is None else int(first_mover))
+        if want[0] != self._mode[0]:
+            check(self.L.azx_tournament_set_harvest(self.h, want[0]))
+            self._mode = (want[0], self._mode[1])
+        if want[1] != self._mode[1]:
+            check(self.L.azx_tournament_set_first_mover(self.h, want[1]))
+        self._mode = want
         pairs = [(int(i), int(j)) for i, j in pairs]
         P, rounds = len(pairs), int(rounds)
         if tables_per_pair is None:
@@ -637,6 +696,10 @@ class Tournament:
             out[pair] = dict(outcome=outcome[sl], length=length[sl], stats=st[s].as_dict())
             if moves:
                 out[pair]["moves"] = mv[sl]
+        if collect:
+            rows = C.c_int64(0)
+            check(self.L.azx_tournament_rows(self.h, C.byref(rows)))
+            _collected(out, self.engines[int(sink)], rows.value, collect)
         return out
 
 

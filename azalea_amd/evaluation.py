@@ -217,7 +217,8 @@ def _throughput_policy(agent, external_batch=False):
 
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
-                        games=None, external_batch: bool = False, pooled: bool = False) -> Dict[Pair, OutcomeCounts]:
+                        games=None, external_batch: bool = False, pooled: bool = False,
+                        collect=None) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -234,7 +235,11 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     `pooled`: play all pairs in ONE ply loop (engine.Tournament, azx_tournament_play) instead of one match per pair
     after the other: the same games, tallies and `games` records, bit for bit.  `n_slots` stays "slots per engine"
     (default min((K - 1) * num_rounds, AZX_GAMES or 4096), rounded up to even): every engine's pool is shared out
-    among its K - 1 opponents, max(1, n_slots // (K - 1)) tables per pair."""
+    among its K - 1 opponents, max(1, n_slots // (K - 1)) tables per pair.
+    `collect`: optional dict that receives, per pair, the replay rows of that pair's games -- evaluation games that
+    double as training data: dict(rows=..., row_metrics=...) as engine.Match.play(collect=True) returns them (row p of
+    a game from the agent that moved at ply p; game_uid = the game's index, pair s owning [s * num_rounds,
+    (s + 1) * num_rounds); games in the order they settled).  The games and tallies are the same with or without."""
     import torch
     from . import engine as _eng
     from .policy import SearchTreeFull, external_evaluator
@@ -300,14 +305,16 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
         if pooled:
             tour = _eng.Tournament(engines)
             try:
-                results = tour.play(pairs, num_rounds, tables_per_pair=tables_per_pair, moves=games is not None)
+                results = tour.play(pairs, num_rounds, tables_per_pair=tables_per_pair, moves=games is not None,
+                                    collect=collect is not None)
             finally:
                 tour.close()
         for s, (i, j) in enumerate(pairs):
             if not pooled:
                 match = _eng.Match(engines[i], engines[j])
                 try:
-                    results[(i, j)] = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None)
+                    results[(i, j)] = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None,
+                                                 collect=collect is not None)
                 finally:
                     match.close()
             res = results[(i, j)]
@@ -317,6 +324,14 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
             outcomes[(i, j)] = [int(st["wins"][0]), 0, int(st["wins"][1])]
             if games is not None:
                 games[(i, j)] = {k: res[k] for k in ("outcome", "length", "moves")}
+            if collect is not None:
+                if pooled:                               # one queue for all pairs: pair s owns a range of uids
+                    uid = results["rows"]["game_uid"]
+                    mine = (uid >= s * num_rounds) & (uid < (s + 1) * num_rounds)
+                    collect[(i, j)] = dict(rows={k: v[mine] for k, v in results["rows"].items()},
+                                           row_metrics=results["row_metrics"][mine])
+                else:
+                    collect[(i, j)] = dict(rows=res["rows"], row_metrics=res["row_metrics"])
             logging.info("pair %s: outcomes %s (%.1f games/s on the device)", (i, j), outcomes[(i, j)],
                          (len(pairs) if pooled else 1) * num_rounds / max(st["seconds"], 1e-9))
         return outcomes

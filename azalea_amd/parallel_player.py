@@ -9,7 +9,11 @@ rank plays its share and the rows are all-gathered (azalea_amd/distributed.py).
 
 The `pool` argument is accepted for signature compatibility (policy_trainer.py:75) and unused:
 there are no worker processes.  Random movers and two-agent setups go through the host play_game
-loop (one game at a time), like the reference's in-process pool (num_workers=0).  So do duck-typed
+loop (one game at a time), like the reference's in-process pool (num_workers=0) -- unless a two-agent
+Player is created with `device_match=True`: then each agent gets an engine of `n_games` slots, the two
+play each other entirely on the device (engine.Match, agent 0 moving first in every game as in
+play_game) and every game's replay rows, each from the agent that moved, are harvested on the device
+and handed out by `read` like self-play's.  So do duck-typed
 networks (config["network"] naming another class, policy.py:11-18) by default; with
 `external_batch=True` such a net on a CUDA (ROCm) device plays `n_games` games in one engine instead,
 the engine handing it the whole pool's leaf batch on the device at every evaluation point
@@ -68,23 +72,35 @@ def rows_to_frame(rows) -> ReplayDataFrame:
 class Player:
     MAX_BARREN_PRODUCTIONS = 1000     # consecutive productions without a finished game before read() gives up
 
+    MATCH_CHUNK = 2                   # device_match: games per Match.play call, in units of n_games
+
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
-                 external_batch: bool = False):
+                 external_batch: bool = False, device_match: bool = False):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
         the trainer's weights first; the followers are driven by policy_trainer.serve_selfplay).
         `external_batch`: a single agent whose Policy holds a network other than HexNetwork, on a CUDA device,
         plays `n_games` games in one engine that hands the net every leaf batch of the pool on the device
-        (instead of the host loop); a ValueError when that does not hold."""
+        (instead of the host loop); a ValueError when that does not hold.
+        `device_match`: exactly two agents, each with a Policy whose network is on a CUDA (ROCm) device, play each
+        other in two engines of `n_games` slots on the device (agents[0] moves first in every game), and the games'
+        replay rows are harvested there.  HexNetwork agents use the device tower; other networks need
+        external_batch=True as well.  A ValueError when any of that does not hold, or under torch.distributed with
+        gather=True: there is no silent fall-back to the host loop."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.agents = agents
         self.running = True
         self.gather = gather
         self.external_batch = bool(external_batch)
-        if self.external_batch:
+        self.device_match = bool(device_match)
+        if self.device_match:
+            self._match_policies()
+        elif self.external_batch:
             self._external_policy()
+        self._match = None             # device_match: (engine a, engine b, engine.Match)
+        self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
         self.learner = None            # actor_learner.Learner: read() pulls the actors' backlogs instead of playing
         self.weight_syncs = 0          # broadcasts of the trainer's weights this player took part in
@@ -185,6 +201,7 @@ class Player:
         if self._engine is not None:
             self._engine.close()
             self._engine = None
+        self._close_match()
 
     # ---- device-resident replay (azalea_amd/device_replay.py) ---------------------------------
     def device_engine(self):
@@ -225,8 +242,31 @@ class Player:
                              "torch.distributed")
         return pol
 
+    def _match_policies(self):
+        """The two agents' Policies of a device_match Player; a ValueError naming what does not hold otherwise."""
+        from .evaluation import _throughput_policy
+        if len(self.agents) != 2:
+            raise ValueError("device_match needs exactly two agents, got %d" % len(self.agents))
+        pols = []
+        for i, agent in enumerate(self.agents):
+            try:
+                pol = _throughput_policy(agent, self.external_batch)
+            except TypeError as exc:
+                raise ValueError("device_match: agent %d: %s" % (i, str(exc).replace("evaluate_throughput", "it"))) from exc
+            pols.append(pol)
+        for i, pol in enumerate(pols):
+            dev = _net_device(pol.net)
+            if dev.type != "cuda":
+                raise ValueError("device_match needs every network on a CUDA (ROCm) device, agent %d's is on %s" % (i, dev))
+        if self.gather and azdist.is_distributed():
+            raise ValueError("device_match does not share reads across ranks: pass gather=False under "
+                             "torch.distributed")
+        return pols
+
     def _engine_policy(self):
         """The Policy whose searches run in this Player's engine (None: the host loop plays)."""
+        if self.device_match:
+            return self._match_policies()[0]      # (its rng seeds both engines' streams)
         return self._external_policy() if self.external_batch else self._device_policy()
 
     def _agree_seed_base(self) -> None:
@@ -249,6 +289,9 @@ class Player:
             self._seed_base = (local ^ (azdist.rank() * 0x9E3779B1)) & 0x7FFFFFFF
 
     def _produce(self, want: int) -> None:
+        if self.device_match:
+            self._produce_match(self._match_policies())
+            return
         if self.external_batch:
             self._produce_external(self._external_policy(), want)
             return
@@ -333,14 +376,80 @@ class Player:
         rows, st = eng.play(max(1, int(want)))
         self._harvest(eng, rows, st)
 
-    def _harvest(self, eng, rows, st) -> None:
+    def _close_match(self) -> None:
+        if self._match is not None:
+            a, b, match = self._match
+            if match is not None:
+                match.close()
+            a.close()
+            b.close()
+            self._match = None
+
+    def _match_engine(self, pol: Policy, which: int):
+        """Agent `which`'s engine, configured as evaluation.evaluate_throughput configures a pair's engines."""
+        n = self.agents[0].game.board_size
+        temperature = noise_scale = 0.0            # Policy.choose_action's schedule (policy.py:132-149)
+        if pol.settings["move_sampling"]:
+            temperature = pol.exploration_temperature
+            if pol.settings["move_exploration"]:
+                noise_scale = pol.exploration_noise_scale
+        external = not pol._uses_device_net()
+        dev = _net_device(pol.net)
+        # game_rng keys on seed + uid: the two agents' streams are disjoint ranges of 2^32 games
+        return _eng.Engine(board_size=n, n_games=self.n_games, simulations=pol.simulations,
+                           search_batch_size=pol.search_batch_size, exploration_coef=pol.exploration_coef,
+                           exploration_depth=pol.exploration_depth, noise_alpha=pol.exploration_noise_alpha,
+                           noise_scale=noise_scale, temperature=temperature,
+                           evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
+                           num_blocks=getattr(pol, "num_blocks", 0) if external else pol.num_blocks,
+                           base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
+                           device=dev.index or 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
+                           seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
+
+    def _produce_match(self, pols) -> None:
+        """One chunk of MATCH_CHUNK * n_games games between the two agents' engines, harvested on the device."""
+        if self._seed_base is None:
+            raise RuntimeError("Player: the seed base must be agreed before the engines are created")
+        if self._match is None:
+            a = self._match_engine(pols[0], 0)
+            try:
+                b = self._match_engine(pols[1], 1)
+            except Exception:
+                a.close()
+                raise
+            self._match = (a, b, None)
+        a, b, match = self._match
+        for eng, pol in ((a, pols[0]), (b, pols[1])):         # the live weights, before every chunk
+            net = pol.net
+            if hasattr(net, "eval"):
+                net.eval()
+            if pol._uses_device_net():
+                self._push_weights(eng, pol)
+            else:
+                eng.set_external_evaluator(external_evaluator(net))
+                dev = _net_device(net)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))
+                torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+        if match is None:                                     # (a match wants its engines ready: weights / evaluator)
+            match = _eng.Match(a, b)
+            self._match = (a, b, match)
+        chunk = self.MATCH_CHUNK * self.n_games
+        res = match.play(chunk, first_game=self._match_next, collect=True, first_mover=0)
+        self._match_next += chunk
+        st = res["stats"]
+        self._harvest(a, res["rows"], dict(game_errors=st["voided"], seconds=st["seconds"],
+                                           games=st["games"] - st["voided"]), meta=res["row_metrics"])
+
+    def _harvest(self, eng, rows, st, meta=None) -> None:
         """Whole games of one engine play call -> the read queue, with play_game's per-game metrics."""
         uid = rows["game_uid"]
         self._skipped += int(st["game_errors"])
         if len(uid) == 0:
             return
         # play_game's per-game metrics are means over the game's own plies (play_game.py:73-76)
-        meta = eng.play_row_metrics()
+        if meta is None:
+            meta = eng.play_row_metrics()
         starts = np.flatnonzero(np.r_[True, uid[1:] != uid[:-1]])
         ends = np.r_[starts[1:], len(uid)]
         names = [k for k, _ in eng.ROW_METRIC_COLUMNS]

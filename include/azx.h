@@ -309,6 +309,13 @@ int azx_play_device(azx_engine *e, int64_t min_positions, int64_t max_plies, int
                     azx_play_stats *stats);
 /* queue rows [first, first+n) -> records in the DEVICE buffer records_dev (n * AZX_RECORD_BYTES). Blocking. */
 int azx_rows_pack(azx_engine *e, int64_t first, int64_t n, void *records_dev);
+/* queue rows [first, first+n) -> host arrays in azx_play's row layout (board int32[n][cells], color[n], nlegal[n],
+ * moves_prob f32[n][cells], reward[n], game_uid[n]); any pointer may be NULL.  Valid for whatever filled the queue
+ * last: azx_play / azx_play_device, or a harvesting match / tournament (azx_match_set_harvest,
+ * azx_tournament_set_harvest), until that engine's next play, match or tournament call.  AZX_EINVAL for rows outside
+ * the rows queued.  Blocking.  An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_rows_read). */
+int azx_rows_read(azx_engine *e, int64_t first, int64_t n, int32_t *board, int32_t *color, int32_t *nlegal,
+                  float *moves_prob, float *reward, int64_t *game_uid);
 /* ReplayBuffer.put of n records held in a DEVICE buffer: FIFO with the wrap-around / overflow behaviour
  * of azx_replay_put.  Blocking. */
 int azx_replay_put_records(azx_engine *e, int64_t n, const void *records_dev);
@@ -431,7 +438,8 @@ int azx_debug_stagger(azx_engine *e, int32_t *out4);
  * Outputs, indexed by u - first_game, any may be NULL: outcome[n_games], length[n_games] (plies),
  * moves[n_games][cells] (tile + 1 in play order, 0-padded: the game record).
  * The call resets all slots of both engines at entry and leaves them as azx_reset leaves them (fresh games, all
- * active, the engine's own uid numbering); it writes no replay rows to the harvest queue.  It blocks.  Per ply the
+ * active, the engine's own uid numbering); it writes no replay rows to the harvest queue unless azx_match_set_harvest
+ * turned that on (below), and empties both engines' queues either way.  It blocks.  Per ply the
  * host reads back one counter; nothing it transfers grows with G.  a's searches run on a's stream and b's on b's,
  * concurrently.  A call that fails (AZX_EHIP, AZX_ERANGE, ...) leaves the engines where the failure found them:
  * azx_reset both before using them again.
@@ -461,6 +469,36 @@ void azx_match_destroy(azx_match *m);
 int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *outcome, int16_t *length,
                    int16_t *moves, azx_match_stats *stats);
 
+/* ---- replay rows from matches (data-collecting games between two agents) --------------------------------------
+ * Additions WITHIN ABI revision 7 (azx_version stays 7): callers detect them by symbol (dlsym azx_match_set_harvest).
+ * The reference's play_game(agents, collect_data=True) records a replay row at every ply from whichever agent moves
+ * (play_game.py:29-67, :81-98).  Every engine's move draw already writes that row (pre-move board, moves_prob, legal
+ * count, search metrics) into its own slot; with harvesting on, the step that settles a WON game copies the game's
+ * rows -- row p from the engine that moved at ply p -- into the harvest queue of one engine, where they are what
+ * throughput self-play leaves there: azx_rows_read, azx_rows_pack, azx_play_row_metrics (metric 3 flags a game's
+ * first row) and, through records, azx_replay_put_records consume them.  color = p & 1, reward = +1 / -1 for the
+ * winner's / loser's rows (play_game.py:64-65), game_uid = u.  A voided game leaves no rows (parallel_player.py:73-76).
+ * Row order: games in the order their settling steps reserved queue space (NOT by u: it depends on the pool size and
+ * on the scheduling of a ply's waves), a game's rows contiguous with plies ascending.
+ *   azx_match_set_harvest(m, on)        the following azx_match_play calls harvest into engine a's queue (on != 0)
+ *   azx_match_set_first_mover(m, mode)  -1 (default): agent u & 1 moves first in game u; 0 / 1: that agent moves first
+ *                                       in EVERY game, as play_game always starts with agents[0] (play_game.py:47);
+ *                                       anything else is AZX_EINVAL.  Independent of harvesting; first_player_wins
+ *                                       keeps counting colour 1's wins.
+ *   azx_match_rows(m, rows_out)         rows the last azx_match_play harvested (0 with harvesting off)
+ * A harvesting call sizes the queue for the worst case, n_games * cells rows (a game has at most `cells` plies; the
+ * queue is no ring and nothing is parked): a row takes 192 + 768 + 4 + 4 + 4 + 8 + 32 = 1012 bytes of device memory,
+ * so 16384 games of 11x11 reserve about 2.0 GB, kept by the engine until azx_destroy.  AZX_ENOMEM (the message names
+ * the bytes) when that cannot be had.  The rows stay readable until engine a's next play, match or tournament call.
+ * Rows are never dropped silently: should a game's rows not fit, or the two engines' row counts not add up to the
+ * game, the call fails with AZX_ESTATE after the games have been played.
+ * Note what EVERY match and tournament call, harvesting or not, does to the queues of all its engines: it empties them
+ * (rows a previous azx_play_device left there are no longer readable afterwards).  With harvesting off a call enqueues
+ * the same work and returns the same bytes as before these entry points existed. */
+int azx_match_set_harvest(azx_match *m, int on);
+int azx_match_set_first_mover(azx_match *m, int mode);
+int azx_match_rows(azx_match *m, int64_t *rows_out);
+
 /* ---- tournaments: several matches side by side in one ply loop, sharing engines ----------------------------------
  * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_tournament_create).
  * The reference hands every round's pairs to its pool at once (azalea/evaluation.py:29-58).  A tournament joins
@@ -489,7 +527,7 @@ int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games, int8_t *ou
  * tables_per_pair < 1, or an engine whose n_games < d_i * tables_per_pair (the message names the engine and both
  * numbers).  AZX_ESTATE as for azx_match_play (evaluator unregistered since, an earlier external failure).
  * The call resets all slots of all engines at entry and leaves them as azx_reset leaves them; it writes no replay
- * rows.  It blocks.  Per ply the host reads back one counter (the games decided over all pairs), plus the info words
+ * rows unless azx_tournament_set_harvest turned that on (below).  It blocks.  Per ply the host reads back one counter (the games decided over all pairs), plus the info words
  * of each engine with a registered evaluator; nothing it transfers grows with the slot count.  Engines with a
  * registered evaluator take part as in a match: per ply the host first enqueues every device-evaluated engine's whole
  * search and draw, then advances all external engines' searches point by point in turn.  A failure of an evaluator
@@ -502,6 +540,14 @@ void azx_tournament_destroy(azx_tournament *t);
 int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                         int64_t first_game, int64_t rounds, int32_t tables_per_pair,
                         int8_t *outcome, int16_t *length, int16_t *moves, azx_match_stats *stats);
+/* Replay rows from a tournament, as from a match (see azx_match_set_harvest above; detected by symbol alike):
+ * sink_engine is the index of the engine whose harvest queue takes the rows of ALL pairs (-1 = off, the default; any
+ * other value out of range is AZX_EINVAL); the queue is sized for n_pairs * rounds * cells rows.  The rows of pair s
+ * are those with game_uid in [first_game + s * rounds, first_game + (s + 1) * rounds): bit for bit the rows of the
+ * harvesting match of its two engines, whichever engine is the sink.  azx_tournament_set_first_mover: as for a match. */
+int azx_tournament_set_harvest(azx_tournament *t, int sink_engine);
+int azx_tournament_set_first_mover(azx_tournament *t, int mode);
+int azx_tournament_rows(azx_tournament *t, int64_t *rows_out);
 
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with

@@ -39,7 +39,22 @@ median of either.  The tallies of the two schedules are the same games, and are 
 
     python tools/bench_match.py --tournament [--rr-rounds 100] [--tour-agents 8] [--tour-rounds 20] [--repeats 3]
 One JSON line (profiles/tournament_bench.json).  `--tournament --trace-run`: two pooled runs of (g) and nothing else,
-for the profiler as above."""
+for the profiler as above.
+
+`--collect`: what harvesting the games' replay rows on the device costs, and what it buys (nothing of the above):
+  (h) one engine.Match of two 6x64 agents, `--big-rounds` games in `--big-slots` slots, `--repeats` times alternately
+      without and with collect="device" (the rows stay in engine a's harvest queue), medians of the device time of the
+      call (azx_match_stats.seconds) and of the wall time, and the spread (max - min) / median of either
+  (j) Player(None, [a, b], device_match=True, n_games=S).read for S in `--player-slots`, with `--chunks` games per
+      Match.play call in units of S: rows/s and games/s over `--player-reads` reads of one chunk's worth of rows
+  (k) the same two agents through the host loop (Player without device_match: play_game, one game at a time),
+      `--host-games` games
+`--collect --trace-run`: one harvesting (or, with `--no-harvest`, plain) match of (h)'s shape and nothing else, for the
+profiler as above.
+
+    python tools/bench_match.py --collect [--big-rounds 16384] [--big-slots 4096] [--repeats 3]
+                                          [--player-slots 256,4096] [--chunks 1,2,4] [--host-games 2]
+One JSON line (profiles/match_rows_bench.json)."""
 import argparse
 import json
 import os
@@ -243,8 +258,117 @@ def tournament_main(args):
     print(json.dumps(res))
 
 
+def match_engines(ag, slots):
+    """One engine per agent, as evaluation.evaluate_throughput builds them (move sampling on, noise off)."""
+    out = []
+    for k, a in enumerate(ag):
+        pol = a.policy
+        E = eng.Engine(board_size=BOARD, n_games=slots, simulations=pol.simulations, search_batch_size=pol.search_batch_size,
+                       exploration_coef=pol.exploration_coef, exploration_depth=pol.exploration_depth,
+                       noise_alpha=pol.exploration_noise_alpha, noise_scale=0.0, temperature=pol.exploration_temperature,
+                       evaluator=eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans, seed=k << 32)
+        pol.net.eval()
+        sd = {n: v for n, v in pol.net.state_dict().items() if v.dtype == torch.float32}
+        E.set_weights({n: (v.contiguous().data_ptr(), v.numel()) for n, v in sd.items()}, on_device=True)
+        out.append(E)
+    return out
+
+
+def collect_main(args):
+    from azalea_amd.parallel_player import Player
+    two = agents(args.sims, 2)
+    med = statistics.median
+    spread = lambda xs: (max(xs) - min(xs)) / med(xs)
+    res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
+           "device": torch.cuda.get_device_name(0), "repeats": args.repeats}
+    G, S = args.big_rounds, args.big_slots
+    if G > 0:
+        a, b = match_engines(two, S)
+        m = eng.Match(a, b)
+
+        def run(collect):
+            t, out = timed(lambda: m.play(G, collect=collect))
+            print("match of %d games in %d slots, collect=%s: wall %.2f s, device %.2f s, %d rows" % (
+                G, S, collect, t, out["stats"]["seconds"], out.get("n_rows", 0)), file=sys.stderr, flush=True)
+            return t, out
+
+        if args.trace_run:
+            t, out = run(False if args.no_harvest else "device")
+            print(json.dumps({"games": G, "slots": S, "harvest": not args.no_harvest, "seconds": t,
+                              "device_seconds": out["stats"]["seconds"], "rows": out.get("n_rows", 0)}))
+            return
+        m.play(min(G, 2 * S) if args.warm_games < 0 else args.warm_games, collect="device")   # warm: allocator, queue, kernel load
+        wall = {False: [], "device": []}
+        dev = {False: [], "device": []}
+        rows = plies = 0
+        for _ in range(args.repeats):
+            for collect in (False, "device"):
+                t, out = run(collect)
+                wall[collect].append(t)
+                dev[collect].append(out["stats"]["seconds"])
+                plies = out["stats"]["plies"]
+                rows = out.get("n_rows", rows)
+        res["harvest_cost"] = {
+            "games": G, "slots": S, "rows": rows, "plies": plies,
+            "off_device_seconds": dev[False], "on_device_seconds": dev["device"],
+            "off_wall_seconds": wall[False], "on_wall_seconds": wall["device"],
+            "off_games_per_sec": G / med(dev[False]), "on_games_per_sec": G / med(dev["device"]),
+            "on_rows_per_sec": rows / med(dev["device"]),
+            "on_over_off_device_seconds": med(dev["device"]) / med(dev[False]),
+            "on_over_off_wall_seconds": med(wall["device"]) / med(wall[False]),
+            "spread_off": spread(dev[False]), "spread_on": spread(dev["device"])}
+        m.close()
+        a.close()
+        b.close()
+    # (j) the two-agent Player on the device
+    res["player"] = []
+    for slots in [int(x) for x in args.player_slots.split(",") if x]:
+        for chunk in [int(x) for x in args.chunks.split(",") if x]:
+            Player.MATCH_CHUNK = chunk
+            pl = Player(None, two, device_match=True, n_games=slots, gather=False)
+            pl.read(1)                                       # the first chunk: engines, queue, kernel load
+            while pl._games:
+                pl._games.popleft()
+            secs, nrows, ngames = [], 0, 0
+            for _ in range(args.player_reads):
+                t, (frame, metrics) = timed(lambda: pl.read(1))
+                n_q = sum(len(r["reward"]) for r, _ in pl._games)
+                g_q = len(pl._games)
+                pl._games.clear()                            # the whole chunk counts: what one production yields
+                secs.append(t)
+                nrows += len(frame) + n_q
+                ngames += int(metrics["games"]) + g_q
+            pl.stop()
+            res["player"].append({"slots": slots, "chunk_games": chunk * slots, "reads": args.player_reads,
+                                  "seconds": secs, "rows": nrows, "games": ngames,
+                                  "rows_per_sec": nrows / sum(secs), "games_per_sec": ngames / sum(secs)})
+            print("player: %s" % res["player"][-1], file=sys.stderr, flush=True)
+    # (k) the host loop for the same two agents
+    if args.host_games > 0:
+        pl = Player(None, two, n_games=1, gather=False)
+
+        def host_games():
+            for _ in range(args.host_games):
+                pl._produce(1)
+        t, _ = timed(host_games)
+        rows = sum(len(r["reward"]) for r, _ in pl._games)
+        res["host_loop"] = {"games": len(pl._games), "rows": rows, "seconds": t, "games_per_sec": len(pl._games) / t,
+                            "rows_per_sec": rows / t}
+        pl.stop()
+        print("host loop: %s" % res["host_loop"], file=sys.stderr, flush=True)
+        for r in res["player"]:
+            r["over_host_loop_rows_per_sec"] = r["rows_per_sec"] / res["host_loop"]["rows_per_sec"]
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--collect", action="store_true")
+    ap.add_argument("--no-harvest", action="store_true", help="--collect --trace-run: the same match without harvesting")
+    ap.add_argument("--warm-games", type=int, default=-1)
+    ap.add_argument("--player-slots", default="256,4096")
+    ap.add_argument("--chunks", default="1,2,4")
+    ap.add_argument("--player-reads", type=int, default=1)
     ap.add_argument("--external", action="store_true")
     ap.add_argument("--ext-games", type=int, default=256)
     ap.add_argument("--ext-slots", type=int, default=256)
@@ -261,6 +385,8 @@ def main():
     ap.add_argument("--tour-agents", type=int, default=8)
     ap.add_argument("--tour-rounds", type=int, default=20)
     args = ap.parse_args()
+    if args.collect:
+        return collect_main(args)
     if args.external:
         return external_main(args)
     if args.tournament:
