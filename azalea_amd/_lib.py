@@ -23,6 +23,7 @@ def record_bytes(cells):
 
 EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH, EVAL_EXTERNAL = 0, 1, 2, 3
 FLAG_NO_COMPACT = 1
+FLAG_RANDOM_REFLECT = 2  # AZX_FLAG_RANDOM_REFLECT: evaluation requests randomly turned by 180 degrees (opt-in)
 EEXTERNAL = -7           # AZX_EEXTERNAL: the registered external evaluator failed or produced a bad row
 
 
@@ -116,6 +117,7 @@ SYMBOLS = {
     "azx_replay_collate": (C.c_int, [_vp, C.c_int64, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _i32p]),
     "azx_replay_collate_async": (C.c_int, [_vp, C.c_int64, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "azx_replay_set_mover_view": (C.c_int, [_vp, C.c_int]),
+    "azx_replay_set_reflect": (C.c_int, [_vp, C.c_int, C.c_uint64]),
     "azx_selftest_arith": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "azx_selftest_divide": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "azx_selftest_dirichlet": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint32, _f32p]),

@@ -96,6 +96,8 @@ struct azx_engine {
     int64_t ring_idx_cap = 0;
     int32_t *ring_maxk = nullptr;
     bool ring_mover_view = false;       // azx_replay_set_mover_view
+    bool ring_reflect = false;          // azx_replay_set_reflect: its seed, and the collates (blocking + async) since
+    uint64_t ring_reflect_seed = 0, ring_reflect_count = 0;
     std::vector<void *> ring_allocs;
     // azx_replay_collate_async: index staging, AZX_COLLATE_SLOTS deep (pinned host + device), one event per slot
     long long *cidx_host[8] = {nullptr}, *cidx_dev[8] = {nullptr};
@@ -183,6 +185,11 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
         return fail(AZX_EINVAL, "unknown evaluator %d", cfg->evaluator);
     if (cfg->device < 0 || cfg->device >= ndev)
         return fail(AZX_EINVAL, "device %d not in [0, %d)", cfg->device, ndev);
+    if ((cfg->flags & AZX_FLAG_RANDOM_REFLECT) &&
+        (cfg->evaluator == AZX_EVAL_UNIFORM || cfg->evaluator == AZX_EVAL_UNIFORM_HASH))
+        return fail(AZX_EINVAL, "AZX_FLAG_RANDOM_REFLECT needs a network input to reflect: the inline evaluator %s has "
+                                "none (use AZX_EVAL_RESNET or AZX_EVAL_EXTERNAL)",
+                    cfg->evaluator == AZX_EVAL_UNIFORM ? "AZX_EVAL_UNIFORM" : "AZX_EVAL_UNIFORM_HASH");
     if (cfg->game_index_stride < 0 || cfg->game_index_offset < 0 ||
         cfg->game_index_offset >= std::max(1, cfg->game_index_stride))
         return fail(AZX_EINVAL, "game_index_offset %d outside [0, game_index_stride %d)", cfg->game_index_offset,
@@ -422,6 +429,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " AZX_PIPELINE=" + (e->pipeline ? "1" : "0") +
                        " AZX_PIPELINE_STAGGER=" + (e->stagger ? "1" : "0") +
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
+                       " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -935,9 +943,10 @@ extern "C" int azx_get_leaves(azx_engine *e, int cap, int32_t *boards, int32_t *
                 boards[(size_t)j * d.ncells + c] = hb[(size_t)ev * AZX_CELL_STRIDE + c];
         if (legal_moves) {
             for (int c = 0; c < d.ncells; ++c) legal_moves[(size_t)j * d.ncells + c] = 0;
-            for (size_t i = 0; i < cells.size(); ++i)
-                legal_moves[(size_t)j * d.ncells + i] =
-                    (hflip[ev] ? flip_cell(cells[i], d.N) : cells[i]) + 1;
+            for (size_t i = 0; i < cells.size(); ++i) {
+                const int t = (hflip[ev] & 1) ? flip_cell(cells[i], d.N) : cells[i];
+                legal_moves[(size_t)j * d.ncells + i] = ((hflip[ev] & 2) ? d.ncells - 1 - t : t) + 1;   // bit 1: turned by 180 degrees
+            }
         }
     }
     return AZX_OK;
@@ -1685,6 +1694,13 @@ extern "C" int azx_replay_fill(azx_engine *e, int64_t min_positions, int64_t max
     return AZX_OK;
 }
 
+// azx_replay_set_reflect: the key of this collate's row bits -- (seed, collates since the seed was set), nothing of
+// the ring -- and the count moves on, for the blocking and the enqueued collate alike
+static unsigned long long reflect_key(azx_engine *e) {
+    if (!e->ring_reflect) return 0ull;
+    return azx_mix64(azx_mix64(e->ring_reflect_seed ^ 0x5245464C45435421ull) + e->ring_reflect_count++);
+}
+
 extern "C" int azx_replay_collate(azx_engine *e, int64_t batch, const int64_t *indices, int64_t *color_dev,
                                   int32_t *legal_moves_dev, int64_t *result_dev, int32_t *board_dev,
                                   float *moves_prob_dev, float *reward_dev, int32_t *max_k_out) {
@@ -1715,7 +1731,8 @@ extern "C" int azx_replay_collate(azx_engine *e, int64_t batch, const int64_t *i
     HIPCHECK(hipMemsetAsync(e->ring_maxk, 0, sizeof(int32_t), e->stream));
     azx_launch_replay_collate(e->ring, e->ring_idx, (int)batch, e->d.ncells, (long long *)color_dev,
                               legal_moves_dev, (long long *)result_dev, board_dev, moves_prob_dev, reward_dev,
-                              e->ring_maxk, e->ring_mover_view ? e->d.N : 0, e->stream);
+                              e->ring_maxk, e->ring_mover_view ? e->d.N : 0, e->ring_reflect ? 1 : 0,
+                              reflect_key(e), e->stream);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(max_k_out, e->ring_maxk, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -1728,6 +1745,15 @@ extern "C" int azx_replay_set_mover_view(azx_engine *e, int on) {
     if (!e) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
     e->ring_mover_view = on != 0;
+    return AZX_OK;
+}
+
+extern "C" int azx_replay_set_reflect(azx_engine *e, int on, uint64_t seed) {
+    if (!e) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    e->ring_reflect = on != 0;
+    e->ring_reflect_seed = seed;
+    e->ring_reflect_count = 0;
     return AZX_OK;
 }
 
@@ -1766,7 +1792,8 @@ extern "C" int azx_replay_collate_async(azx_engine *e, int64_t batch, const int6
     HIPCHECK(hipMemcpyAsync(e->cidx_dev[slot], e->cidx_host[slot], (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, st));
     azx_launch_replay_collate(e->ring, e->cidx_dev[slot], (int)batch, e->d.ncells, (long long *)color_dev,
                               legal_moves_dev, (long long *)result_dev, board_dev, moves_prob_dev, reward_dev,
-                              e->cidx_maxk, e->ring_mover_view ? e->d.N : 0, st);
+                              e->cidx_maxk, e->ring_mover_view ? e->d.N : 0, e->ring_reflect ? 1 : 0,
+                              reflect_key(e), st);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(e->cidx_ev[slot], st));
     return AZX_OK;

@@ -91,7 +91,7 @@ struct DevEngine {
     // evaluation requests / results (packed by atomic counter)
     uint8_t *ev_board;      // [E][AZX_CELL_STRIDE] network input (first player's view)
     int32_t *ev_src;        // [E] g*bs + i
-    int32_t *ev_flip;       // [E] 1 if the board was flipped (mover is O)
+    int32_t *ev_flip;       // [E] bit 0: the board was flipped (mover is O); bit 1: turned by 180 degrees (AZX_FLAG_RANDOM_REFLECT)
     float *ev_value;        // [E]
     float *ev_prior;        // [E][AZX_CELL_STRIDE] by ORIGINAL cell index
     int32_t *n_eval;        // [1]

@@ -74,7 +74,8 @@ __global__ __launch_bounds__(1024) void k_ext_scan(DevEngine E, ExtBufs x) {
 }
 
 // one wavefront per row: the int32 board and the legal list (ascending original cells, mapped through the flip
-// when the mover is O, + 1), zero-padded to the row width -- what azx_get_leaves builds on the host
+// when the mover is O and through the 180-degree turn when ev_flip bit 1 is set, + 1), zero-padded to the row width
+// -- what azx_get_leaves builds on the host
 __global__ __launch_bounds__(256) void k_ext_export(DevEngine E, ExtBufs x, int n) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(256) void k_ext_export(DevEngine E, ExtBufs x, int 
         const int c = s * 64 + lane;
         if ((m >> lane) & 1ull) {
             const int pos = pre + __popcll(m & ((1ull << lane) - 1ull));
-            ol[pos] = (flip ? ext_flip_cell(c, E.N) : c) + 1;
+            const int t = (flip & 1) ? ext_flip_cell(c, E.N) : c;
+            ol[pos] = ((flip & 2) ? nc - 1 - t : t) + 1;            // bit 1: the board was turned by 180 degrees
         }
         pre += __popcll(m);
     }

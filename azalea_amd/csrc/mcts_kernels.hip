@@ -744,12 +744,23 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     };
 
     // ---- emit one evaluation request: network-input board (flipped for O) ----------------
-    auto emit_request = [&](int e, int src_index, const unsigned char *colors, int mover) {
+    // AZX_FLAG_RANDOM_REFLECT (off by default, outside every parity claim): request number `ordinal` of this move's
+    // search (0 = the root request, 1 + select index of the batch's first descent + u for unique leaf u) draws one
+    // bit from the game's key on a stream of its own -- a pure function of (seed, uid, ply, ordinal), nothing of it
+    // shared with the Dirichlet words (noise_base + sel * golden) or the Philox move draw.  A set bit hands the
+    // network the board turned by 180 degrees (cell index reversed; it commutes with the O-flip) and is carried as
+    // bit 1 of ev_flip, so that whoever maps network cells back to original cells undoes it.
+    const bool reflect_on = !FAST && (E.flags & AZX_FLAG_RANDOM_REFLECT) != 0;
+    auto emit_request = [&](int e, int src_index, const unsigned char *colors, int mover, int ordinal) {
         const bool flip = mover == 2;                       // state.color == 1: mcts.py:178
+        bool rot = false;
+        if (reflect_on)
+            rot = (mix32((noise_base ^ 0x52464C54u) + (uint32_t)ordinal * 0x85ebca6bu) >> 31) != 0u;
         for (int o = lane; o < AZX_CELL_STRIDE; o += 64) {
             unsigned char v = 0;
             if (o < ncells) {
-                const int src = flip ? flip_src(o, N) : o;
+                const int on = rot ? ncells - 1 - o : o;    // the unrotated network cell shown at o
+                const int src = flip ? flip_src(on, N) : on;
                 v = colors[src];
                 if (flip && v) v = 3 - v;
             }
@@ -757,7 +768,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         }
         if (lane == 0) {
             E.ev_src[e] = src_index;
-            E.ev_flip[e] = flip ? 1 : 0;
+            E.ev_flip[e] = (flip ? 1 : 0) | (rot ? 2 : 0);
         }
     };
 
@@ -807,7 +818,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             int e = 0;
             if (lane == 0) e = atomicAdd(E.n_eval, 1);
             e = __builtin_amdgcn_readfirstlane(e);
-            emit_request(e, g * bs + 0, L.colors, root.color);
+            emit_request(e, g * bs + 0, L.colors, root.color, 0);
             if (lane == 0) {
                 const size_t lb = (size_t)g * bs;
                 E.leaf_node[lb] = root_id;
@@ -1332,7 +1343,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     for (int s = 0; s < SLOTS; ++s) E.leaf_mask[(lb + u) * 4 + s] = rl64(m_mask[s], i);
                 }
                 if (!terminal) {
-                    emit_request(e, g * bs + u, L.colors + i * AZX_CELL_STRIDE, tm >> 1);
+                    emit_request(e, g * bs + u, L.colors + i * AZX_CELL_STRIDE, tm >> 1, 1 + select_count - bs + u);
                     e += 1;
                     c_evals += 1;
                 } else {

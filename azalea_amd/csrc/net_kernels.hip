@@ -1514,9 +1514,10 @@ __global__ __launch_bounds__(256, 3) void k_heads_mfma(NetDev P, const float *__
         for (int s2 = 0; s2 < 2; ++s2) {
             const int cell = s2 * 64 + lane;
             if (cell < ncells) {
-                int oc = cell;
-                if (flip) {                            // back to the mover's frame (hex.py:107-111)
-                    const int i = cell / N, j = cell - i * N;
+                const int uc = (flip & 2) ? ncells - 1 - cell : cell;   // undo the 180-degree turn (AZX_FLAG_RANDOM_REFLECT)
+                int oc = uc;
+                if (flip & 1) {                        // back to the mover's frame (hex.py:107-111)
+                    const int i = uc / N, j = uc - i * N;
                     oc = (N - 1 - j) * N + (N - 1 - i);
                 }
                 prior_out[(size_t)e * AZX_CELL_STRIDE + oc] = legal[s2] ? expf(x[s2] - lse) : 0.f;
@@ -1712,9 +1713,10 @@ __global__ __launch_bounds__(192 * HEADS_KSPLIT) void k_heads(NetDev P, const fl
         for (int s = 0; s < 3; ++s) {
             const int cell = s * 64 + lane;
             if (cell < ncells) {
-                int oc = cell;
-                if (flip) {                            // back to the mover's frame (hex.py:107-111)
-                    const int i = cell / N, j = cell - i * N;
+                const int uc = (flip & 2) ? ncells - 1 - cell : cell;   // undo the 180-degree turn (AZX_FLAG_RANDOM_REFLECT)
+                int oc = uc;
+                if (flip & 1) {                        // back to the mover's frame (hex.py:107-111)
+                    const int i = uc / N, j = uc - i * N;
                     oc = (N - 1 - j) * N + (N - 1 - i);
                 }
                 prior_out[(size_t)e * AZX_CELL_STRIDE + oc] = legal[s] ? expf(x[s] - lse) : 0.f;

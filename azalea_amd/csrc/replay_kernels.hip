@@ -45,10 +45,16 @@ __global__ __launch_bounds__(64) void k_replay_put(ReplayRows src, ReplayRows ri
 // view the SEARCH evaluates them in (mcts.py:178-181, hex.py flip_player_board_moves) -- colours swapped, the board
 // mirrored along the anti-diagonal, every legal move mapped with it in its original list position (so moves_prob
 // stays aligned) -- on a board of mover_n x mover_n cells.
+// reflect != 0 (azx_replay_set_reflect; NOT the reference's batch either: its Hex random_reflect is the identity,
+// hex.py:124-134): output row b draws one bit from (reflect_key, b) -- reflect_key = a mix of the caller's seed and the
+// number of collates since it was set, never the ring index -- and a set bit hands the row out turned by 180 degrees,
+// AFTER the mover view: the board's cell index reversed, every legal entry t as ncells + 1 - t in its original list
+// position; moves_prob, colour, reward, max_k and the padding are untouched.
 __global__ __launch_bounds__(64) void k_replay_collate(ReplayRows ring, const long long *idx, int B,
                                                        int ncells, long long *color, int32_t *legal,
                                                        long long *result, int32_t *board,
-                                                       float *prob, float *reward, int32_t *max_k, int mover_n) {
+                                                       float *prob, float *reward, int32_t *max_k, int mover_n,
+                                                       int reflect, unsigned long long reflect_key) {
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
     if (b >= B) return;
@@ -57,6 +63,8 @@ __global__ __launch_bounds__(64) void k_replay_collate(ReplayRows ring, const lo
     const float *rp = ring.prob + r * AZX_CELL_STRIDE;
     const int k = ring.k[r];
     const bool flip = mover_n > 0 && ring.color[r] == 1;
+    const bool rot = reflect != 0 &&
+                     (azx_mix64(reflect_key + (unsigned long long)(b + 1) * 0x9E3779B97F4A7C15ull) >> 63) != 0ull;
     int base = 0;
 #pragma unroll
     for (int s = 0; s < AZX_CELL_STRIDE / 64; ++s) {
@@ -69,6 +77,7 @@ __global__ __launch_bounds__(64) void k_replay_collate(ReplayRows ring, const lo
             const int row = c / mover_n, col = c - row * mover_n;
             fc = (mover_n - 1 - col) * mover_n + (mover_n - 1 - row);
         }
+        if (rot && on) fc = ncells - 1 - fc;
         if (on) {
             board[(size_t)b * ncells + fc] = flip && v ? 3 - v : v;
             prob[(size_t)b * ncells + c] = c < k ? rp[c] : 0.0f;
@@ -179,8 +188,9 @@ void azx_launch_replay_put(const ReplayRows &src, const ReplayRows &ring, long l
 
 void azx_launch_replay_collate(const ReplayRows &ring, const long long *idx, int B, int ncells,
                                long long *color, int32_t *legal, long long *result, int32_t *board,
-                               float *prob, float *reward, int32_t *max_k, int mover_n, hipStream_t st) {
+                               float *prob, float *reward, int32_t *max_k, int mover_n, int reflect,
+                               unsigned long long reflect_key, hipStream_t st) {
     if (B <= 0) return;
     hipLaunchKernelGGL(k_replay_collate, dim3(B), dim3(64), 0, st, ring, idx, B, ncells, color, legal,
-                       result, board, prob, reward, max_k, mover_n);
+                       result, board, prob, reward, max_k, mover_n, reflect, reflect_key);
 }

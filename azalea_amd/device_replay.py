@@ -24,6 +24,8 @@ _KEYS = ("color", "legal_moves", "result", "board", "moves_prob", "reward")
 class DeviceReplayBuffer:
     learner = None      # (class defaults: a buffer built around an existing ring without __init__ plays its refills inline)
     ahead = None
+    _reflect = False
+    reflect_seed = 0
 
     def __init__(self, engine, capacity: int, contents: ReplayDataFrame = None, shared: bool = True):
         """`engine`: azalea_amd.engine.Engine whose self-play feeds the buffer (Player._get_engine).
@@ -39,6 +41,8 @@ class DeviceReplayBuffer:
         self._retired = deque()         # (record chunks, event): chunks whose ring put may still be in flight
         self.last_exchange = None       # timing of the last shared refill (bench / diagnostics)
         self._mover_view = False
+        self._reflect = False
+        self.reflect_seed = 0           # the seed random_reflect = True hands to azx_replay_set_reflect
         self.device = getattr(engine, "torch_device", None) or torch.device("cuda", engine.cfg.device)
         if contents is not None and len(contents):
             self.put(contents)
@@ -55,6 +59,19 @@ class DeviceReplayBuffer:
     def mover_view(self, on: bool) -> None:
         self.engine.replay_set_mover_view(bool(on))
         self._mover_view = bool(on)
+
+    @property
+    def random_reflect(self) -> bool:
+        """NOT the reference's batch either (off by default; its Hex random_reflect is the identity): minibatches
+        hand out about half their rows turned by 180 degrees (azx_replay_set_reflect, include/azx.h;
+        policy_trainer.train's config["random_reflect"]), after the mover view when both are on.  Turning it on
+        (re)starts the bit sequence from `reflect_seed`.  The ring itself never changes."""
+        return self._reflect
+
+    @random_reflect.setter
+    def random_reflect(self, on: bool) -> None:
+        self.engine.replay_set_reflect(bool(on), self.reflect_seed)
+        self._reflect = bool(on)
 
     # ---- ReplayBuffer surface -----------------------------------------------------------------
     def __len__(self) -> int:
@@ -314,14 +331,18 @@ class DeviceReplayBuffer:
         idx = np.arange(len(self)) if indices is None else np.asarray(indices, np.int64)
         if not len(idx):
             return {}
-        view = self._mover_view
+        view, reflect = self._mover_view, self._reflect
         if view:
             self.mover_view = False      # checkpoints hold the rows as the ring does: absolute colours
+        if reflect:
+            self.random_reflect = False  # ... and unturned
         try:
             return {k: v.cpu().numpy() for k, v in self.sample(idx).items()}
         finally:
             if view:
                 self.mover_view = True
+            if reflect:
+                self.random_reflect = True
 
     def state_dict(self) -> Dict:
         return {"rows": self.rows(), "write_idx": self.write_idx, "fresh_counter": self.fresh_counter}

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EVAL_EXTERNAL, EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH,  # noqa: F401
-                   FLAG_NO_COMPACT, AzxError, Config, MatchStats, PlayStats, check)
+                   FLAG_NO_COMPACT, FLAG_RANDOM_REFLECT, AzxError, Config, MatchStats, PlayStats, check)
 
 
 def _p(a, ctype):
@@ -505,6 +505,11 @@ class Engine:
     def replay_set_mover_view(self, on: bool):
         """azx_replay_set_mover_view: the collates hand out the second player's rows as the search sees them."""
         check(self.L.azx_replay_set_mover_view(self.h, 1 if on else 0))
+
+    def replay_set_reflect(self, on: bool, seed: int = 0):
+        """azx_replay_set_reflect: the collates hand out about half their rows turned by 180 degrees, the bit of
+        output row b a function of (seed, collates since this call, b).  Every call restarts the collate count."""
+        check(self.L.azx_replay_set_reflect(self.h, 1 if on else 0, int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def replay_collate_async(self, indices, out, stream):
         """replay_collate enqueued on `stream` (a hipStream_t as int) without synchronising and without max_k."""

@@ -75,7 +75,7 @@ class Player:
     MATCH_CHUNK = 2                   # device_match: games per Match.play call, in units of n_games
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
-                 external_batch: bool = False, device_match: bool = False):
+                 external_batch: bool = False, device_match: bool = False, random_reflect: bool = False):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -87,7 +87,12 @@ class Player:
         other in two engines of `n_games` slots on the device (agents[0] moves first in every game), and the games'
         replay rows are harvested there.  HexNetwork agents use the device tower; other networks need
         external_batch=True as well.  A ValueError when any of that does not hold, or under torch.distributed with
-        gather=True: there is no silent fall-back to the host loop."""
+        gather=True: there is no silent fall-back to the host loop.
+        `random_reflect` (NOT the reference's behaviour for Hex, whose random_reflect is the identity; off by
+        default): the engines this Player builds -- device self-play, external_batch, both engines of device_match
+        -- hand the network about half of all evaluation requests turned by 180 degrees
+        (engine.FLAG_RANDOM_REFLECT, include/azx.h).  A ValueError when the games would run through the host loop
+        instead."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.agents = agents
@@ -99,6 +104,12 @@ class Player:
             self._match_policies()
         elif self.external_batch:
             self._external_policy()
+        self.random_reflect = bool(random_reflect)
+        if self.random_reflect and not (self.device_match or self.external_batch) and self._device_policy() is None:
+            raise ValueError("random_reflect needs the games to run in a device engine (a single agent whose Policy "
+                             "holds a HexNetwork, external_batch=True or device_match=True): these agents play "
+                             "through the host loop, which does not reflect")
+        self._engine_flags = _eng.FLAG_RANDOM_REFLECT if self.random_reflect else 0
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -351,6 +362,7 @@ class Player:
                 temperature=pol.exploration_temperature if sampling else 0.0,
                 evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
                 num_blocks=pol.num_blocks, base_chans=pol.base_chans,
+                flags=self._engine_flags,
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
             self._engine_key = key
         return self._engine
@@ -404,6 +416,7 @@ class Player:
                            num_blocks=getattr(pol, "num_blocks", 0) if external else pol.num_blocks,
                            base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
                            device=dev.index or 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
+                           flags=self._engine_flags,
                            seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
 
     def _produce_match(self, pols) -> None:

@@ -22,7 +22,7 @@ from torch.utils.data import DataLoader
 from . import distributed as azdist
 from .azalea_agent import AzaleaAgent
 from .parallel_player import Player
-from .prep import torch_batch_replays
+from .prep import rot180_batch, torch_batch_replays
 from .replay_buffer import ReplayBuffer
 from .utils import import_and_get
 
@@ -282,7 +282,16 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
 
     config["selfplay_external_batch"] (default False): a network other than HexNetwork (config["network"] naming
     another class) plays its self-play in one batched engine on the device instead of the host loop
-    (Player(external_batch=True)); its training step stays the stock PyTorch one."""
+    (Player(external_batch=True)); its training step stays the stock PyTorch one.
+
+    config["random_reflect"] (default False; NOT the reference's behaviour for Hex, and outside every parity claim):
+    what the reference's two game.random_reflect call sites (mcts.py:183-186, policy_trainer.py:84) would do if its Hex
+    random_reflect were not the identity -- the 180-degree turn, the one symmetry that keeps each player's direction
+    (game/hex.py:124-134).  Self-play hands the network about half its evaluation requests turned
+    (Player(random_reflect=True)), and so do the training batches: the collate kernel with device_replay
+    (DeviceReplayBuffer.random_reflect, seeded from config["seed"]), prep.rot180_batch on each host batch otherwise
+    (mask from a torch.Generator seeded from config["seed"]; after to_mover_view when both are on).  Neither its cost
+    nor its effect on strength has been measured."""
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])
     torch.manual_seed(config["seed"])
@@ -317,7 +326,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     agent = AzaleaAgent(game_factory, policy=policy, device=config["device"])
     lockstep_role = ("leader" if leader else "follower") if mode == "lockstep" else None
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
-                    external_batch=bool(config.get("selfplay_external_batch", False)))
+                    external_batch=bool(config.get("selfplay_external_batch", False)),
+                    random_reflect=bool(config.get("random_reflect", False)))
     if mode == "actor_learner" and player._device_policy() is None:
         raise ValueError("selfplay_mode 'actor_learner' needs a Policy that holds a HexNetwork; use 'lockstep'")
     from_ring = False
@@ -326,11 +336,24 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
         logging.info("training batches: %s", "second player's rows flipped to the search's view (train_mover_view)"
                      if mover_view else "absolute boards, as the reference trains (config['train_mover_view'] = True "
                      "trains in the view the search evaluates in: DESIGN 8.6)")
+    reflect = bool(config.get("random_reflect", False))
+    reflect_gen = None
+    if reflect and not device_replay:
+        reflect_gen = torch.Generator()
+        reflect_gen.manual_seed(int(config["seed"]))
+    if leader:
+        logging.info("random 180-degree reflection (config['random_reflect']): %s",
+                     "off" if not reflect else
+                     "on -- self-play evaluation requests (engine flag) and training batches (%s)"
+                     % ("collate kernel" if device_replay else "prep.rot180_batch on host batches"))
     if device_replay:
         from .device_replay import DeviceReplayBuffer
         if not isinstance(replaybuf, DeviceReplayBuffer):
             replaybuf = DeviceReplayBuffer(player.device_engine(), len(replaybuf), replaybuf)
         replaybuf.mover_view = mover_view         # the collate kernel flips; host batches are flipped below
+        if reflect or replaybuf.random_reflect:
+            replaybuf.reflect_seed = int(config["seed"])
+            replaybuf.random_reflect = reflect    # the collate kernel turns; host batches are turned below
     elif mode == "actor_learner":
         player._agree_seed_base()          # a collective the actors make in device_engine(): rank 0 joins it here
     if history is not None and mode:
@@ -367,7 +390,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
             batches = lambda: replaybuf.loader(batch_size)
             if gstep is not None:
                 # the captured / hand-written step reads its rows straight from the ring: iterate the epoch's index
-                # chunks, the same order loader() visits (random_reflect is the identity for Hex, hex.py:124-134)
+                # chunks, the same order loader() visits (game.random_reflect is the identity for Hex, hex.py:124-134;
+                # config["random_reflect"] turns rows inside the collate)
                 def index_chunks():
                     order = replaybuf.epoch_indices()
                     for s in range(0, len(order), batch_size):
@@ -423,6 +447,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
                     if mover_view and not device_replay:
                         batch = to_mover_view(batch, game_class)
                     batch = game_class.random_reflect(batch)
+                    if reflect_gen is not None:
+                        batch = rot180_batch(batch, torch.randint(0, 2, (len(batch["reward"]),), generator=reflect_gen))
                     if gstep is not None and len(batch["reward"]) == batch_size:
                         l3 = gstep.step({k: v.to(device) for k, v in batch.items()})
                         loss_dev = l3[0].clone() if loss_dev is None else loss_dev + l3[0]

@@ -56,8 +56,28 @@ enum {
 };
 
 enum {
-    AZX_FLAG_NO_COMPACT = 1  /* keep the reference's never-free arena + moving root_id
+    AZX_FLAG_NO_COMPACT = 1, /* keep the reference's never-free arena + moving root_id
                                 (search_tree.py:115-132) instead of compacting on advance */
+    AZX_FLAG_RANDOM_REFLECT = 2  /* NOT the reference's behaviour for Hex (off by default, outside every parity claim).
+                                The reference calls game.random_reflect on every leaf batch before the network sees it
+                                (mcts.py:183-186); its Hex implementation returns its inputs and names the one transform
+                                that keeps the player's direction, np.rot90(b, 2) (game/hex.py:124-134).  With this flag
+                                every evaluation request -- the root request of a search and every leaf -- draws one bit
+                                that is a pure function of (seed, game uid, ply, ordinal of the request within that
+                                move's search: 0 = root, then 1 + select index of the leaf's batch start + its place
+                                among the batch's unique leaves), from the game's key on a stream of its own: it shares
+                                nothing with the Dirichlet or move draws and does not depend on the slot, n_games, the
+                                half-pool, the launch or the order requests were queued in.  A set bit hands the
+                                evaluator the board turned by 180 degrees (cell c -> cells - 1 - c, composed with the
+                                perspective flip; the two commute) and the legal list t -> cells + 1 - t in its ORIGINAL
+                                order; priors are mapped back, so everything behind the evaluator (azx_put_evals /
+                                azx_get_evals "prior j = child j", the trees, the rows) is indexed as without the flag.
+                                Internally the engine's per-request word ev_flip carries the turn as bit 1 (bit 0 = the
+                                perspective flip).  AZX_EVAL_RESNET and AZX_EVAL_EXTERNAL (phase API and registered
+                                evaluator) only: azx_create with AZX_EVAL_UNIFORM / AZX_EVAL_UNIFORM_HASH, which have
+                                no network input, is AZX_EINVAL.  Matches and tournaments take the flag per engine.
+                                azx_kernel_info reports reflect=on|off.  An addition WITHIN ABI revision 7: azx_config
+                                is unchanged. */
 };
 
 typedef struct {
@@ -90,7 +110,8 @@ typedef struct azx_engine azx_engine;
 const char *azx_last_error(void);
 int azx_version(void);            /* ABI revision: 7 = azx_set_external_evaluator, AZX_EEXTERNAL (throughput self-play and
                                    *     azx_search with a caller-supplied evaluator over device buffers); the azx_match_*
-                                   *     entry points were added within revision 7 -- callers detect them by symbol;
+                                   *     entry points were added within revision 7 -- callers detect them by symbol; so
+                                   *     were AZX_FLAG_RANDOM_REFLECT (azx_config unchanged) and azx_replay_set_reflect;
                                    * 6 = azx_reserve_cus, azx_replay_put_records_async (self-play beside training);
                                    * 5 = AZX_ERANGE, azx_debug_weights, weights packed on the device
                                    * (4 = 8-float row metrics, azx_kernel_info, azx_debug_set_queue_cap;
@@ -150,7 +171,8 @@ int azx_search_begin(azx_engine *e, const double *noise, int n_select, int noise
 int azx_search_step(azx_engine *e, int *n_pending, int *done);
 /* pending positions in (slot, leaf order) order: boards[n][cells] int32 already flipped to
  * the first player's view (mcts.py:178-181), legal_moves[n][cells] padded with 0 (flipped
- * tiles, original order), slot[n], k[n]. */
+ * tiles, original order), slot[n], k[n].  With AZX_FLAG_RANDOM_REFLECT about half the rows come
+ * turned by 180 degrees as well (board and tiles alike). */
 int azx_get_leaves(azx_engine *e, int cap, int32_t *boards, int32_t *legal_moves,
                    int32_t *slot, int32_t *k, int *n_out);
 /* value[n], prior[n][cells] (prior j = child j, first k entries) in the same order */
@@ -360,6 +382,17 @@ int azx_replay_collate_async(azx_engine *e, int64_t batch, const int64_t *indice
  * original list position (moves_prob stays aligned; `color` still reports the mover).  The training distribution then
  * is the distribution the search evaluates. */
 int azx_replay_set_mover_view(azx_engine *e, int on);
+
+/* NOT the reference's batch either (off by default): the training-side twin of AZX_FLAG_RANDOM_REFLECT.  The reference
+ * calls game.random_reflect on every training batch (policy_trainer.py:84); for Hex that is the identity
+ * (game/hex.py:124-134).  With on != 0 both collates draw one bit per OUTPUT row from (seed, number of collates --
+ * blocking or enqueued -- since this call, row b of the batch), never from the ring index, and hand a row whose bit is
+ * set out turned by 180 degrees: the board with its cell index reversed (c -> cells - 1 - c), every legal entry t as
+ * cells + 1 - t in its ORIGINAL list position (moves_prob stays aligned), colour, reward, max_k and padding untouched.
+ * It composes with the mover view: view first, then the turn.  The ring never changes; every call resets the collate
+ * count.  An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol
+ * (dlsym azx_replay_set_reflect). */
+int azx_replay_set_reflect(azx_engine *e, int on, uint64_t seed);
 
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
