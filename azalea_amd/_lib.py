@@ -24,6 +24,7 @@ def record_bytes(cells):
 EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH, EVAL_EXTERNAL = 0, 1, 2, 3
 FLAG_NO_COMPACT = 1
 FLAG_RANDOM_REFLECT = 2  # AZX_FLAG_RANDOM_REFLECT: evaluation requests randomly turned by 180 degrees (opt-in)
+FLAG_TOWER_F16 = 4       # AZX_FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product (opt-in, outside every parity claim)
 EEXTERNAL = -7           # AZX_EEXTERNAL: the registered external evaluator failed or produced a bad row
 
 

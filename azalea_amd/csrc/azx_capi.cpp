@@ -190,6 +190,9 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
         return fail(AZX_EINVAL, "AZX_FLAG_RANDOM_REFLECT needs a network input to reflect: the inline evaluator %s has "
                                 "none (use AZX_EVAL_RESNET or AZX_EVAL_EXTERNAL)",
                     cfg->evaluator == AZX_EVAL_UNIFORM ? "AZX_EVAL_UNIFORM" : "AZX_EVAL_UNIFORM_HASH");
+    if ((cfg->flags & AZX_FLAG_TOWER_F16) && cfg->evaluator != AZX_EVAL_RESNET)     // (shape, AZX_TOWER=fp32: azx_net_create)
+        return fail(AZX_EINVAL, "AZX_FLAG_TOWER_F16 selects a tower kernel of the built-in network: evaluator %d is not "
+                                "AZX_EVAL_RESNET", cfg->evaluator);
     if (cfg->game_index_stride < 0 || cfg->game_index_offset < 0 ||
         cfg->game_index_offset >= std::max(1, cfg->game_index_stride))
         return fail(AZX_EINVAL, "game_index_offset %d outside [0, game_index_stride %d)", cfg->game_index_offset,
@@ -255,7 +258,8 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
 #undef A
     if (rc) { azx_destroy(e); return rc; }
     if (cfg->evaluator == AZX_EVAL_RESNET) {
-        rc = azx_net_create(&e->net, d.N, cfg->num_blocks, cfg->base_chans, (int)E, e->stream);
+        rc = azx_net_create(&e->net, d.N, cfg->num_blocks, cfg->base_chans, (int)E,
+                            (cfg->flags & AZX_FLAG_TOWER_F16) ? 1 : 0, e->stream);
         if (rc) { g_err = azx_net_error(); azx_destroy(e); return rc; }
     }
     {   // inverse-CDF table of the device Dirichlet sampler for this engine's alpha

@@ -7,7 +7,10 @@
 
 struct AzxNet;
 
-int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, hipStream_t st);
+// tower_f16 != 0 (AZX_FLAG_TOWER_F16): the plain-f16 tower k_tower_f16_s16 instead of the split-f16 one; AZX_EINVAL when
+// the shape has no fused tower (azx_net_has_fused_tower) or AZX_TOWER=fp32 is set
+int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, int tower_f16, hipStream_t st);
+bool azx_net_has_fused_tower(int N, int blocks, int chans);   // 64 channels, <= 121 cells, >= 1 block
 void azx_net_destroy(AzxNet *net);
 // the engine re-made its stream (azx_reserve_cus): use `st` from now on and make the wide tower's side streams on the
 // same CU mask (`mask` words, 0 words = all CUs); the old side streams are drained and dropped
@@ -16,7 +19,7 @@ const char *azx_net_error();
 int azx_net_set_weights(AzxNet *net, int n, const char *const *names, const void *const *ptrs,
                         const int64_t *counts, int on_device);
 bool azx_net_ready(const AzxNet *net);
-// AZX_ERANGE when a split-f16 tower launch since the last check saw an activation beyond the f16 range (blocks on st)
+// AZX_ERANGE when a split-f16 or plain-f16 tower launch since the last check saw an activation beyond the f16 range (blocks on st)
 int azx_net_check_range(AzxNet *net, hipStream_t st);
 // packed buffer number `which` (name, bytes, contents); *nbytes = -1 past the last one
 int azx_net_debug_weights(AzxNet *net, int which, void *out, int64_t cap, int64_t *nbytes, char *name, int name_cap);

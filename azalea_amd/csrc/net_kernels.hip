@@ -582,6 +582,234 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
 }
 
 // ============================================================================================
+// k_tower_f16_s16: the OPT-IN single-product tower (AZX_FLAG_TOWER_F16 / AZX_TOWER=f16; NOT the reference's
+// arithmetic, outside every parity claim).  It computes k_tower_f16x3_s16's sums with every `lo` half taken as
+// zero: weights enter as f16(w) -- the `hi` fragments of the same packs Ws16 / Wh16 / Whd16 --, the activations
+// written back after each ReLU as f16(a), one v_mfma_f32_16x16x32_f16 per product, fp32 accumulation, fp32 bias
+// and residual (the unrounded block input, held in registers), exact one-hot stem input; an activation beyond the
+// f16 range raises sat_flag as there.  Same block shape (2 boards per 256-thread block, a wave owns 64 positions
+// x 64 channels), same LDS image and therefore the same conflict-free chunk order: the `lo` half of every
+// 272-byte row is simply neither written nor read.  A k-step is 16 MFMAs fed by 4 weight fragments (L2) and 4
+// activation fragments (LDS).  The registers the `lo` operands held go to a second weight set: all four channel
+// tiles of step t + 1 are requested during step t (one request in the shadow of each position tile's MFMAs), so
+// an L2 round trip has up to a whole k-step to pass instead of the half step of the x3 schedule, which at a third
+// of the MFMAs would be too short.  The activations stay single-buffered as there: tile m is refilled for step
+// t + 1 once its four MFMAs of step t have issued, the last tile at the head of the next step.
+// ============================================================================================
+__global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16_s16(NetDev P, const uint8_t *__restrict__ ev_board,
+                                                                      const int32_t *__restrict__ n_eval_ptr,
+                                                                      int n_eval_host, float *__restrict__ hfeat) {
+    constexpr int C = 64, ROWB = 272, MT = 4, NT = 4;     // as k_tower_f16x3_s16
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int n_eval = n_eval_ptr ? *n_eval_ptr : n_eval_host;
+    const int e0 = blockIdx.x * F16X3_BPB;
+    if (e0 >= n_eval) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wb = wave >> 1, wh = wave & 1;             // board within the block, which half of its positions
+    const int N = P.N, ncells = P.ncells;
+    const int e = e0 + wb;
+    const bool live = e < n_eval;
+    const int board_b = 128 * ROWB;
+    const int zero_off = 0;                              // two shared zero rows first (see k_tower_f16x3_s16)
+    const int x_off = 2 * ROWB + wb * board_b;
+    unsigned char *X = smem + x_off;
+    const int li = lane & 15, lh = lane >> 4;
+    const int lrow = li < 8 ? li ^ 4 : li;               // row of a tile column / chunk of a k-group: k_tower_f16x3_s16
+    const int lchunk = 128 * (lh & 1) + 16 * (lh >> 1);
+
+    unsigned long long tapok = 0ull;                     // bit tap*4 + m
+    int rbase[MT], ry_[MT], rx_[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int r = 64 * wh + 16 * m + lrow;
+        const int ry = r / N, rx = r - ry * N;
+        ry_[m] = ry;
+        rx_[m] = rx;
+        rbase[m] = x_off + r * ROWB + lchunk;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int yy = ry + tap / 3 - 1, xx = rx + tap % 3 - 1;
+            if (r < ncells && yy >= 0 && yy < N && xx >= 0 && xx < N) tapok |= 1ull << (tap * 4 + m);
+        }
+    }
+    uint32_t tapok_lo = (uint32_t)tapok, tapok_hi = (uint32_t)(tapok >> 32);
+    auto act_offset = [&](int tap, int m) -> int {       // a padding tap reads the zero rows
+        const int delta = ((tap / 3 - 1) * N + (tap % 3 - 1)) * ROWB;
+        const uint32_t word = tap < 8 ? tapok_lo : tapok_hi;
+        const int mask = (int)(word << (31 - ((tap * 4 + m) & 31))) >> 31;
+        return (mask | 0xF0) & (rbase[m] + delta);
+    };
+
+    f32x4 res[MT][NT];
+    auto load_bias = [&](const float *bias, float4 (&b4)[NT]) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) b4[n] = *reinterpret_cast<const float4 *>(bias + 16 * n + 4 * lh);
+    };
+    float satmax = 0.f;                                  // largest activation this lane has rounded to f16
+    auto epilogue = [&](f32x4 (&acc)[MT][NT], const float4 (&bias4)[NT], auto kind_tag) {
+        constexpr int kind = decltype(kind_tag)::value;  // 0 conv1, 1 conv2 (+ residual), 2 stem
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const float4 b4 = bias4[n];
+            const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                float v4[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float v = acc[m][n][j] + bv[j];
+                    if (kind == 1) v += res[m][n][j];
+                    v = fmaxf(v, 0.0f);
+                    if (kind != 0) res[m][n][j] = v;     // the residual stays fp32, unrounded
+                    v4[j] = v;
+                }
+                if (AZX_SAT_TRACK) satmax = fmaxf(fmaxf(satmax, v4[0]), fmaxf(v4[1], fmaxf(v4[2], v4[3])));
+                uint2 h4;                                // the same conversion as split2_f16's hi halves
+                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h4.x) : "v"(v4[0]), "v"(v4[1]));
+                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h4.y) : "v"(v4[2]), "v"(v4[3]));
+                unsigned char *pw = X + (64 * wh + 16 * m + lrow) * ROWB + 128 * (lh >> 1) + 16 * n + 8 * (lh & 1);
+                *reinterpret_cast<uint2 *>(pw) = h4;
+            }
+        }
+    };
+
+    // ---- stem: one 32-wide k-step with one-hot activations ------------------------------------------
+    {
+        const int NH = N + 2;
+        unsigned char *cells = X + 121 * ROWB;
+        const uint8_t *bd = ev_board + (size_t)(live ? e : n_eval - 1) * AZX_CELL_STRIDE;
+        if (wh == 0) {
+            for (int i = lane; i < NH * NH; i += 64) {
+                const int y = i / NH - 1, x = i - (y + 1) * NH - 1;
+                cells[i] = (y >= 0 && y < N && x >= 0 && x < N) ? bd[y * N + x] : (uint8_t)3;
+            }
+        }
+        for (int i = tid; i < 2 * ROWB / 4; i += F16X3_BPB * 128) reinterpret_cast<uint32_t *>(smem + zero_off)[i] = 0u;
+        __syncthreads();
+        f32x4 acc[MT][NT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const uint4 *ws = reinterpret_cast<const uint4 *>(P.Ws16);   // [ntile][hi,lo][lane]: the hi fragments
+        f16x8 wf[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const uint4 qh = ws[(n * 2) * 64 + lane];
+            wf[n] = *reinterpret_cast<const f16x8 *>(&qh);
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            uint32_t onehot = 0u;                        // bit k = 3*tap + colour of that neighbour
+            if (64 * wh + 16 * m + lrow < ncells) {
+                const unsigned char *c0 = cells + ry_[m] * NH + rx_[m];
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    const uint32_t v = c0[(tap / 3) * NH + tap % 3];
+                    onehot |= (v < 3u ? 1u : 0u) << (3 * tap + v);
+                }
+            }
+            const uint32_t byte = (onehot >> (8 * lh)) & 0xffu;      // k = 8 h + j
+            uint4 q;
+            q.x = ((byte >> 0) & 1u) * 0x3C00u | ((byte >> 1) & 1u) * 0x3C000000u;
+            q.y = ((byte >> 2) & 1u) * 0x3C00u | ((byte >> 3) & 1u) * 0x3C000000u;
+            q.z = ((byte >> 4) & 1u) * 0x3C00u | ((byte >> 5) & 1u) * 0x3C000000u;
+            q.w = ((byte >> 6) & 1u) * 0x3C00u | ((byte >> 7) & 1u) * 0x3C000000u;
+            const f16x8 xf = *reinterpret_cast<const f16x8 *>(&q);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[n], xf, acc[m][n], 0, 0, 0);
+        }
+        float4 sb4[NT];
+        load_bias(P.stem_b, sb4);
+        __syncthreads();   // every wave has read the staged cells: the tail rows are free again
+        epilogue(acc, sb4, std::integral_constant<int, 2>{});
+    }
+    __syncthreads();
+
+    const uint4 *wsrc = reinterpret_cast<const uint4 *>(P.Wh16);     // 512 uint4 per stage: [ntile 4][hi,lo][lane]
+    int stage = 0;
+    const int last_stage = P.layers * 18 - 1;
+    // two weight sets: k-step t multiplies out of set t & 1 while set (t + 1) & 1 is filled.  18 steps per layer,
+    // so every layer starts on set 0, which the last step of the layer before has requested.
+    f16x8 w_[2][NT];
+    auto load_w = [&](int st, int nn, int set) {
+        const uint4 qq = wsrc[(size_t)min(st, last_stage) * 512 + (nn * 2) * 64 + lane];
+        w_[set][nn] = *reinterpret_cast<const f16x8 *>(&qq);
+    };
+#pragma unroll
+    for (int n = 0; n < NT; ++n) load_w(0, n, 0);
+    auto conv_layer = [&](int layer, auto residual_tag) {
+        constexpr bool residual = decltype(residual_tag)::value;
+        asm volatile("" : "+v"(tapok_lo), "+v"(tapok_hi), "+v"(rbase[0]), "+v"(rbase[1]), "+v"(rbase[2]), "+v"(rbase[3]));
+        f32x4 acc[MT][NT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f16x8 x_[MT];
+        auto load_x = [&](int tt, int mm) {
+            x_[mm] = *reinterpret_cast<const f16x8 *>(smem + act_offset(tt >> 1, mm) + (tt & 1) * 32);
+        };
+#pragma unroll
+        for (int m = 0; m < MT - 1; ++m) load_x(0, m);
+        // k-step t = 0..17: tap t/2, channels 32 (t%2) .. +31: 16 MFMAs, position tile by position tile, 8 loads
+#pragma unroll
+        for (int t = 0; t < 18; ++t) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int m = q >> 2, n = q & 3;
+                if (n == 1) load_w(stage + t + 1, m, (t + 1) & 1);   // t = 17: the next layer's first k-step
+                if (q == 0) load_x(t, MT - 1);                       // the lagging last tile
+                else if (n == 0 && t + 1 < 18) load_x(t + 1, m - 1); // tile m - 1 is done for this step
+                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_[t & 1][n], x_[m], acc[m][n], 0, 0, 0);
+                if (n & 1) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        stage += 18;
+        float4 lb4[NT];
+        load_bias(P.bias + layer * C, lb4);
+        __syncthreads();   // both waves of the board finished reading it
+        epilogue(acc, lb4, std::integral_constant<int, residual ? 1 : 0>{});
+        __syncthreads();   // the partner wave wrote the other rows of this board
+    };
+    for (int blk = 0; blk < P.blocks; ++blk) {
+        conv_layer(2 * blk, std::false_type{});
+        conv_layer(2 * blk + 1, std::true_type{});
+    }
+
+    // the heads' six 1x1 filters as one more MFMA layer on the centre tap's fragments (see k_tower_f16x3_s16)
+    {
+        const uint4 *whd = reinterpret_cast<const uint4 *>(P.Whd16);
+        f16x8 ah[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const uint4 qh = whd[(ks * 2) * 64 + lane];
+            ah[ks] = *reinterpret_cast<const f16x8 *>(&qh);
+        }
+        const float4 hb = *reinterpret_cast<const float4 *>(P.hbias16 + 4 * lh);
+        const float hbv[4] = {hb.x, hb.y, hb.z, hb.w};
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            f32x4 hacc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const f16x8 xh = *reinterpret_cast<const f16x8 *>(smem + rbase[m] + ks * 32);
+                hacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], xh, hacc, 0, 0, 0);
+            }
+            const int row = 64 * wh + 16 * m + lrow;
+            if (live && row < ncells) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int o = 4 * lh + r;
+                    if (o < 6) hfeat[((size_t)e * 6 + o) * ncells + row] = fmaxf(hacc[r] + hbv[r], 0.0f);
+                }
+            }
+        }
+    }
+    if (satmax > 65504.0f) atomicOr(P.sat_flag, 1u);     // an activation left the f16 range (NetDev::sat_flag)
+}
+
+// ============================================================================================
 // wide residual tower (C a multiple of 128, N <= 13: BASELINE configs[4], 13x13 / 19x256): one
 // launch per conv layer, activations in HBM.  A board's activations (169 x 256 x (hi,lo) f16 =
 // 173 KB) do not fit the 160 KB LDS, so the in-LDS fusion of k_tower_f16x3_s16 is not available; at
@@ -1736,7 +1964,7 @@ __global__ __launch_bounds__(192 * HEADS_KSPLIT) void k_heads(NetDev P, const fl
 // ROCm 7.2 happens not to enforce, but the contract is the opt-in).
 static int raise_lds_limits() {
     const int cap = 160 * 1024;
-    const void *fns[] = {(const void *)k_tower_f16x3_s16, (const void *)k_conv_wide_f16x3_s16,
+    const void *fns[] = {(const void *)k_tower_f16x3_s16, (const void *)k_tower_f16_s16, (const void *)k_conv_wide_f16x3_s16,
                          (const void *)k_tower_mfma<64, 4, 2, 1, 2>, (const void *)k_tower_mfma<64, 6, 1, 2, 2>,
                          (const void *)k_tower_mfma<32, 6, 2, 2, 1>, (const void *)k_heads_mfma, (const void *)k_heads};
     for (const void *f : fns)
@@ -1745,7 +1973,9 @@ static int raise_lds_limits() {
     return AZX_OK;
 }
 
-int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, hipStream_t st) {
+bool azx_net_has_fused_tower(int N, int blocks, int chans) { return chans == 64 && N * N <= 121 && blocks >= 1; }
+
+int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, int tower_f16, hipStream_t st) {
     if (N < 2 || N > AZX_MAX_BOARD) return nfail(AZX_EINVAL, "net: board size out of range");
     if (blocks < 0 || chans < 1) return nfail(AZX_EINVAL, "net: bad num_blocks/base_chans");
     if (int rc = raise_lds_limits()) return rc;
@@ -1762,7 +1992,16 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, hi
     // pick the fused MFMA tower when its tiling covers (C, N)
     const char *force = getenv("AZX_TOWER");
     const bool want_fp32 = force && !strcmp(force, "fp32");
-    if (chans == 64 && ncells <= 121 && blocks >= 1 && !want_fp32) net->tower_variant = 4;   // k_tower_f16x3
+    const bool fused = azx_net_has_fused_tower(N, blocks, chans);
+    if (tower_f16 && (!fused || want_fp32)) {
+        delete net;
+        return nfail(AZX_EINVAL, want_fp32 ? "net: the plain-f16 tower was asked for (AZX_FLAG_TOWER_F16) but AZX_TOWER=fp32 forces the fp32 MFMA tower"
+                                           : "net: the plain-f16 tower (AZX_FLAG_TOWER_F16) exists for the fused tower's shapes only: "
+                                             "64 channels, at most 121 cells, at least one block");
+    }
+    // AZX_TOWER=f16: the plain-f16 tower wherever the fused tower would run, ignored elsewhere (a lenient knob, unlike the flag)
+    const bool want_f16 = tower_f16 || (force && !strcmp(force, "f16"));
+    if (fused && !want_fp32) { net->tower_variant = 4; net->tower_f16 = want_f16; }   // k_tower_f16x3_s16 | k_tower_f16_s16
     else if (chans == 64 && ncells <= 128) net->tower_variant = 1;   // <64,4,2,1,2>
     else if (chans == 64 && ncells <= 192) net->tower_variant = 2;   // <64,6,1,2,2>
     else if (chans == 32 && ncells <= 192) net->tower_variant = 3;   // <32,6,2,2,1>
@@ -1774,14 +2013,14 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, hi
     {
         char b[260];
         const char *tower = "k_stem_generic + k_conv_generic (VALU)";
-        if (net->tower_variant == 4) tower = "k_tower_f16x3_s16";
+        if (net->tower_variant == 4) tower = net->tower_f16 ? "k_tower_f16_s16" : "k_tower_f16x3_s16";
         else if (net->tower_variant == 5) tower = "k_stem_wide_f16x3 + k_conv_wide_f16x3_s16 per layer";
         else if (net->tower_variant == 1) tower = "k_tower_mfma<64,4,2,1,2> (fp32 MFMA)";
         else if (net->tower_variant == 2) tower = "k_tower_mfma<64,6,1,2,2> (fp32 MFMA)";
         else if (net->tower_variant == 3) tower = "k_tower_mfma<32,6,2,2,1> (fp32 MFMA)";
         const bool hm = net->tower_variant == 4 && net->opt_heads_mfma && ncells <= 128;
         snprintf(b, sizeof b, "%s + %s (%dx%d on %dx%d; AZX_TOWER=%s AZX_WIDE_STREAMS=%d AZX_HEADS=%s AZX_PACK=%s)",
-                 tower, hm ? "k_heads_mfma" : "k_heads", blocks, chans, N, N, want_fp32 ? "fp32" : "default",
+                 tower, hm ? "k_heads_mfma" : "k_heads", blocks, chans, N, N, want_fp32 ? "fp32" : net->tower_f16 ? "f16" : "default",
                  net->opt_wsplit, net->opt_heads_mfma ? "mfma" : "valu", net->pack_on_host ? "host" : "device");
         net->info = b;
     }
@@ -1934,7 +2173,8 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
         const size_t lds = net->lds_bytes;
         if (net->tower_variant == 4) {
             const dim3 grid((max_n + F16X3_BPB - 1) / F16X3_BPB), block(F16X3_BPB * 128);
-            hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, hfeat_rows);
+            if (net->tower_f16) hipLaunchKernelGGL(k_tower_f16_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, hfeat_rows);
+            else hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, hfeat_rows);
             hfeat = hfeat_rows;
         } else if (net->tower_variant == 5) {
             const dim3 grid(max_n, d.C / 128), block(256);
@@ -2025,8 +2265,8 @@ int azx_net_check_range(AzxNet *net, hipStream_t st) {
         return nfail(AZX_EHIP, "net: reading the activation range flag failed");
     if (!flag) return AZX_OK;
     (void)hipMemsetAsync(net->d.sat_flag, 0, sizeof flag, st);
-    return nfail(AZX_ERANGE, "net: an activation of the residual tower exceeded the f16 range (65504) of the split-f16 "
-                             "kernels -- the evaluations of this call are not valid (AZX_TOWER=fp32 runs the fp32 MFMA tower)");
+    return nfail(AZX_ERANGE, "net: an activation of the residual tower exceeded the f16 range (65504) of the f16 tower "
+                             "kernels (split-f16 and plain f16 alike) -- the evaluations of this call are not valid (AZX_TOWER=fp32 runs the fp32 MFMA tower)");
 }
 
 void azx_net_eval(AzxNet *net, const DevEngine &e, hipStream_t st) {

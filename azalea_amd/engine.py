@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EVAL_EXTERNAL, EVAL_RESNET, EVAL_UNIFORM, EVAL_UNIFORM_HASH,  # noqa: F401
-                   FLAG_NO_COMPACT, FLAG_RANDOM_REFLECT, AzxError, Config, MatchStats, PlayStats, check)
+                   FLAG_NO_COMPACT, FLAG_RANDOM_REFLECT, FLAG_TOWER_F16, AzxError, Config, MatchStats, PlayStats, check)
 
 
 def _p(a, ctype):

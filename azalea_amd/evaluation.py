@@ -218,7 +218,7 @@ def _throughput_policy(agent, external_batch=False):
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                         games=None, external_batch: bool = False, pooled: bool = False,
-                        collect=None) -> Dict[Pair, OutcomeCounts]:
+                        collect=None, info=None) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -239,12 +239,17 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     `collect`: optional dict that receives, per pair, the replay rows of that pair's games -- evaluation games that
     double as training data: dict(rows=..., row_metrics=...) as engine.Match.play(collect=True) returns them (row p of
     a game from the agent that moved at ply p; game_uid = the game's index, pair s owning [s * num_rounds,
-    (s + 1) * num_rounds); games in the order they settled).  The games and tallies are the same with or without."""
+    (s + 1) * num_rounds); games in the order they settled).  The games and tallies are the same with or without.
+    A policy attribute `tower_precision` ("f16": the plain-f16 tower, one MFMA per product; opt-in and OUTSIDE every
+    parity claim, policy.tower_flags) is honoured per agent, pooled or not: a match between the same weights at the
+    two precisions is two agents that differ in that attribute.  `info`: optional dict that receives, per agent
+    index, its engine's kernel_info() (which tower and heads kernels played)."""
     import torch
     from . import engine as _eng
-    from .policy import SearchTreeFull, external_evaluator
+    from .policy import SearchTreeFull, external_evaluator, tower_flags
 
     pols = [_throughput_policy(a, external_batch) for a in agents]
+    flags = [tower_flags(pol) for pol in pols]           # a ValueError before any engine is made
     num_rounds = int(num_rounds)
     if num_rounds < 1:
         raise ValueError("num_rounds must be >= 1")
@@ -284,8 +289,10 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                               base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
                               device=(dev.index or 0) if dev.type == "cuda" else 0,
                               nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),   # 0: the engine's default
-                              seed=((int(seed) << 8) + a) << 32)
+                              flags=flags[a], seed=((int(seed) << 8) + a) << 32)
             engines.append(eng)
+            if info is not None:
+                info[a] = eng.kernel_info()
             if hasattr(pol.net, "eval"):
                 pol.net.eval()
             if external:

@@ -31,7 +31,7 @@ from . import distributed as azdist
 from . import engine as _eng
 from .game.hex import HexGameState
 from .play_game import play_game
-from .policy import Policy, SearchTreeFull, external_evaluator
+from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags
 from .replay_buffer import ReplayDataFrame
 
 Metrics = Dict[str, float]
@@ -92,7 +92,12 @@ class Player:
         default): the engines this Player builds -- device self-play, external_batch, both engines of device_match
         -- hand the network about half of all evaluation requests turned by 180 degrees
         (engine.FLAG_RANDOM_REFLECT, include/azx.h).  A ValueError when the games would run through the host loop
-        instead."""
+        instead.
+        A policy attribute `tower_precision` (None / "f16x3" = the split-f16 tower as always, "f16"; opt-in and
+        OUTSIDE every parity claim, policy.tower_flags) is honoured per agent by the device engines of the one-agent
+        throughput mode and of device_match (engine.FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product).  A
+        ValueError -- here, before any engine is made -- when "f16" is asked for but the games would run through
+        the host loop or an external evaluator, or the network's shape has no fused tower."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.agents = agents
@@ -110,6 +115,7 @@ class Player:
                              "holds a HexNetwork, external_batch=True or device_match=True): these agents play "
                              "through the host loop, which does not reflect")
         self._engine_flags = _eng.FLAG_RANDOM_REFLECT if self.random_reflect else 0
+        self._check_tower_precision()
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -234,6 +240,16 @@ class Player:
         pol = getattr(self.agents[0], "policy", None)
         return pol if isinstance(pol, Policy) and pol._uses_device_net() and len(self.agents) == 1 else None
 
+    def _check_tower_precision(self) -> None:
+        """Every agent's `tower_precision` is one this Player's engines can honour (policy.tower_flags, which refuses
+        policies without a HexNetwork itself); no GPU needed."""
+        on_device = self.device_match or self._device_policy() is not None
+        for i, agent in enumerate(self.agents):
+            pol = getattr(agent, "policy", None)
+            if pol is not None and tower_flags(pol) and not on_device:
+                raise ValueError("agent %d asks for tower_precision='f16', but these games run through the host loop, "
+                                 "which does not launch the device tower" % i)
+
     def _external_policy(self) -> Policy:
         """The Policy whose duck-typed net evaluates the pool's leaf batches (external_batch=True); a ValueError
         naming what does not hold otherwise -- there is no silent fall-back to the host loop."""
@@ -345,7 +361,7 @@ class Player:
         key = (n, device, pol.simulations, pol.search_batch_size, float(pol.exploration_coef),
                pol.exploration_depth, pol.exploration_noise_alpha, pol.exploration_noise_scale,
                pol.exploration_temperature, pol.num_blocks, pol.base_chans,
-               bool(pol.settings.get("move_sampling")), bool(pol.settings.get("move_exploration")), external)
+               bool(pol.settings.get("move_sampling")), bool(pol.settings.get("move_exploration")), external, tower_flags(pol))
         if self._engine is None or key != self._engine_key:
             if self._engine is not None:
                 self._engine.close()
@@ -362,7 +378,7 @@ class Player:
                 temperature=pol.exploration_temperature if sampling else 0.0,
                 evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
                 num_blocks=pol.num_blocks, base_chans=pol.base_chans,
-                flags=self._engine_flags,
+                flags=self._engine_flags | tower_flags(pol),
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
             self._engine_key = key
         return self._engine
@@ -416,7 +432,7 @@ class Player:
                            num_blocks=getattr(pol, "num_blocks", 0) if external else pol.num_blocks,
                            base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
                            device=dev.index or 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
-                           flags=self._engine_flags,
+                           flags=self._engine_flags | tower_flags(pol),
                            seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
 
     def _produce_match(self, pols) -> None:

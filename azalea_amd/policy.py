@@ -71,6 +71,32 @@ def external_evaluator(net, pad_rows=True):
     return evaluate
 
 
+TOWER_PRECISIONS = (None, "f16x3", "f16")
+
+
+def tower_flags(pol) -> int:
+    """The engine flag a policy's optional attribute `tower_precision` asks for in throughput mode (Player,
+    evaluate_throughput): None / "f16x3" -- the split-f16 tower, as always -- give 0, "f16" gives
+    engine.FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product.  That is an opt-in OUTSIDE every parity claim
+    (not the reference's arithmetic; include/azx.h has the definition, DESIGN 7.8 the measured errors).  A
+    ValueError for an unknown string, and for "f16" on a policy whose network is not a HexNetwork the fused tower
+    covers (64 channels, at most 121 cells, at least one block).  Runs without a GPU and before any engine is made.
+    Policy's own parity-mode engine never reads the attribute: parity mode stays parity."""
+    prec = getattr(pol, "tower_precision", None)
+    if prec not in TOWER_PRECISIONS:
+        raise ValueError("tower_precision must be one of %r, got %r" % (TOWER_PRECISIONS, prec))
+    if prec != "f16":
+        return 0
+    if not (isinstance(pol, Policy) and pol._uses_device_net()):
+        raise ValueError("tower_precision='f16' selects a kernel of the built-in HexNetwork tower: this policy's "
+                         "network runs through an external evaluator")
+    n, blocks, chans = int(pol.board_size), int(pol.num_blocks), int(pol.base_chans)
+    if not (chans == 64 and n * n <= 121 and blocks >= 1):
+        raise ValueError("tower_precision='f16' needs a shape the fused tower covers (64 channels, at most 121 cells, "
+                         "at least one block): got %d blocks x %d channels on %dx%d" % (blocks, chans, n, n))
+    return _eng.FLAG_TOWER_F16
+
+
 _SEARCH_KEYS = ("simulations", "search_batch_size", "exploration_coef", "exploration_depth",
                 "exploration_noise_alpha", "exploration_noise_scale", "exploration_temperature")
 _NET_KEYS = ("network_type", "board_size", "num_blocks", "base_chans")

@@ -260,6 +260,22 @@ def save_checkpoint(policy, name, *, optimizer=None, replaybuf=None) -> str:
     return path
 
 
+def apply_selfplay_tower(policy, config) -> None:
+    """config["selfplay_tower"] (absent / None / "f16x3": the split-f16 tower, as always; "f16": the plain-f16 tower)
+    becomes the training policy's `tower_precision`, which its self-play Player honours (policy.tower_flags: a
+    ValueError for an unknown string or a network without a fused tower).  Absent, the policy is left as it is."""
+    if "selfplay_tower" not in config:
+        return
+    from .policy import tower_flags
+    before = getattr(policy, "tower_precision", None)
+    policy.tower_precision = config["selfplay_tower"]
+    try:
+        tower_flags(policy)
+    except ValueError:
+        policy.tower_precision = before
+        raise
+
+
 def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False, history=None) -> str:
     """The reference training loop (policy_trainer.py:23-119) over this package's Player.
     `history`: optional dict; receives the learning rate each epoch trained with under "lr", the name of the training
@@ -291,7 +307,14 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     (Player(random_reflect=True)), and so do the training batches: the collate kernel with device_replay
     (DeviceReplayBuffer.random_reflect, seeded from config["seed"]), prep.rot180_batch on each host batch otherwise
     (mask from a torch.Generator seeded from config["seed"]; after to_mover_view when both are on).  Neither its cost
-    nor its effect on strength has been measured."""
+    nor its effect on strength has been measured.
+
+    config["selfplay_tower"] (default absent = the split-f16 tower; "f16": opt-in, NOT the reference's arithmetic and
+    outside every parity claim): the self-play engine of the training policy runs the plain-f16 tower, one MFMA per
+    product instead of three (engine.FLAG_TOWER_F16; include/azx.h has the definition, DESIGN 7.8 the measured
+    errors).  It sets the policy's `tower_precision` for its self-play side only (apply_selfplay_tower); the training
+    step, the checkpoints and Policy's own parity-mode engine are untouched."""
+    apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])
     torch.manual_seed(config["seed"])

@@ -58,7 +58,7 @@ enum {
 enum {
     AZX_FLAG_NO_COMPACT = 1, /* keep the reference's never-free arena + moving root_id
                                 (search_tree.py:115-132) instead of compacting on advance */
-    AZX_FLAG_RANDOM_REFLECT = 2  /* NOT the reference's behaviour for Hex (off by default, outside every parity claim).
+    AZX_FLAG_RANDOM_REFLECT = 2, /* NOT the reference's behaviour for Hex (off by default, outside every parity claim).
                                 The reference calls game.random_reflect on every leaf batch before the network sees it
                                 (mcts.py:183-186); its Hex implementation returns its inputs and names the one transform
                                 that keeps the player's direction, np.rot90(b, 2) (game/hex.py:124-134).  With this flag
@@ -78,6 +78,24 @@ enum {
                                 no network input, is AZX_EINVAL.  Matches and tournaments take the flag per engine.
                                 azx_kernel_info reports reflect=on|off.  An addition WITHIN ABI revision 7: azx_config
                                 is unchanged. */
+    AZX_FLAG_TOWER_F16 = 4   /* NOT the reference's arithmetic (off by default, outside every parity claim).  The 6x64-class
+                                fused tower normally carries every fp32 operand as hi + lo f16 halves and issues three
+                                MFMAs per product (fp32-class accuracy, the 1e-4 parity tolerance).  With this flag the
+                                engine's network runs k_tower_f16_s16 instead: that arithmetic with every lo half taken as
+                                zero.  The folded weights (stem with the embedding folded in, the conv layers, the six 1x1
+                                head filters) enter as f16(w); the activations written back after each ReLU enter the next
+                                conv and the head filters as f16(a); products accumulate in fp32; the folded-BN bias and
+                                the residual (the unrounded block input) stay fp32; the one-hot stem input is exact;
+                                everything behind the six head planes (FC layers, log-softmax, -99 padding) is unchanged
+                                fp32.  An activation beyond 65504 is +inf in f16 and raises AZX_ERANGE as without the flag;
+                                the weight range guard of azx_set_weights is the same.  Expect value errors of order 1e-4
+                                to 1e-3 and log-prob errors up to a few 1e-2 on peaked trained networks.
+                                AZX_EVAL_RESNET on a shape the fused tower covers (64 channels, at most 121 cells, at
+                                least one block) only, and not together with AZX_TOWER=fp32: azx_create is AZX_EINVAL
+                                otherwise.  Matches and tournaments take the flag per engine.  The environment variable
+                                AZX_TOWER=f16 selects the same kernel wherever the fused tower would run and is ignored
+                                elsewhere.  azx_kernel_info names the tower.  An addition WITHIN ABI revision 7:
+                                azx_config is unchanged. */
 };
 
 typedef struct {
@@ -111,7 +129,7 @@ const char *azx_last_error(void);
 int azx_version(void);            /* ABI revision: 7 = azx_set_external_evaluator, AZX_EEXTERNAL (throughput self-play and
                                    *     azx_search with a caller-supplied evaluator over device buffers); the azx_match_*
                                    *     entry points were added within revision 7 -- callers detect them by symbol; so
-                                   *     were AZX_FLAG_RANDOM_REFLECT (azx_config unchanged) and azx_replay_set_reflect;
+                                   *     were AZX_FLAG_RANDOM_REFLECT and AZX_FLAG_TOWER_F16 (azx_config unchanged) and azx_replay_set_reflect;
                                    * 6 = azx_reserve_cus, azx_replay_put_records_async (self-play beside training);
                                    * 5 = AZX_ERANGE, azx_debug_weights, weights packed on the device
                                    * (4 = 8-float row metrics, azx_kernel_info, azx_debug_set_queue_cap;

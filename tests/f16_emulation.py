@@ -1,0 +1,48 @@
+"""Float64 torch emulation of the plain-f16 tower (AZX_FLAG_TOWER_F16, k_tower_f16_s16): the yardstick of
+tests/test_gpu_tower_f16.py, pinned by tests/test_tower_f16_emulation.py.  A plain module, no test in it.
+
+The definition (include/azx.h): BatchNorm folded into the convolutions and the 3 -> 4 embedding folded into the stem
+as the weight packer does it (scale = w / sqrt(var + 1e-5), shift = b - mean * scale in f64, the products stored as
+fp32); the folded stem, conv and head-filter weights enter as f16(w); the activation written back after each ReLU
+enters the next conv and the head filters as f16(a); sums, bias and the residual (the unrounded block input) are not
+rounded -- float64 here, fp32 in the kernel; the one-hot stem input is exact; the heads behind the six planes are
+unchanged.  rounded=False leaves every f16 rounding out: the network itself."""
+import torch
+from torch.nn import functional as F
+
+
+def _fold(state, pre):
+    w, b, m, v = (torch.as_tensor(state[pre + k]).double() for k in (".weight", ".bias", ".running_mean", ".running_var"))
+    scale = w / torch.sqrt(v + 1e-5)
+    return scale, (b - m * scale).float().double()
+
+
+def forward(state, blocks, board, legal_moves, rounded=True):
+    """(value [B], moves_logprob [B, K]) as float64 numpy arrays; `state`: the HexNetwork state dict (numpy or torch)."""
+    r16 = (lambda t: t.float().half().double()) if rounded else (lambda t: t)
+    g = lambda name: torch.as_tensor(state[name]).double()   # noqa: E731
+    board, legal_moves = torch.as_tensor(board).long(), torch.as_tensor(legal_moves).long()
+
+    def folded(conv, bn):
+        scale, shift = _fold(state, bn)
+        return r16((g(conv) * scale[:, None, None, None]).float().double()), shift[None, :, None, None]
+
+    # stem: T[co][v] per tap = scale[co] * sum_i emb[v][i] * w[co][i][tap]; zero padding = no contribution off the board
+    scale, shift = _fold(state, "bn1")
+    table = torch.einsum("vi,oiyx->ovyx", g("encoder.weight"), g("conv1.weight")) * scale[:, None, None, None]
+    onehot = F.one_hot(board, 3).permute(0, 3, 1, 2).double()
+    x = F.relu(F.conv2d(onehot, r16(table.float().double()), padding=1) + shift[None, :, None, None])
+    for b in range(blocks):
+        w1, b1 = folded("resblocks.%d.conv1.weight" % b, "resblocks.%d.bn1" % b)
+        w2, b2 = folded("resblocks.%d.conv2.weight" % b, "resblocks.%d.bn2" % b)
+        y = F.relu(F.conv2d(r16(x), w1, padding=1) + b1)
+        x = F.relu(F.conv2d(r16(y), w2, padding=1) + b2 + x)        # the residual is the unrounded block input
+    wv, bv = folded("value_conv1.weight", "value_bn1")
+    wp, bp = folded("move_conv1.weight", "move_bn1")
+    xr = r16(x)
+    v = F.relu(F.conv2d(xr, wv) + bv).flatten(1)
+    v = F.linear(F.relu(F.linear(v, g("value_fc2.weight"), g("value_fc2.bias"))), g("value_fc3.weight"), g("value_fc3.bias"))
+    p = F.relu(F.conv2d(xr, wp) + bp).flatten(1)
+    logit = F.linear(p, g("move_fc.weight"), g("move_fc.bias"))
+    logit = torch.gather(logit, 1, (legal_moves - 1).clamp(min=0)).masked_fill(legal_moves == 0, -99)
+    return torch.tanh(v).squeeze(1).numpy(), F.log_softmax(logit, dim=1).numpy()
