@@ -31,6 +31,7 @@
 #include <map>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -862,7 +863,23 @@ struct WideBwdFuse { const unsigned char *mask; const float *raw, *skip; const d
 // block = board x 64 channels).  A training batch of 128 boards is 256 of the former -- one workgroup per CU, one wave per
 // SIMD, nobody to run while a block stages its next chunk -- and 512 of the latter: two independent workgroups per CU, the
 // regime the kernel was tuned in, at the price of twice the activation-fragment reads per MFMA (well inside the LDS rate).
-template <int TRAIN, int NTW = WIDE16_NT>
+// PLAIN = 1 (inference only; k_conv_wide_f16_s16, the OPT-IN single-product wide tower: AZX_FLAG_TOWER_F16 / AZX_TOWER=f16,
+// NOT the reference's arithmetic, outside every parity claim): the same sums with every `lo` operand taken as zero.  Only
+// the `hi` plane of the input is staged, so the 272-byte LDS row holds 128 channels (the second 64 where the `lo` half
+// was: the same piece order, the same conflict-free ds_read_b128 addresses) and a chunk is 128 channels: C / 128 chunks
+// of 36 k-steps (tap t / 4, channels 32 (t % 4) .. +31 of the chunk), half the barriers and half the staged bytes.  A
+// k-step is 22 MFMAs fed by 4 weight fragments (part 0 of the same pack) and 6 activation fragments.  The registers of
+// the `lo` operands hold a second weight set: all of k-step t + 1's weights -- the next chunk's first step included, across
+// its staging -- are requested during step t, as in k_tower_f16_s16.  Prologue (bias + the residual as hi + lo) and
+// epilogue (the split pair, the fp32 copy of the last layer) are the x3 kernel's: the residual stream is not rounded.
+// (f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the 36 x 22 MFMAs of a PLAIN chunk are past what
+// `#pragma unroll` unrolls in full, and a k-step left in a loop indexes its register sets at run time)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
+
+template <int TRAIN, int NTW = WIDE16_NT, int PLAIN = 0>
 __device__ __forceinline__ void conv_wide_s16_body(const NetDev &P, int layer, const unsigned short *__restrict__ in,
                                                    unsigned short *out, const unsigned short *resid,
                                                    float *__restrict__ out32,
@@ -871,6 +888,7 @@ __device__ __forceinline__ void conv_wide_s16_body(const NetDev &P, int layer, c
                                                    const WideBwdFuse &F = WideBwdFuse{}) {
     constexpr int MT = WIDE16_MT, NT = NTW, ROWB = WIDE_ROWB;
     static_assert(NT == 4 || (NT == 2 && TRAIN != 0), "two tiles per wave: training instantiations only");
+    static_assert(!PLAIN || (TRAIN == 0 && NT == 4), "the single-product k-loop: inference only");
     float satmax = 0.f;
     extern __shared__ __align__(16) unsigned char smem[];
     const int n_eval = n_eval_ptr ? *n_eval_ptr : n_eval_host;
@@ -1005,10 +1023,24 @@ __device__ __forceinline__ void conv_wide_s16_body(const NetDev &P, int layer, c
     // 82.0 vs 82.2 backward: the staging round trips are not what the kernel waits for.  profiles/r6_train_wide_ab.txt)
     auto main_loop = [&](auto wm_tag) __attribute__((always_inline)) {
     constexpr int WM = decltype(wm_tag)::value;
+    // PLAIN: a staged chunk is 128 channels, i.e. two of the pack's 64-channel chunks, and the weights sit in two
+    // register sets (k-step t multiplies out of set t & 1; 36 steps per chunk, so every chunk starts on set 0)
+    constexpr int CHB = PLAIN ? 256 : 128;               // bytes of a chunk in a plane of the HBM row
+    const int NCHL = PLAIN ? C / 128 : NCH;
+    f16x8 wp_[2][NT];
+    auto load_wp = [&](int chunk, int t, int nn) {
+        const int q = ((layer * 9 + (t >> 2)) * NCH + 2 * chunk + ((t >> 1) & 1)) * 2 + (t & 1);
+        const uint4 qq = *wptr(q, nn, 0);
+        wp_[t & 1][nn] = *reinterpret_cast<const f16x8 *>(&qq);
+    };
+    if constexpr (PLAIN) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) load_wp(0, 0, n);
+    }
     // (Measured and dropped, round 6: three weight register sets, k-step g's fragments requested during k-step g - 2 and
     // across chunk boundaries -- a two-tile k-step is 576 matrix-pipe cycles, about an L2 round trip: 67.5 vs 60.9 us
     // forward, 85.9 vs 80.0 backward; the weights are not late, the 50 extra registers cost.  profiles/r6_train_wide_ab.txt)
-    for (int chunk = 0; chunk < NCH; ++chunk) {
+    for (int chunk = 0; chunk < NCHL; ++chunk) {
 #if AZX_WIDE_ABLATE & 1
         if (chunk == 0)
 #endif
@@ -1034,7 +1066,8 @@ __device__ __forceinline__ void conv_wide_s16_body(const NetDev &P, int layer, c
                     // piece d of the LDS row (destination order, contiguous stores): k-group 2 (d & 1) + (d >> 3),
                     // part (d >> 2) & 1, k-half (d >> 1) & 1 -- a row's 16 lanes still read its two 128-byte lines whole
                     const int row = idx >> 4, d = idx & 15;
-                    const size_t src = (size_t)row * rowg + (size_t)chunk * 128 + ((d >> 2) & 1) * (size_t)C * 2 +
+                    // (PLAIN: bit 2 of d is the 64-channel half of the chunk's hi plane instead of the part)
+                    const size_t src = (size_t)row * rowg + (size_t)chunk * CHB + ((d >> 2) & 1) * (PLAIN ? (size_t)128 : (size_t)C * 2) +
                                        ((d >> 1) & 1) * 64 + (2 * (d & 1) + (d >> 3)) * 16;
                     if (j0 + j < NST) stg[j] = *reinterpret_cast<const uint4 *>(gin + src);
                 }
@@ -1072,7 +1105,35 @@ __device__ __forceinline__ void conv_wide_s16_body(const NetDev &P, int layer, c
             if (part) xl[mm] = *reinterpret_cast<const f16x8 *>(pa);
             else xh[mm] = *reinterpret_cast<const f16x8 *>(pa);
         };
-        if constexpr (NT == 2) {
+        if constexpr (PLAIN) {
+            // k-step t = 0..35 of this chunk: 22 MFMAs, position tile by position tile.  The first two position tiles
+            // request the four channel tiles' weights of step t + 1, one behind every second MFMA (t = 35: the next
+            // chunk's first step; after the last chunk a repeat of its own, never used).  Tile m's activation fragment
+            // is refilled for step t + 1 once its MFMAs of step t have issued; the last tile lags into the head of the
+            // next step (one register set, as in k_tower_f16_s16)
+            f16x8 x_[MT];
+            auto load_xp = [&](int tt, int mm) {
+                x_[mm] = *reinterpret_cast<const f16x8 *>(smem + act_offset(tt >> 2, mm) + (tt & 3) * 32);
+            };
+#pragma unroll
+            for (int m = 0; m < MT - 1; ++m) load_xp(0, m);
+            static_for<36>([&](auto t_tag) __attribute__((always_inline)) {
+                constexpr int t = decltype(t_tag)::value;
+#pragma unroll
+                for (int q = 0; q < 4 * MT; ++q) {
+                    const int m = q >> 2, n = q & 3;
+                    if ((q & 1) && q < 2 * NT) {
+                        if (t + 1 < 36) load_wp(chunk, t + 1, q >> 1);
+                        else load_wp(min(chunk + 1, NCHL - 1), 0, q >> 1);
+                    }
+                    if (q == 0) load_xp(t, MT - 1);
+                    else if (n == 0 && t + 1 < 36) load_xp(t + 1, m - 1);
+                    if (!(WM == 0 ? (m == MT - 1 && n >= 2) : (m == 0 && n < 2)))
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp_[t & 1][n], x_[m], acc[m][n], 0, 0, 0);
+                    if (n & 1) __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+        } else if constexpr (NT == 2) {
             // two tiles per wave: a k-step is ONE pass of 36 MFMAs (6 position tiles x 2 channel tiles x 3); the weights
             // of k-step t + 1 go into the other of two register sets in the first MFMAs' shadows, a position tile's
             // activation fragments are reloaded for t + 1 one tile after its MFMAs have issued, the last tile lags
@@ -1342,6 +1403,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_wide_f16x3_s16(NetDev P, int la
     conv_wide_s16_body<0>(P, layer, in, out, resid, out32, n_eval_ptr, n_eval_host, e_base, e_end, 1.f, nullptr);
 }
 
+// the opt-in single-product form (PLAIN = 1 above): same arguments, same grid, same LDS image size
+__global__ __launch_bounds__(256, 2) void k_conv_wide_f16_s16(NetDev P, int layer, const unsigned short *__restrict__ in,
+                                                              unsigned short *out, const unsigned short *resid,
+                                                              float *__restrict__ out32,
+                                                              const int32_t *__restrict__ n_eval_ptr, int n_eval_host,
+                                                              int e_base, int e_end) {
+    conv_wide_s16_body<0, WIDE16_NT, 1>(P, layer, in, out, resid, out32, n_eval_ptr, n_eval_host, e_base, e_end, 1.f, nullptr);
+}
+
 // the training step's convolutions (TRAIN = 1 above): `w16` = one layer's fragments in the wide pack
 // ([tap][chunk][half][ntile][hi, lo][lane][8]: k_tw_pack), boards [0, n_boards)
 template <int NTW>
@@ -1388,9 +1458,11 @@ int azx_net_wide_train_conv(int N, int C, const unsigned short *w16, const unsig
 
 // stem of the wide tower: the one-hot K = 27 product of k_tower_f16x3_s16's stem, one board x 128
 // output channels per block, straight to the HBM activation layout
-__global__ __launch_bounds__(256, 2) void k_stem_wide_f16x3(NetDev P, const uint8_t *__restrict__ ev_board,
-                                                            unsigned short *out, float *__restrict__ out32,
-                                                            const int32_t *__restrict__ n_eval_ptr, int n_eval_host) {
+// (PLAIN: k_stem_wide_f16, the single-product tower's stem -- the folded stem weights as f16(w), one MFMA per fragment)
+template <int PLAIN>
+__device__ __forceinline__ void stem_wide_body(const NetDev &P, const uint8_t *__restrict__ ev_board,
+                                               unsigned short *out, float *__restrict__ out32,
+                                               const int32_t *__restrict__ n_eval_ptr, int n_eval_host) {
     constexpr int MW = WIDE_MW, NW = WIDE_NW;
     float satmax = 0.f;
     __shared__ unsigned char cells[(AZX_MAX_BOARD + 2) * (AZX_MAX_BOARD + 2) + 15];
@@ -1450,13 +1522,13 @@ __global__ __launch_bounds__(256, 2) void k_stem_wide_f16x3(NetDev P, const uint
 #pragma unroll
         for (int n = 0; n < NW; ++n) {
             const uint4 *pa = ws + ((size_t)(kk * NT + nt0 + n) * 2) * 64 + lane;
-            const uint4 qh = pa[0], ql = pa[64];
+            const uint4 qh = pa[0], ql = PLAIN ? uint4{0u, 0u, 0u, 0u} : pa[64];
             const f16x8 wh8 = *reinterpret_cast<const f16x8 *>(&qh);
             const f16x8 wl8 = *reinterpret_cast<const f16x8 *>(&ql);
 #pragma unroll
             for (int m = 0; m < MW; ++m) {
                 acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh8, bfr[m], acc[m][n], 0, 0, 0);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl8, bfr[m], acc[m][n], 0, 0, 0);
+                if (!PLAIN) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl8, bfr[m], acc[m][n], 0, 0, 0);
             }
         }
     }
@@ -1495,6 +1567,18 @@ __global__ __launch_bounds__(256, 2) void k_stem_wide_f16x3(NetDev P, const uint
         }
     }
     if (satmax > 65504.0f) atomicOr(P.sat_flag, 1u);     // an activation left the f16 range: its hi half is +inf (NetDev::sat_flag)
+}
+
+__global__ __launch_bounds__(256, 2) void k_stem_wide_f16x3(NetDev P, const uint8_t *__restrict__ ev_board,
+                                                            unsigned short *out, float *__restrict__ out32,
+                                                            const int32_t *__restrict__ n_eval_ptr, int n_eval_host) {
+    stem_wide_body<0>(P, ev_board, out, out32, n_eval_ptr, n_eval_host);
+}
+
+__global__ __launch_bounds__(256, 2) void k_stem_wide_f16(NetDev P, const uint8_t *__restrict__ ev_board,
+                                                          unsigned short *out, float *__restrict__ out32,
+                                                          const int32_t *__restrict__ n_eval_ptr, int n_eval_host) {
+    stem_wide_body<1>(P, ev_board, out, out32, n_eval_ptr, n_eval_host);
 }
 
 // ============================================================================================
@@ -1965,6 +2049,7 @@ __global__ __launch_bounds__(192 * HEADS_KSPLIT) void k_heads(NetDev P, const fl
 static int raise_lds_limits() {
     const int cap = 160 * 1024;
     const void *fns[] = {(const void *)k_tower_f16x3_s16, (const void *)k_tower_f16_s16, (const void *)k_conv_wide_f16x3_s16,
+                         (const void *)k_conv_wide_f16_s16,
                          (const void *)k_tower_mfma<64, 4, 2, 1, 2>, (const void *)k_tower_mfma<64, 6, 1, 2, 2>,
                          (const void *)k_tower_mfma<32, 6, 2, 2, 1>, (const void *)k_heads_mfma, (const void *)k_heads};
     for (const void *f : fns)
@@ -1974,6 +2059,10 @@ static int raise_lds_limits() {
 }
 
 bool azx_net_has_fused_tower(int N, int blocks, int chans) { return chans == 64 && N * N <= 121 && blocks >= 1; }
+static bool has_wide_tower(int N, int chans) { return chans % 128 == 0 && N * N <= 192; }     // tower variant 5
+bool azx_net_has_f16_tower(int N, int blocks, int chans) {
+    return azx_net_has_fused_tower(N, blocks, chans) || (has_wide_tower(N, chans) && blocks >= 1);
+}
 
 int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, int tower_f16, hipStream_t st) {
     if (N < 2 || N > AZX_MAX_BOARD) return nfail(AZX_EINVAL, "net: board size out of range");
@@ -1993,19 +2082,24 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     const char *force = getenv("AZX_TOWER");
     const bool want_fp32 = force && !strcmp(force, "fp32");
     const bool fused = azx_net_has_fused_tower(N, blocks, chans);
-    if (tower_f16 && (!fused || want_fp32)) {
+    const bool has_f16 = azx_net_has_f16_tower(N, blocks, chans);
+    if (tower_f16 && (!has_f16 || want_fp32)) {
         delete net;
-        return nfail(AZX_EINVAL, want_fp32 ? "net: the plain-f16 tower was asked for (AZX_FLAG_TOWER_F16) but AZX_TOWER=fp32 forces the fp32 MFMA tower"
-                                           : "net: the plain-f16 tower (AZX_FLAG_TOWER_F16) exists for the fused tower's shapes only: "
-                                             "64 channels, at most 121 cells, at least one block");
+        return nfail(AZX_EINVAL, want_fp32 ? "net: the plain-f16 tower was asked for (AZX_FLAG_TOWER_F16) but AZX_TOWER=fp32 forces the fp32 tower"
+                                           : "net: the plain-f16 tower (AZX_FLAG_TOWER_F16) exists for the fused tower's shapes (64 channels, at most "
+                                             "121 cells) and the wide tower's (a multiple of 128 channels) only, with at least one block");
     }
-    // AZX_TOWER=f16: the plain-f16 tower wherever the fused tower would run, ignored elsewhere (a lenient knob, unlike the flag)
+    // AZX_TOWER=f16: the plain-f16 tower wherever the fused or the wide tower would run with at least one block, ignored
+    // elsewhere (a lenient knob, unlike the flag)
     const bool want_f16 = tower_f16 || (force && !strcmp(force, "f16"));
     if (fused && !want_fp32) { net->tower_variant = 4; net->tower_f16 = want_f16; }   // k_tower_f16x3_s16 | k_tower_f16_s16
     else if (chans == 64 && ncells <= 128) net->tower_variant = 1;   // <64,4,2,1,2>
     else if (chans == 64 && ncells <= 192) net->tower_variant = 2;   // <64,6,1,2,2>
     else if (chans == 32 && ncells <= 192) net->tower_variant = 3;   // <32,6,2,2,1>
-    else if (chans % 128 == 0 && ncells <= 192 && !want_fp32) net->tower_variant = 5;   // k_conv_wide_f16x3 per layer
+    else if (has_wide_tower(N, chans) && !want_fp32) {     // k_conv_wide_f16x3_s16 | k_conv_wide_f16_s16 per layer
+        net->tower_variant = 5;
+        net->tower_f16 = want_f16 && blocks >= 1;
+    }
     net->use_mfma = net->tower_variant != 0;
     { const char *v = getenv("AZX_WIDE_STREAMS"); net->opt_wsplit = std::min(4, std::max(1, v ? atoi(v) : 2)); }
     { const char *v = getenv("AZX_HEADS"); net->opt_heads_mfma = !(v && !strcmp(v, "valu")); }
@@ -2014,7 +2108,8 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
         char b[260];
         const char *tower = "k_stem_generic + k_conv_generic (VALU)";
         if (net->tower_variant == 4) tower = net->tower_f16 ? "k_tower_f16_s16" : "k_tower_f16x3_s16";
-        else if (net->tower_variant == 5) tower = "k_stem_wide_f16x3 + k_conv_wide_f16x3_s16 per layer";
+        else if (net->tower_variant == 5) tower = net->tower_f16 ? "k_stem_wide_f16 + k_conv_wide_f16_s16 per layer"
+                                                                 : "k_stem_wide_f16x3 + k_conv_wide_f16x3_s16 per layer";
         else if (net->tower_variant == 1) tower = "k_tower_mfma<64,4,2,1,2> (fp32 MFMA)";
         else if (net->tower_variant == 2) tower = "k_tower_mfma<64,6,1,2,2> (fp32 MFMA)";
         else if (net->tower_variant == 3) tower = "k_tower_mfma<32,6,2,2,1> (fp32 MFMA)";
@@ -2178,7 +2273,9 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
             hfeat = hfeat_rows;
         } else if (net->tower_variant == 5) {
             const dim3 grid(max_n, d.C / 128), block(256);
-            hipLaunchKernelGGL(k_stem_wide_f16x3, grid, block, 0, st, d, boards, net->wideX,
+            const auto k_stem = net->tower_f16 ? k_stem_wide_f16 : k_stem_wide_f16x3;
+            const auto k_conv = net->tower_f16 ? k_conv_wide_f16_s16 : k_conv_wide_f16x3_s16;
+            hipLaunchKernelGGL(k_stem, grid, block, 0, st, d, boards, net->wideX,
                                d.blocks == 0 ? net->act : (float *)nullptr, n_eval_ptr, n_host);
             // A layer is one launch over all boards, and a launch ends with a partly filled round of blocks
             // (9 964 blocks over 512 slots: 19.46 rounds, 2.7 % of a layer idle) -- 38 times per batch.  The
@@ -2211,9 +2308,9 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
                     if (e1 <= e0) continue;
                     const dim3 g(8 * (d.C / 128), (e1 - e0 + 7) / 8);
                     for (int b = 0; b < d.blocks; ++b) {
-                        hipLaunchKernelGGL(k_conv_wide_f16x3_s16, g, block, lds, s, d, 2 * b, (const unsigned short *)net->wideX, net->wideY,
+                        hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b, (const unsigned short *)net->wideX, net->wideY,
                                            (const unsigned short *)nullptr, (float *)nullptr, n_eval_ptr, n_host, e0, e1);
-                        hipLaunchKernelGGL(k_conv_wide_f16x3_s16, g, block, lds, s, d, 2 * b + 1, (const unsigned short *)net->wideY, net->wideX,
+                        hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b + 1, (const unsigned short *)net->wideY, net->wideX,
                                            (const unsigned short *)net->wideX, b == d.blocks - 1 ? net->act : (float *)nullptr, n_eval_ptr, n_host, e0, e1);
                     }
                     if (part) {     // the heads read every board; if the join cannot be expressed on the streams, block

@@ -67,7 +67,7 @@ struct AzxNet {
     float *hb_value = nullptr;
     size_t lds_bytes = 0;
     int tower_variant = 0;
-    bool tower_f16 = false;     // variant 4 only: k_tower_f16_s16 (one product, AZX_FLAG_TOWER_F16 / AZX_TOWER=f16) reads the same packs
+    bool tower_f16 = false;     // variants 4 and 5: k_tower_f16_s16 / k_stem_wide_f16 + k_conv_wide_f16_s16 (one product, AZX_FLAG_TOWER_F16 / AZX_TOWER=f16) read the same packs
     // wide tower: the second half of a batch's boards runs its layer launches on a second stream
     hipStream_t stream2[3] = {nullptr, nullptr, nullptr};
     std::vector<uint32_t> cu_mask;   // azx_net_set_stream: the side streams are made on the engine's CU mask (empty = all CUs)

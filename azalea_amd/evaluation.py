@@ -240,8 +240,8 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     double as training data: dict(rows=..., row_metrics=...) as engine.Match.play(collect=True) returns them (row p of
     a game from the agent that moved at ply p; game_uid = the game's index, pair s owning [s * num_rounds,
     (s + 1) * num_rounds); games in the order they settled).  The games and tallies are the same with or without.
-    A policy attribute `tower_precision` ("f16": the plain-f16 tower, one MFMA per product; opt-in and OUTSIDE every
-    parity claim, policy.tower_flags) is honoured per agent, pooled or not: a match between the same weights at the
+    A policy attribute `tower_precision` ("f16": the plain-f16 tower, one MFMA per product, of the 6x64-class fused
+    tower or of the wide 128 / 256-channel tower; opt-in and OUTSIDE every parity claim, policy.tower_flags) is honoured per agent, pooled or not: a match between the same weights at the
     two precisions is two agents that differ in that attribute.  `info`: optional dict that receives, per agent
     index, its engine's kernel_info() (which tower and heads kernels played)."""
     import torch

@@ -97,7 +97,8 @@ class Player:
         OUTSIDE every parity claim, policy.tower_flags) is honoured per agent by the device engines of the one-agent
         throughput mode and of device_match (engine.FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product).  A
         ValueError -- here, before any engine is made -- when "f16" is asked for but the games would run through
-        the host loop or an external evaluator, or the network's shape has no fused tower."""
+        the host loop or an external evaluator, or the network's shape has no plain-f16 tower (the 6x64-class fused
+        tower's shapes and the wide tower's -- 128 / 256 channels, up to 13x13 -- have one, given at least one block)."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.agents = agents

@@ -79,8 +79,9 @@ def tower_flags(pol) -> int:
     evaluate_throughput): None / "f16x3" -- the split-f16 tower, as always -- give 0, "f16" gives
     engine.FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product.  That is an opt-in OUTSIDE every parity claim
     (not the reference's arithmetic; include/azx.h has the definition, DESIGN 7.8 the measured errors).  A
-    ValueError for an unknown string, and for "f16" on a policy whose network is not a HexNetwork the fused tower
-    covers (64 channels, at most 121 cells, at least one block).  Runs without a GPU and before any engine is made.
+    ValueError for an unknown string, and for "f16" on a policy whose network is not a HexNetwork with a plain-f16
+    tower: the fused tower's shapes (64 channels, at most 121 cells) or the wide tower's (a multiple of 128 channels,
+    any board), with at least one block either way.  Runs without a GPU and before any engine is made.
     Policy's own parity-mode engine never reads the attribute: parity mode stays parity."""
     prec = getattr(pol, "tower_precision", None)
     if prec not in TOWER_PRECISIONS:
@@ -91,9 +92,11 @@ def tower_flags(pol) -> int:
         raise ValueError("tower_precision='f16' selects a kernel of the built-in HexNetwork tower: this policy's "
                          "network runs through an external evaluator")
     n, blocks, chans = int(pol.board_size), int(pol.num_blocks), int(pol.base_chans)
-    if not (chans == 64 and n * n <= 121 and blocks >= 1):
-        raise ValueError("tower_precision='f16' needs a shape the fused tower covers (64 channels, at most 121 cells, "
-                         "at least one block): got %d blocks x %d channels on %dx%d" % (blocks, chans, n, n))
+    fused, wide = chans == 64 and n * n <= 121, chans >= 128 and chans % 128 == 0      # net.h: azx_net_has_f16_tower
+    if not ((fused or wide) and blocks >= 1):
+        raise ValueError("tower_precision='f16' needs a shape with a plain-f16 tower -- the fused tower's (64 channels, at "
+                         "most 121 cells) or the wide tower's (a multiple of 128 channels) -- and at least one block: got "
+                         "%d blocks x %d channels on %dx%d" % (blocks, chans, n, n))
     return _eng.FLAG_TOWER_F16
 
 

@@ -263,7 +263,7 @@ def save_checkpoint(policy, name, *, optimizer=None, replaybuf=None) -> str:
 def apply_selfplay_tower(policy, config) -> None:
     """config["selfplay_tower"] (absent / None / "f16x3": the split-f16 tower, as always; "f16": the plain-f16 tower)
     becomes the training policy's `tower_precision`, which its self-play Player honours (policy.tower_flags: a
-    ValueError for an unknown string or a network without a fused tower).  Absent, the policy is left as it is."""
+    ValueError for an unknown string or a network without a plain-f16 tower).  Absent, the policy is left as it is."""
     if "selfplay_tower" not in config:
         return
     from .policy import tower_flags
@@ -312,7 +312,7 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     config["selfplay_tower"] (default absent = the split-f16 tower; "f16": opt-in, NOT the reference's arithmetic and
     outside every parity claim): the self-play engine of the training policy runs the plain-f16 tower, one MFMA per
     product instead of three (engine.FLAG_TOWER_F16; include/azx.h has the definition, DESIGN 7.8 the measured
-    errors).  It sets the policy's `tower_precision` for its self-play side only (apply_selfplay_tower); the training
+    errors; the 6x64-class fused tower and the wide tower of 128 / 256 channels have one).  It sets the policy's `tower_precision` for its self-play side only (apply_selfplay_tower); the training
     step, the checkpoints and Policy's own parity-mode engine are untouched."""
     apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)

@@ -90,12 +90,25 @@ enum {
                                 fp32.  An activation beyond 65504 is +inf in f16 and raises AZX_ERANGE as without the flag;
                                 the weight range guard of azx_set_weights is the same.  Expect value errors of order 1e-4
                                 to 1e-3 and log-prob errors up to a few 1e-2 on peaked trained networks.
-                                AZX_EVAL_RESNET on a shape the fused tower covers (64 channels, at most 121 cells, at
-                                least one block) only, and not together with AZX_TOWER=fp32: azx_create is AZX_EINVAL
-                                otherwise.  Matches and tournaments take the flag per engine.  The environment variable
-                                AZX_TOWER=f16 selects the same kernel wherever the fused tower would run and is ignored
-                                elsewhere.  azx_kernel_info names the tower.  An addition WITHIN ABI revision 7:
-                                azx_config is unchanged. */
+                                The WIDE tower (tower variant 5: base_chans a multiple of 128, any board the engine
+                                supports, at least one block) has the same switch: k_stem_wide_f16 + k_conv_wide_f16_s16
+                                per layer instead of k_stem_wide_f16x3 + k_conv_wide_f16x3_s16.  Every convolution of the
+                                tower takes the hi half of each operand only: the folded stem and conv weights enter as
+                                f16(w) (part 0 of the same packs), the activation written back after each ReLU enters the
+                                next convolution as f16(a), the one-hot stem input is exact; products accumulate in fp32,
+                                the folded-BN bias is fp32.  The activation image in memory keeps its layout [cell][C hi |
+                                C lo]: the epilogue still writes the split pair and the residual is still read as hi + lo,
+                                so the residual stream is NOT rounded to f16 from block to block.  The last layer writes the
+                                same unrounded fp32 copy, and k_heads is unchanged: unlike the 6x64 case the head filters
+                                and their input are not rounded.  AZX_ERANGE and the weight packs as above.  Expect errors
+                                of order 1e-5 to 1e-4 (value) and 1e-4 (log-prob) on randomly initialised networks
+                                (DESIGN 7.8); no trained wide network has been measured.
+                                AZX_EVAL_RESNET on a shape with such a tower -- the fused tower's (64 channels, at most 121
+                                cells) or the wide tower's, at least one block either way -- only, and not together with
+                                AZX_TOWER=fp32: azx_create is AZX_EINVAL otherwise.  Matches and tournaments take the flag
+                                per engine.  The environment variable AZX_TOWER=f16 selects the same kernels wherever the
+                                flag would be accepted and is ignored elsewhere.  azx_kernel_info names the tower.  An
+                                addition WITHIN ABI revision 7: azx_config is unchanged. */
 };
 
 typedef struct {

@@ -12,7 +12,13 @@ split-f16 tower (k_tower_f16x3_s16), in ONE process on one GPU.  Recorded, not g
       the wins with its binomial (Wilson) 95 % interval
 
     python tools/bench_tower_precision.py [--steps 10] [--repeats 3] [--games 400] [--sims 400]
-One JSON line (profiles/tower_f16_bench.json)."""
+One JSON line (profiles/tower_f16_bench.json).
+
+--wide: the same (a) and (b) for the wide tower (k_conv_wide_f16_s16 against k_conv_wide_f16x3_s16) at the shape and
+batch of bench.py's config5 leg: 13x13, 19x256, 512 games x 10 rows per evaluation, 800 simulations, a seeded
+randomly initialised network (speed does not depend on the weights).  No (c): no trained wide checkpoint exists, so
+strength at the two precisions is NOT measured.
+    python tools/bench_tower_precision.py --wide [--steps 2] [--repeats 3]      (profiles/wide_f16_bench.json)"""
 import argparse
 import json
 import math
@@ -33,6 +39,7 @@ from azalea_amd.game.hex import HexGame
 from azalea_amd.policy import Policy
 
 BOARD, GAMES, BATCH = 11, 4096, 10
+BLOCKS, CHANS, SIMS, DESYNC = 6, 64, 400, 92
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 PRECISIONS = (("f16x3", 0), ("f16", eng.FLAG_TOWER_F16))
 
@@ -43,8 +50,16 @@ def golden_state(name):
     return {k[2:]: z[k] for k in z.files if k.startswith("w:")}
 
 
+def seeded_state(board, blocks, chans, seed=0):
+    from azalea_amd.network import HexNetwork
+    torch.manual_seed(seed)
+    net = HexNetwork(board_size=board, num_blocks=blocks, base_chans=chans).eval()
+    return {k: v.detach().numpy() for k, v in net.state_dict().items()}
+
+
 def headline_engine(flags, sims, state, pipeline):
-    """bench.py's headline engine with the pool started out of phase (random prefixes of 0..92 plies)."""
+    """bench.py's headline engine (--wide: its config5 leg's) with the pool started out of phase (random prefixes of
+    0..DESYNC plies)."""
     if pipeline:
         os.environ.pop("AZX_PIPELINE", None)
     else:
@@ -52,12 +67,12 @@ def headline_engine(flags, sims, state, pipeline):
     try:
         E = eng.Engine(board_size=BOARD, n_games=GAMES, simulations=sims, search_batch_size=BATCH, exploration_coef=0.5,
                        exploration_depth=15, noise_alpha=0.03, noise_scale=0.25, temperature=1.0,
-                       evaluator=eng.EVAL_RESNET, num_blocks=6, base_chans=64, flags=flags)
+                       evaluator=eng.EVAL_RESNET, num_blocks=BLOCKS, base_chans=CHANS, flags=flags)
     finally:
         os.environ.pop("AZX_PIPELINE", None)
     E.set_weights(state)
-    E.reset(moves=eng.random_prefixes(BOARD, np.arange(GAMES, dtype=np.int64), 92, 1))
-    E.play_steps(2)
+    E.reset(moves=eng.random_prefixes(BOARD, np.arange(GAMES, dtype=np.int64), DESYNC, 1))
+    E.play_steps(1 if CHANS > 64 else 2)
     return E
 
 
@@ -87,22 +102,33 @@ def wilson(k, n, z=1.96):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--games", type=int, default=400)
     ap.add_argument("--sims", type=int, default=400)
     ap.add_argument("--skip", default="", help="comma list of a, b, c")
+    ap.add_argument("--wide", action="store_true", help="the wide tower at bench.py's config5 shape (13x13, 19x256); no (c)")
     args = ap.parse_args()
     skip = set(args.skip.split(","))
+    if args.wide:
+        global BOARD, GAMES, BLOCKS, CHANS, SIMS, DESYNC
+        BOARD, GAMES, BLOCKS, CHANS, SIMS, DESYNC = 13, 512, 19, 256, 800, 128
+        skip.add("c")
+    if args.steps is None:
+        args.steps = 2 if args.wide else 10
     res = {"board": BOARD, "games": GAMES, "batch": BATCH, "device": torch.cuda.get_device_name(0),
            "steps": args.steps, "repeats": args.repeats}
-    g3 = golden_state("g3_forward_11_6x64.npz")
-    flop_per_row = 2.0 * 121 * (27 * 64 + 12 * 9 * 64 * 64 + 6 * 64)      # stem + 12 convs + the six head filters
+    g3 = seeded_state(BOARD, BLOCKS, CHANS) if args.wide else golden_state("g3_forward_11_6x64.npz")
+    # stem + convs + the six head filters: 11.7 MFLOP per 6x64 row on 11x11, 7.58 GFLOP per 19x256 row on 13x13
+    flop_per_row = 2.0 * BOARD * BOARD * (27 * CHANS + 2 * BLOCKS * 9 * CHANS * CHANS + 6 * CHANS)
+    if args.wide:
+        res.update(blocks=BLOCKS, chans=CHANS, sims=SIMS, weights="seeded random initialisation",
+                   strength="NOT measured: no trained wide checkpoint exists")
 
     for leg, pipeline in (("a", False), ("b", True)):
         if leg in skip:
             continue
-        engines = {name: headline_engine(flags, 400, g3, pipeline) for name, flags in PRECISIONS}
+        engines = {name: headline_engine(flags, SIMS, g3, pipeline) for name, flags in PRECISIONS}
         try:
             if leg == "a":
                 runs, last = alternate(engines, args.steps, args.repeats,
