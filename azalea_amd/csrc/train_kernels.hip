@@ -3348,6 +3348,13 @@ int azx_trn_step(AzxTrain *t, float lr, float momentum, float weight_decay, hipS
 }
 
 int azx_trn_debug(AzxTrain *t, const char *name, void *out, int64_t cap, int64_t *nbytes) {
+    if (!strcmp(name, "flags")) {
+        // host values (read at create; the graph on the first graphed step): copied here, not through the pointer table
+        const int32_t f[3] = {t->use_graph ? 1 : 0, t->fork ? 1 : 0, t->exec ? 1 : 0};
+        *nbytes = (int64_t)sizeof f;
+        if (out && cap >= *nbytes) memcpy(out, f, sizeof f);
+        return AZX_OK;
+    }
     auto it = t->dbg.find(name);
     if (it == t->dbg.end()) return tfail(AZX_EINVAL, std::string("train: no buffer named '") + name + "'");
     *nbytes = (int64_t)it->second.second;

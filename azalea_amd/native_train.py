@@ -220,10 +220,11 @@ class NativeTrainStep:
         return {"value": self.out_value, "moves_logprob": self.out_logprob[:, :k]}
 
     def debug(self, name: str) -> np.ndarray:
-        """An internal buffer by name (tests): raw<l> / act<l> / g<l> as float32 [B * cells * C], 'grad:<tensor>' flat."""
+        """An internal buffer by name (tests): raw<l> / act<l> / g<l> as float32 [B * cells * C], 'grad:<tensor>' flat;
+        'flags' is three int32 host values: AZX_TRAIN_GRAPH on, the filter-gradient fork on, the graph instantiated."""
         nbytes = C.c_int64(0)
         _lib.check(self._L.azx_train_debug(self._h, name.encode(), None, 0, C.byref(nbytes)))
-        dt = np.float64 if name in ("sums", "hsums") else np.float32
+        dt = np.float64 if name in ("sums", "hsums") else np.int32 if name == "flags" else np.float32
         out = np.empty(nbytes.value // np.dtype(dt).itemsize, dt)
         _lib.check(self._L.azx_train_debug(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), nbytes.value, C.byref(nbytes)))
         return out

@@ -657,7 +657,8 @@ int azx_train_outputs(azx_trainer *t, float **loss3, float **value, float **move
  * (a hipStream_t; NULL = the default stream) and NOT synchronised: order it after whatever filled the inputs and
  * before whatever reads the weights.  lr / momentum / weight_decay: torch.optim.SGD's (policy_trainer.py:44-49). */
 int azx_train_step(azx_trainer *t, float lr, float momentum, float weight_decay, void *hip_stream);
-/* tests: internal buffer by name ("raw<l>", "act<l>", "g<l>" [B][cells][C]; "sums"; "grad:<state_dict name>") */
+/* tests: internal buffer by name ("raw<l>", "act<l>", "g<l>" [B][cells][C]; "sums"; "grad:<state_dict name>");
+ * "flags" is three host int32: AZX_TRAIN_GRAPH on, the filter-gradient fork on (AZX_TRAIN_FORK), graph instantiated */
 int azx_train_debug(azx_trainer *t, const char *name, void *out, int64_t cap, int64_t *nbytes);
 
 /* engine stream (hipStream_t) so callers can bracket work with HIP events */
