@@ -147,6 +147,10 @@ SYMBOLS = {
     "azx_tournament_set_first_mover": (C.c_int, [_vp, C.c_int]),
     "azx_tournament_rows": (C.c_int, [_vp, _i64p]),
     "azx_rows_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _i32p, _i32p, _i32p, _f32p, _f32p, _i64p]),
+    # opening books of matches / tournaments (additions within revision 7)
+    "azx_openings_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p, _i32p, _i32p]),
+    "azx_match_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
+    "azx_tournament_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
 }
 
 class TrainConfig(C.Structure):

@@ -1911,6 +1911,112 @@ extern "C" int azx_debug_counters(azx_engine *e, uint64_t *out16) {
     return AZX_OK;
 }
 
+// ---- opening books of matches and tournaments: the host-side check (no device call) ---------------------------
+// Colour of the winner after `tile` was played, or 0: the mover's group around the tile is flood-filled and wins when
+// it spans rows 0 .. N-1 (colour 1) or columns 0 .. N-1 (colour 2) -- hex.py:204-231 over the :190-195 neighbourhood.
+static int hex_host_winner(const std::vector<int8_t> &board, int N, int tile) {
+    static const int dr[6] = {-1, -1, 0, 0, 1, 1}, dc[6] = {0, 1, -1, 1, -1, 0};
+    const int color = board[(size_t)tile];
+    std::vector<char> seen(board.size(), 0);
+    std::vector<int> border(1, tile);
+    seen[(size_t)tile] = 1;
+    int lo = N, hi = -1;
+    while (!border.empty()) {
+        const int t = border.back();
+        border.pop_back();
+        const int r = t / N, c = t - r * N, i = color == 1 ? r : c;
+        lo = std::min(lo, i);
+        hi = std::max(hi, i);
+        if (lo == 0 && hi == N - 1) return color;
+        for (int d = 0; d < 6; ++d) {
+            const int rr = r + dr[d], cc = c + dc[d];
+            if (rr < 0 || rr >= N || cc < 0 || cc >= N) continue;
+            const int nb = rr * N + cc;
+            if (seen[(size_t)nb] || board[(size_t)nb] != color) continue;
+            seen[(size_t)nb] = 1;
+            border.push_back(nb);
+        }
+    }
+    return 0;
+}
+
+// the arguments every opening-book entry point refuses before it looks at the table
+static int openings_args(int n_openings, int stride, const int16_t *moves, const int32_t *lengths) {
+    if (n_openings < 0 || n_openings > (1 << 20))
+        return fail(AZX_EINVAL, "n_openings %d outside [0, %d]", n_openings, 1 << 20);
+    if (stride < 0) return fail(AZX_EINVAL, "stride %d must be >= 0", stride);
+    if (n_openings > 0 && (!moves || !lengths)) return fail(AZX_EINVAL, "null opening table with n_openings = %d", n_openings);
+    return AZX_OK;
+}
+
+extern "C" int azx_openings_check(int board_size, int n_openings, int stride, const int16_t *moves,
+                                  const int32_t *lengths, int32_t *bad_opening, int32_t *bad_ply) {
+    if (board_size < 2 || board_size > AZX_MAX_BOARD)
+        return fail(AZX_EINVAL, "board_size %d outside [2, %d]", board_size, AZX_MAX_BOARD);
+    TRY(openings_args(n_openings, stride, moves, lengths));
+    const int N = board_size, ncells = N * N;
+    std::vector<int8_t> board((size_t)ncells);
+    auto refuse = [&](int o, int p) {
+        if (bad_opening) *bad_opening = o;
+        if (bad_ply) *bad_ply = p;
+        return AZX_EINVAL;
+    };
+    for (int o = 0; o < n_openings; ++o) {
+        const int len = lengths[o];
+        if (len < 0 || len > stride) {
+            (void)fail(AZX_EINVAL, "opening %d: length %d outside [0, stride %d]", o, len, stride);
+            return refuse(o, -1);
+        }
+        std::fill(board.begin(), board.end(), (int8_t)0);
+        for (int p = 0; p < len; ++p) {
+            const int mv = moves[(size_t)o * stride + p];
+            if (mv < 1 || mv > ncells) {
+                (void)fail(AZX_EINVAL, "opening %d, ply %d: move %d outside [1, %d] (tile + 1 on a %dx%d board)", o, p, mv,
+                           ncells, N, N);
+                return refuse(o, p);
+            }
+            if (board[(size_t)mv - 1]) {
+                (void)fail(AZX_EINVAL, "opening %d, ply %d: tile %d is played twice", o, p, mv - 1);
+                return refuse(o, p);
+            }
+            board[(size_t)mv - 1] = (int8_t)(1 + (p & 1));
+            if (hex_host_winner(board, N, mv - 1)) {
+                (void)fail(AZX_EINVAL, "opening %d, ply %d: move %d decides the game for colour %d (an opening must leave "
+                           "the game undecided)", o, p, mv, 1 + (p & 1));
+                return refuse(o, p);
+            }
+        }
+    }
+    return AZX_OK;
+}
+
+// the checked book on the device, replacing `*book` (the handle's); n_openings == 0 clears it.  Blocking copies:
+// no play call of the handle is running (they block), so the old tables are free to go.
+static int book_set(MatchBook *book, int board_size, int n_openings, int stride, const int16_t *moves,
+                    const int32_t *lengths) {
+    TRY(azx_openings_check(board_size, n_openings, stride, moves, lengths, nullptr, nullptr));
+    MatchBook nb = {nullptr, nullptr, 0, 0};
+    if (n_openings > 0) {
+        int16_t *dm = nullptr;
+        int32_t *dl = nullptr;
+        const size_t mbytes = sizeof(int16_t) * (size_t)n_openings * (size_t)stride;
+        hipError_t err = hipMalloc((void **)&dm, std::max<size_t>(mbytes, 16));
+        if (err == hipSuccess) err = hipMalloc((void **)&dl, sizeof(int32_t) * (size_t)n_openings);
+        if (err == hipSuccess && mbytes) err = hipMemcpy(dm, moves, mbytes, hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMemcpy(dl, lengths, sizeof(int32_t) * (size_t)n_openings, hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            if (dm) (void)hipFree(dm);
+            if (dl) (void)hipFree(dl);
+            return fail(AZX_ENOMEM, "copying a book of %d openings to the device failed: %s", n_openings, hipGetErrorString(err));
+        }
+        nb = MatchBook{dm, dl, n_openings, stride};
+    }
+    if (book->moves) (void)hipFree(const_cast<int16_t *>(book->moves));
+    if (book->len) (void)hipFree(const_cast<int32_t *>(book->len));
+    *book = nb;
+    return AZX_OK;
+}
+
 // ---- matches between two engines on the device (match_kernels.hip) -------------------------------------------
 // evaluation.worker + play_game (evaluation.py:60-80, play_game.py:27-52) for a whole pool of games: slot g of
 // engine a and slot g of engine b hold the two agents' trees of one game.  Per ply the host enqueues
@@ -1932,6 +2038,7 @@ struct azx_match {
     bool harvest = false;                        // azx_match_set_harvest: won games' replay rows go to a's harvest queue
     int first_mode = -1;                         // azx_match_set_first_mover
     int64_t rows_last = 0;                       // rows the last azx_match_play harvested
+    MatchBook book = {nullptr, nullptr, 0, 0};   // azx_match_set_openings: device tables the match owns (n == 0: none)
 };
 
 static const char *match_engine_problem(const azx_engine *e) {
@@ -1949,6 +2056,8 @@ extern "C" void azx_match_destroy(azx_match *m) {
     if (m->m.outcome) (void)hipFree(m->m.outcome);
     if (m->m.length) (void)hipFree(m->m.length);
     if (m->moves_buf) (void)hipFree(m->moves_buf);
+    if (m->book.moves) (void)hipFree(const_cast<int16_t *>(m->book.moves));
+    if (m->book.len) (void)hipFree(const_cast<int32_t *>(m->book.len));
     if (m->host_word) (void)hipHostFree(m->host_word);
     for (hipEvent_t ev : {m->ev_fork, m->ev_join, m->t0, m->t1})
         if (ev) (void)hipEventDestroy(ev);
@@ -1995,6 +2104,14 @@ extern "C" int azx_match_set_first_mover(azx_match *m, int mode) {
     if (!m) return fail(AZX_EINVAL, "null match");
     m->first_mode = mode;
     return AZX_OK;
+}
+
+extern "C" int azx_match_set_openings(azx_match *m, int n_openings, int stride, const int16_t *moves,
+                                      const int32_t *lengths) {
+    if (!m) return fail(AZX_EINVAL, "null match");
+    TRY(openings_args(n_openings, stride, moves, lengths));
+    ENGINE_GUARD(m->a);
+    return book_set(&m->book, m->a->d.N, n_openings, stride, moves, lengths);
 }
 
 extern "C" int azx_match_rows(azx_match *m, int64_t *rows_out) {
@@ -2109,6 +2226,7 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     M.n_games = n_games;
     M.harvest = m->harvest ? 1 : 0;
     M.first_mode = m->first_mode;
+    M.book = m->book;
     M.moves = moves ? m->moves_buf : nullptr;
     if (M.moves) HIPCHECK(hipMemsetAsync(M.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, sa));
     unsigned long long ctr0[MCTR_COUNT] = {0};
@@ -2118,6 +2236,7 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     azx_launch_reset(a->d, nullptr, G, nullptr, nullptr, 0, 0, sa);
     azx_launch_reset(b->d, nullptr, G, nullptr, nullptr, 0, 0, sa);
     azx_launch_match_init(a->d, b->d, M, sa);
+    if (M.book.n > 0) azx_launch_match_open(a->d, b->d, M, sa);      // the slots' first games from their openings
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(sa));                  // (ctr0 is on this frame)
     HIPCHECK(hipEventRecord(m->t0, sa));
@@ -2203,13 +2322,15 @@ struct azx_tournament {
     int sink = -1;                               // azx_tournament_set_harvest: the engine whose queue takes the rows
     int first_mode = -1;                         // azx_tournament_set_first_mover
     int64_t rows_last = 0;                       // rows the last azx_tournament_play harvested
+    MatchBook book = {nullptr, nullptr, 0, 0};   // azx_tournament_set_openings: as azx_match's
 };
 
 extern "C" void azx_tournament_destroy(azx_tournament *t) {
     if (!t) return;
     DevGuard guard(t->eng[0]->cfg.device);
     for (void *p : {(void *)t->eng_dev, (void *)t->tab_dev, (void *)t->t.tab_game, (void *)t->t.ctr,
-                    (void *)t->t.outcome, (void *)t->t.length, (void *)t->t.moves})
+                    (void *)t->t.outcome, (void *)t->t.length, (void *)t->t.moves, (void *)t->book.moves,
+                    (void *)t->book.len})
         if (p) (void)hipFree(p);
     if (t->host_word) (void)hipHostFree(t->host_word);
     for (hipEvent_t ev : {t->ev_fork, t->t0, t->t1})
@@ -2267,6 +2388,14 @@ extern "C" int azx_tournament_set_first_mover(azx_tournament *t, int mode) {
     if (!t) return fail(AZX_EINVAL, "null tournament");
     t->first_mode = mode;
     return AZX_OK;
+}
+
+extern "C" int azx_tournament_set_openings(azx_tournament *t, int n_openings, int stride, const int16_t *moves,
+                                           const int32_t *lengths) {
+    if (!t) return fail(AZX_EINVAL, "null tournament");
+    TRY(openings_args(n_openings, stride, moves, lengths));
+    ENGINE_GUARD(t->eng[0]);
+    return book_set(&t->book, t->eng[0]->d.N, n_openings, stride, moves, lengths);
 }
 
 extern "C" int azx_tournament_rows(azx_tournament *t, int64_t *rows_out) {
@@ -2398,6 +2527,7 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     D.moves = moves_dev;
     D.sink = t->sink;
     D.first_mode = t->first_mode;
+    D.book = t->book;
     std::vector<DevEngine> devs;
     for (azx_engine *e : t->eng) devs.push_back(e->d);
     std::vector<unsigned long long> ctr0((size_t)(P + 1) * MCTR_COUNT, 0ull);
@@ -2409,6 +2539,7 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     // fresh games in every slot of every engine (no generation is used up: the uids are the tournament's)
     for (azx_engine *e : t->eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 0, s0);
     azx_launch_tour_init(D, s0);
+    if (D.book.n > 0) azx_launch_tour_open(D, e0->d.slots, s0);      // the tables' first games from their openings
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s0));                  // (the uploads are from this frame)
     HIPCHECK(hipEventRecord(t->t0, s0));

@@ -15,6 +15,17 @@ enum {   // MatchDev::ctr slots
     MCTR_COUNT = 8
 };
 
+// An opening book (azx_match_set_openings / azx_tournament_set_openings): game u starts from the position after
+// the `len[o]` moves moves[o * stride + 0 ..] (tile + 1 in play order, colour 1 at the even plies) of opening
+// o = (u >> 1) % n under the alternating first mover, u % n under a fixed one.  n == 0: no book, every game starts
+// from the empty board.  The host has checked every opening (azx_openings_check): moves in range, no tile twice,
+// undecided after every move.
+struct MatchBook {
+    const int16_t *moves;          // [n][stride]
+    const int32_t *len;            // [n]
+    int32_t n, stride;
+};
+
 struct MatchDev {
     int64_t *slot_game;            // [G] game index u the slot is playing, -1 = idle
     int64_t first_game, n_games;   // the call plays games first_game .. first_game + n_games - 1
@@ -25,10 +36,14 @@ struct MatchDev {
     int32_t harvest;               // 1: every won game's replay rows are appended to the harvest queue (q_*, q_count) of
                                    // engine A when the game settles (match_harvest); 0 = off
     int32_t first_mode;            // -1: agent u & 1 moves first in game u; 0 / 1: that agent moves first in every game
+    MatchBook book;                // the games' opening positions (n == 0: the empty board)
 };
 
 // slot g takes game first_game + g (idle beyond n_games); both engines' slots get uid = game index
 void azx_launch_match_init(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st);
+// with a book only, after azx_launch_match_init: every slot's first game is set up from its opening, exactly as
+// the refill of azx_launch_match_step sets up a later one
+void azx_launch_match_open(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st);
 // whose turn: GameHdr.active in both engines (mover's 1, the other 0; idle slots 0 in both)
 void azx_launch_match_turn(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st);
 // hand the mover's drawn move over, step both engines' slots, settle finished / voided games and refill
@@ -57,11 +72,14 @@ struct TourDev {
     int32_t sink;                  // harvest target: -1 = off, else the index in eng[] of the engine whose harvest queue
                                    // takes the won games' replay rows of ALL pairs (as MatchDev::harvest)
     int32_t first_mode;            // as MatchDev::first_mode
+    MatchBook book;                // as MatchDev::book
 };
 
 // every table takes its pair's round `local` (idle beyond `rounds`) and both its slots that game's uid; every slot
 // of every engine gets active = 0, so the slots no table owns are never searched
 void azx_launch_tour_init(const TourDev &T, hipStream_t st);
+// azx_launch_match_open for every table (with a book only, after azx_launch_tour_init)
+void azx_launch_tour_open(const TourDev &T, int slots, hipStream_t st);
 // whose turn: GameHdr.active of each table's two slots (mover's 1, the other 0; idle tables 0 in both)
 void azx_launch_tour_turn(const TourDev &T, hipStream_t st);
 // k_match_step for a table: hand-over, game step in both slots, settle into the pair's tallies, refill from the

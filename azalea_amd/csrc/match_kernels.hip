@@ -18,6 +18,9 @@
 __device__ __forceinline__ int match_first(int64_t u, int mode) { return mode < 0 ? (int)(u & 1) : mode; }
 // agent to move in game u at `ply`
 __device__ __forceinline__ int match_mover(int64_t u, int ply, int mode) { return match_first(u, mode) ^ (ply & 1); }
+// opening of game u (MatchBook::n > 0): games 2j and 2j + 1 of the alternating first mover share one, so that every
+// opening is played with the colours both ways round; keyed on the game index alone, like the draws
+__device__ __forceinline__ int match_opening(int64_t u, int n, int mode) { return (int)((mode < 0 ? u >> 1 : u) % n); }
 
 __global__ void k_match_init(DevEngine A, DevEngine B, MatchDev M) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -44,32 +47,67 @@ __global__ void k_match_turn(DevEngine A, DevEngine B, MatchDev M) {
     B.ghdr[g].active = b;
 }
 
-// fresh empty game in slot g of one engine (what advance_body's play-mode restart does, with the uid given)
+// fresh game in slot g of one engine (what advance_body's play-mode restart does, with the uid given): the empty
+// board, or with a book the position after game uid's opening, in the state k_reset leaves for that move prefix
+// (stones, colour, ply = ply0 = the opening's length, a one-node tree over the position's legal moves in arena 0)
 template <int SLOTS>
-__device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t uid, int lane) {
+__device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t uid, const MatchBook &bk, int mode,
+                                              int lane) {
     HexWave<SLOTS> z;
     z.clear();
+    int ply = 0, k = E.ncells;
+    const bool opened = bk.n > 0 && uid >= 0;
+    if (opened) {
+        const int o = match_opening(uid, bk.n, mode);
+        const int16_t *mv = bk.moves + (size_t)o * bk.stride;
+        ply = __builtin_amdgcn_readfirstlane(bk.len[o]);
+        z.geom(E.N, lane);
+        for (int p = 0; p < ply; ++p) z.step(__builtin_amdgcn_readfirstlane(mv[p] - 1), E.N, lane);   // (wave-uniform)
+        k = make_masks<SLOTS>(z, lane, E.ncells).k;
+    }
     z.store(E.cells + (size_t)g * SLOTS * 64, lane);
     GameHdr *gh = E.ghdr + g;
     if (lane == 0) {
-        gh->color = 1;
-        gh->winner = 0;
-        gh->ply = 0;
+        gh->color = z.color;
+        gh->winner = z.winner;
+        gh->ply = ply;
         gh->active = 0;            // k_match_turn decides
         gh->move_id = -1;
         gh->n_rows = 0;
-        gh->ply0 = 0;
+        gh->ply0 = ply;
         gh->parked = 0;
         if (uid >= 0) gh->uid = uid;
+        if (opened) E.thdr[g].arena = 0;
     }
     __builtin_amdgcn_s_waitcnt(0);
-    tree_reset<SLOTS>(E, g, E.thdr + g, E.ncells, lane);
+    tree_reset<SLOTS>(E, g, E.thdr + g, k, lane);
+}
+
+// game u's record begins with its opening (MatchBook::n > 0; `rec` is the game's row of the moves buffer)
+__device__ __forceinline__ void match_record_opening(int16_t *rec, int64_t u, const MatchBook &bk, int mode, int lane) {
+    const int o = match_opening(u, bk.n, mode);
+    const int16_t *mv = bk.moves + (size_t)o * bk.stride;
+    const int len = bk.len[o];
+    for (int p = lane; p < len; p += 64) rec[p] = mv[p];
+}
+
+// with a book, after k_match_init: one wave per slot sets up the slot's first game, as the refill does later ones
+template <int SLOTS>
+__global__ __launch_bounds__(64) void k_match_open(DevEngine A, DevEngine B, MatchDev M) {
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x;
+    const int64_t u = M.slot_game[g];
+    if (u < 0) return;
+    match_restart<SLOTS>(A, g, u, M.book, M.first_mode, lane);
+    match_restart<SLOTS>(B, g, u, M.book, M.first_mode, lane);
+    if (M.moves) match_record_opening(M.moves + (size_t)(u - M.first_game) * A.ncells, u, M.book, M.first_mode, lane);
 }
 
 // ---- settle-time harvest: a won game's replay rows into a harvest queue (play_game.py:59-67 for two agents) ----
 // Each engine's move draw (choose_body) has written the rows of the plies IT moved at into its own slot's row area, at
 // row index GameHdr.n_rows: the first mover holds plies 0, 2, 4, ... at rows 0, 1, 2, ..., the other agent plies 1, 3,
-// 5, ....  Row p of the game is therefore row p >> 1 of the engine that moved at ply p.  `src` rows of PIECES 16-byte
+// 5, ....  Row p of the game is therefore row p >> 1 of the engine that moved at ply p (a game from an opening of
+// ply0 moves: row (p - ply0) >> 1, the agent that moved at ply0 holding the even offsets).  `src` rows of PIECES 16-byte
 // pieces each go to every second row of `dst` (which points at the game's first or second queue row), eight pieces
 // in flight per lane.
 template <int PIECES>
@@ -108,9 +146,11 @@ __device__ __forceinline__ MatchSink match_sink(const DevEngine &E) {
     return MatchSink{E.q_board, E.q_prob, E.q_color, E.q_k, E.q_reward, E.q_uid, E.q_meta, E.q_count, E.q_cap};
 }
 
-// the `n` rows of slot `slot` of engine E are the game's plies off, off + 2, ...: queue rows pos + off, pos + off + 2, ...
-__device__ __forceinline__ void match_harvest_rows(const DevEngine &E, int slot, int n, int off, const MatchSink &Q,
-                                                   unsigned long long pos, int64_t u, int winner, int lane) {
+// the `n` rows of slot `slot` of engine E are the game's plies ply0 + off, ply0 + off + 2, ... (ply0: the ply the
+// game's first search ran at, its opening's length): queue rows pos + off, pos + off + 2, ...
+__device__ __forceinline__ void match_harvest_rows(const DevEngine &E, int slot, int n, int off, int ply0,
+                                                   const MatchSink &Q, unsigned long long pos, int64_t u, int winner,
+                                                   int lane) {
     const size_t sr = (size_t)slot * E.ncells;                     // the slot's first row
     const size_t q0 = (size_t)pos + off;
     match_copy_rows<AZX_CELL_STRIDE / 16>(reinterpret_cast<uint4 *>(Q.q_board + q0 * AZX_CELL_STRIDE),
@@ -118,8 +158,8 @@ __device__ __forceinline__ void match_harvest_rows(const DevEngine &E, int slot,
     match_copy_rows<AZX_CELL_STRIDE / 4>(reinterpret_cast<uint4 *>(Q.q_prob + q0 * AZX_CELL_STRIDE),
                                          reinterpret_cast<const uint4 *>(E.row_prob + sr * AZX_CELL_STRIDE), n, lane);
     for (int r = lane; r < n; r += 64) {
-        const int p = 2 * r + off;
-        const size_t q = (size_t)pos + p;
+        const int p = ply0 + 2 * r + off;                          // the ply from the empty board: colour and reward sign
+        const size_t q = (size_t)pos + 2 * r + off;
         Q.q_color[q] = p & 1;
         Q.q_k[q] = E.row_k[sr + r];
         float rew = winner == 1 ? 1.0f : -1.0f;                    // play_game.py:64-65
@@ -128,22 +168,25 @@ __device__ __forceinline__ void match_harvest_rows(const DevEngine &E, int slot,
         Q.q_uid[q] = u;
         const float4 *ms = reinterpret_cast<const float4 *>(E.row_meta) + (sr + r) * 2;
         float4 mt = ms[0];
-        mt.w = p == 0 ? 1.0f : 0.0f;                               // marks the first row of a game
+        mt.w = p == ply0 ? 1.0f : 0.0f;                            // marks the first row of a game
         reinterpret_cast<float4 *>(Q.q_meta)[q * 2] = mt;
         reinterpret_cast<float4 *>(Q.q_meta)[q * 2 + 1] = ms[1];
     }
 }
 
-// One wave.  Slots sa of A and sb of B hold the finished game u (`len` plies, colour `winner` won, agent `first` moved
-// first); Q is the engine whose queue takes the rows.  The game's rows are reserved with one atomicAdd and stay
-// contiguous, plies ascending.  The queue is no ring here and the host sizes it for the worst case; should the rows
+// One wave.  Slots sa of A and sb of B hold the finished game u (`len` plies of which the first `ply0` were its
+// opening, colour `winner` won, agent `first` owns the even plies); Q is the engine whose queue takes the rows.  The
+// agent that moved at ply0 holds plies ply0, ply0 + 2, ... at its rows 0, 1, ..., the other one ply0 + 1, ....  The
+// game's rows are reserved with one atomicAdd and stay contiguous, plies ascending.  The queue is no ring here and the host sizes it for the worst case; should the rows
 // not fit after all, or the two engines' row counts not add up to the game, the reservation is given back, nothing
 // is written and `lost` counts the rows (the host reports that as an internal error).
 __device__ __forceinline__ void match_harvest(const DevEngine &A, int sa, const DevEngine &B, int sb, const MatchSink &Q,
                                               unsigned long long *lost, int64_t u, int first, int winner, int len,
-                                              int lane) {
+                                              int ply0, int lane) {
     const int nA = A.ghdr[sa].n_rows, nB = B.ghdr[sb].n_rows;
-    bool ok = nA + nB == len && (first ? nB : nA) == (len + 1) >> 1;
+    const int opener = first ^ (ply0 & 1);                               // the agent that moved at ply0
+    len -= ply0;                                                         // the rows of the game: one per searched ply
+    bool ok = nA + nB == len && (opener ? nB : nA) == (len + 1) >> 1;
     unsigned long long pos = 0;
     if (ok) {
         if (lane == 0) pos = atomicAdd(Q.q_count, (unsigned long long)len);
@@ -158,8 +201,8 @@ __device__ __forceinline__ void match_harvest(const DevEngine &A, int sa, const 
         if (lane == 0) atomicAdd(lost, (unsigned long long)len);
         return;
     }
-    match_harvest_rows(A, sa, nA, first, Q, pos, u, winner, lane);       // agent 0 moved at the even plies iff it moved first
-    match_harvest_rows(B, sb, nB, 1 - first, Q, pos, u, winner, lane);
+    match_harvest_rows(A, sa, nA, opener, ply0, Q, pos, u, winner, lane);      // agent 0 holds the even rows iff it opened
+    match_harvest_rows(B, sb, nB, 1 - opener, ply0, Q, pos, u, winner, lane);
 }
 
 // One wave per slot, after both engines' searches and move draws of this ply.
@@ -170,7 +213,7 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
     const int64_t u = M.slot_game[g];
     if (u < 0) return;                                         // idle slot
     GameHdr *ga = A.ghdr + g, *gb = B.ghdr + g;
-    const int ply = ga->ply;                                   // (the two slots hold the same game)
+    const int ply = ga->ply, ply0 = ga->ply0;                  // (the two slots hold the same game)
     const int first = match_first(u, M.first_mode);
     const int mover = first ^ (ply & 1);
     const int mid = mover ? gb->move_id : ga->move_id;
@@ -212,7 +255,8 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
     }
     if (!voided && winner == 0) return;                        // the game goes on
 
-    if (M.harvest && !voided) match_harvest(A, g, B, g, match_sink(A), M.ctr + MCTR_ROWS_LOST, u, first, winner, len, lane);
+    if (M.harvest && !voided)
+        match_harvest(A, g, B, g, match_sink(A), M.ctr + MCTR_ROWS_LOST, u, first, winner, len, ply0, lane);
 
     // ---- settle: outcome by agent, tallies, the next game for this slot ----
     long long next_u = -1;
@@ -228,7 +272,7 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
         }
         M.outcome[idx] = (int8_t)outcome;
         M.length[idx] = (int16_t)len;
-        atomicAdd(M.ctr + MCTR_PLIES, (unsigned long long)len);
+        atomicAdd(M.ctr + MCTR_PLIES, (unsigned long long)(len - ply0));     // the moves searched and played
         atomicAdd(M.ctr + MCTR_DECIDED, 1ull);
         // the lowest game index not yet started, or idle
         const unsigned long long nx = atomicAdd(M.ctr + MCTR_NEXT, 1ull);
@@ -237,12 +281,20 @@ __global__ __launch_bounds__(64) void k_match_step(DevEngine A, DevEngine B, Mat
     }
     next_u = ((long long)__builtin_amdgcn_readfirstlane((int)(next_u >> 32)) << 32) |
              (unsigned int)__builtin_amdgcn_readfirstlane((int)next_u);
-    match_restart<SLOTS>(A, g, next_u, lane);
-    match_restart<SLOTS>(B, g, next_u, lane);
+    match_restart<SLOTS>(A, g, next_u, M.book, M.first_mode, lane);
+    match_restart<SLOTS>(B, g, next_u, M.book, M.first_mode, lane);
+    if (M.book.n > 0 && next_u >= 0 && M.moves)
+        match_record_opening(M.moves + (size_t)(next_u - M.first_game) * A.ncells, next_u, M.book, M.first_mode, lane);
 }
 
 void azx_launch_match_init(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
     hipLaunchKernelGGL(k_match_init, dim3((A.G + 255) / 256), dim3(256), 0, st, A, B, M);
+}
+
+void azx_launch_match_open(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
+#define CALL(S) hipLaunchKernelGGL((k_match_open<S>), dim3(A.G), dim3(64), 0, st, A, B, M)
+    DISPATCH_SLOTS(A.slots, CALL);
+#undef CALL
 }
 
 void azx_launch_match_turn(const DevEngine &A, const DevEngine &B, const MatchDev &M, hipStream_t st) {
@@ -275,6 +327,20 @@ __global__ void k_tour_init(TourDev T) {
     }
 }
 
+// k_match_open for a table
+template <int SLOTS>
+__global__ __launch_bounds__(64) void k_tour_open(TourDev T) {
+    const int lane = threadIdx.x;
+    const int t = blockIdx.x;
+    const int64_t u = T.tab_game[t];
+    if (u < 0) return;
+    const TourTable tb = T.tab[t];
+    const DevEngine &A = T.eng[tb.ea], &B = T.eng[tb.eb];
+    match_restart<SLOTS>(A, tb.sa, u, T.book, T.first_mode, lane);
+    match_restart<SLOTS>(B, tb.sb, u, T.book, T.first_mode, lane);
+    if (T.moves) match_record_opening(T.moves + (size_t)(u - T.first_game) * A.ncells, u, T.book, T.first_mode, lane);
+}
+
 __global__ void k_tour_turn(TourDev T) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T.n_tables) return;
@@ -302,7 +368,7 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
     const DevEngine &A = T.eng[tb.ea], &B = T.eng[tb.eb];
     const int sa = tb.sa, sb = tb.sb;
     GameHdr *ga = A.ghdr + sa, *gb = B.ghdr + sb;
-    const int ply = ga->ply;                                   // (the two slots hold the same game)
+    const int ply = ga->ply, ply0 = ga->ply0;                  // (the two slots hold the same game)
     const int ncells = A.ncells;
     const int first = match_first(u, T.first_mode);
     const int mover = first ^ (ply & 1);
@@ -344,7 +410,7 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
 
     if (T.sink >= 0 && !voided)
         match_harvest(A, sa, B, sb, match_sink(T.eng[T.sink]), T.ctr + (size_t)tb.pair * MCTR_COUNT + MCTR_ROWS_LOST, u, first, winner,
-                      len, lane);
+                      len, ply0, lane);
 
     // ---- settle into the pair's tallies; the pair's next round for this table ----
     long long next_u = -1;
@@ -361,7 +427,7 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
         }
         T.outcome[idx] = (int8_t)outcome;
         T.length[idx] = (int16_t)len;
-        atomicAdd(ctr + MCTR_PLIES, (unsigned long long)len);
+        atomicAdd(ctr + MCTR_PLIES, (unsigned long long)(len - ply0));       // the moves searched and played
         atomicAdd(ctr + MCTR_DECIDED, 1ull);
         atomicAdd(T.ctr + (size_t)T.n_pairs * MCTR_COUNT + MCTR_DECIDED, 1ull);
         const unsigned long long nx = atomicAdd(ctr + MCTR_NEXT, 1ull);
@@ -370,13 +436,21 @@ __global__ __launch_bounds__(64) void k_tour_step(TourDev T) {
     }
     next_u = ((long long)__builtin_amdgcn_readfirstlane((int)(next_u >> 32)) << 32) |
              (unsigned int)__builtin_amdgcn_readfirstlane((int)next_u);
-    match_restart<SLOTS>(A, sa, next_u, lane);
-    match_restart<SLOTS>(B, sb, next_u, lane);
+    match_restart<SLOTS>(A, sa, next_u, T.book, T.first_mode, lane);
+    match_restart<SLOTS>(B, sb, next_u, T.book, T.first_mode, lane);
+    if (T.book.n > 0 && next_u >= 0 && T.moves)
+        match_record_opening(T.moves + (size_t)(next_u - T.first_game) * ncells, next_u, T.book, T.first_mode, lane);
 }
 
 void azx_launch_tour_init(const TourDev &T, hipStream_t st) {
     const int n = T.n_tables > T.n_engines * T.max_g ? T.n_tables : T.n_engines * T.max_g;
     hipLaunchKernelGGL(k_tour_init, dim3((n + 255) / 256), dim3(256), 0, st, T);
+}
+
+void azx_launch_tour_open(const TourDev &T, int slots, hipStream_t st) {
+#define CALL(S) hipLaunchKernelGGL((k_tour_open<S>), dim3(T.n_tables), dim3(64), 0, st, T)
+    DISPATCH_SLOTS(slots, CALL);
+#undef CALL
 }
 
 void azx_launch_tour_turn(const TourDev &T, hipStream_t st) {

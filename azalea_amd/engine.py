@@ -546,6 +546,63 @@ def _collected(out, sink, n_rows, collect):
         out["row_metrics"] = sink.play_row_metrics(n_rows)
 
 
+_KEEP = object()            # play(openings=...) not given: the book stays as set_openings left it
+
+
+def _book_key(openings):
+    """A book as a tuple of move tuples (None = no book = ()): what Match / Tournament remember having set."""
+    return tuple(tuple(int(m) for m in o) for o in ([] if openings is None else openings))
+
+
+def _book_arrays(openings):
+    """A list of move lists as the library's opening table: (n, stride, moves int16[n, stride], lengths int32[n])."""
+    book = [list(o) for o in _book_key(openings)]
+    n = len(book)
+    stride = max([1] + [len(o) for o in book])
+    mv = np.zeros((max(n, 1), stride), np.int16)
+    ln = np.zeros(max(n, 1), np.int32)
+    for i, o in enumerate(book):
+        if any(m < -32768 or m > 32767 for m in o):
+            raise ValueError("opening %d: a move does not fit the int16 of a game record" % i)
+        mv[i, :len(o)] = o
+        ln[i] = len(o)
+    return n, stride, mv, ln
+
+
+def _book_error(rc):
+    """A refused book is the caller's mistake: ValueError with the library's message; anything else as check()."""
+    if rc == -1:                # AZX_EINVAL
+        raise ValueError(_lib.lib().azx_last_error().decode(errors="replace"))
+    check(rc)
+
+
+def openings_check(board_size, openings):
+    """azx_openings_check: ValueError, with the library's message (opening, ply, reason), unless every opening -- a
+    list of moves, tile + 1 in play order as in a game record, colour 1 first -- has its moves on the board, plays no
+    tile twice and leaves the game undecided after every move.  Host only: no GPU is needed."""
+    n, stride, mv, ln = _book_arrays(openings)
+    _book_error(_lib.lib().azx_openings_check(int(board_size), n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32), None, None))
+
+
+def all_openings(board_size, plies=1):
+    """Every sequence of `plies` (1 or 2) moves on distinct tiles, in ascending order: n * n openings of one move,
+    n * n * (n * n - 1) of two.  Host only.  No position that shallow is decided on a board of size 3 or more; on a
+    smaller one filter the list through openings_check."""
+    if plies not in (1, 2):
+        raise ValueError("plies must be 1 or 2")
+    cells = int(board_size) * int(board_size)
+    if plies == 1:
+        return [[a] for a in range(1, cells + 1)]
+    return [[a, b] for a in range(1, cells + 1) for b in range(1, cells + 1) if b != a]
+
+
+def _opening_index(first_game, n_games, n_openings, first_mover):
+    """The opening of games first_game .. first_game + n_games - 1 (the rule of include/azx.h): (u >> 1) % n under the
+    alternating first mover, u % n under a fixed one."""
+    u = np.arange(int(first_game), int(first_game) + int(n_games), dtype=np.int64)
+    return ((u >> 1 if first_mover is None else u) % n_openings).astype(np.int32)
+
+
 class Match:
     """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
     agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
@@ -561,6 +618,18 @@ class Match:
         self.h = C.c_void_p()
         check(self.L.azx_match_create(engine_a.h, engine_b.h, C.byref(self.h)))
         self._mode = (0, -1)          # (harvest, first mover) as set in the library
+        self._book = ()               # the opening book as set in the library (a tuple of move tuples; () = none)
+
+    def set_openings(self, openings):
+        """azx_match_set_openings: the following play() calls start game u from opening (u >> 1) % n -- games 2j and
+        2j + 1 are one opening with the agents' colours swapped -- or u % n under a fixed first mover.  `openings` is a
+        list of move lists (tile + 1 in play order, colour 1 first, [] = the empty board); None or [] clears the book.
+        ValueError with the library's message for a book it refuses (openings_check for this board size); the book
+        set before stays in place then.  Not in the reference, whose evaluation games all start from the empty
+        board; use an even first_game and an even number of games for colour-balanced results."""
+        n, stride, mv, ln = _book_arrays(openings)
+        _book_error(self.L.azx_match_set_openings(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32)))
+        self._book = _book_key(openings)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -573,7 +642,7 @@ class Match:
         except Exception:
             pass
 
-    def play(self, n_games, first_game=0, moves=False, collect=False, first_mover=None):
+    def play(self, n_games, first_game=0, moves=False, collect=False, first_mover=None, openings=_KEEP):
         """Games first_game .. first_game + n_games - 1, each to its end.  Returns outcome int8[n] (+1 agent 0 won,
         -1 agent 1 won, 0 voided by SearchTreeFull), length int16[n] (plies), with `moves` the game records
         int16[n, cells] (tile + 1 in play order, 0-padded), and stats (azx_match_stats as a dict).
@@ -583,9 +652,15 @@ class Match:
         ascending, game_uid = the game index) and "row_metrics" ([rows, ROW_METRICS], Engine.play_row_metrics);
         "device": the rows stay in engine a's queue for rows_pack / replay_put_records and only their count is
         returned, as "n_rows" (either way).  `first_mover`: None -- agent u & 1 moves first in game u; 0 / 1 -- that
-        agent moves first in every game (play_game always starts with agents[0])."""
+        agent moves first in every game (play_game always starts with agents[0]).
+        `openings`: the book to play from, as set_openings takes it (None or [] = none); not given, the book stays
+        as it is.  With a book, a record begins with the game's opening, `length` counts it, stats["plies"] does
+        not, the rows of a game begin at the opening's length, and the result gains "opening": the opening index of
+        each game, int32[n]."""
         if collect not in (False, True, "device"):
             raise ValueError("collect must be False, True or 'device'")
+        if openings is not _KEEP and _book_key(openings) != self._book:
+            self.set_openings(openings)
         # (set only when they change: a plain play touches none of the later entry points of the library)
         want = (1 if collect else 0, -1 if first_mover is None else int(first_mover))
         if want[0] != self._mode[0]:
@@ -614,6 +689,8 @@ class Match:
         out = dict(outcome=outcome, length=length, stats=st.as_dict())
         if moves:
             out["moves"] = mv
+        if self._book:
+            out["opening"] = _opening_index(first_game, n, len(self._book), first_mover)
         if collect:
             rows = C.c_int64(0)
             check(self.L.azx_match_rows(self.h, C.byref(rows)))
@@ -637,6 +714,15 @@ class Tournament:
         check(self.L.azx_tournament_create(arr, len(self.engines), C.byref(self.h)))
         self.cells = self.engines[0].cells
         self._mode = (-1, -1)         # (sink, first mover) as set in the library
+        self._book = ()               # the opening book as set in the library (as Match's)
+
+    def set_openings(self, openings):
+        """azx_tournament_set_openings: as Match.set_openings, for the games of every pair.  The rule is keyed on the
+        game index u = first_game + s * rounds + r, so pair s still plays the games of its Match over that range; an
+        even first_game and even `rounds` keep every pair colour-balanced."""
+        n, stride, mv, ln = _book_arrays(openings)
+        _book_error(self.L.azx_tournament_set_openings(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32)))
+        self._book = _book_key(openings)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -650,16 +736,19 @@ class Tournament:
             pass
 
     def play(self, pairs, rounds, first_game=0, tables_per_pair=None, moves=False, collect=False, sink=0,
-             first_mover=None):
+             first_mover=None, openings=_KEEP):
         """`rounds` games of every pair, each to its end.  Returns {pair: dict(outcome int8[rounds], length
         int16[rounds], stats[, moves int16[rounds, cells]])} in the order of `pairs`, each as Match.play returns it
         (stats['seconds'] is the whole call's device time).  tables_per_pair defaults to the most every engine has
         room for, at most `rounds`.
         `collect`, `first_mover`: as Match.play; the rows of ALL pairs go to the harvest queue of engines[sink], and
         the result gains the keys "rows" / "row_metrics" (collect=True) and "n_rows" beside the pairs.  Pair s owns
-        the rows with game_uid in [first_game + s * rounds, first_game + (s + 1) * rounds)."""
+        the rows with game_uid in [first_game + s * rounds, first_game + (s + 1) * rounds).
+        `openings`: as Match.play; with a book every pair's dict gains "opening"."""
         if collect not in (False, True, "device"):
             raise ValueError("collect must be False, True or 'device'")
+        if openings is not _KEEP and _book_key(openings) != self._book:
+            self.set_openings(openings)
         want = (int(sink) if collect else -1, -1 if first_mover is None else int(first_mover))
         if want[0] != self._mode[0]:
             check(self.L.azx_tournament_set_harvest(self.h, want[0]))
@@ -701,6 +790,8 @@ class Tournament:
             out[pair] = dict(outcome=outcome[sl], length=length[sl], stats=st[s].as_dict())
             if moves:
                 out[pair]["moves"] = mv[sl]
+            if self._book:
+                out[pair]["opening"] = _opening_index(int(first_game) + s * rounds, rounds, len(self._book), first_mover)
         if collect:
             rows = C.c_int64(0)
             check(self.L.azx_tournament_rows(self.h, C.byref(rows)))

@@ -218,7 +218,7 @@ def _throughput_policy(agent, external_batch=False):
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                         games=None, external_batch: bool = False, pooled: bool = False,
-                        collect=None, info=None) -> Dict[Pair, OutcomeCounts]:
+                        collect=None, info=None, openings=None) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -243,7 +243,15 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     A policy attribute `tower_precision` ("f16": the plain-f16 tower, one MFMA per product, of the 6x64-class fused
     tower or of the wide 128 / 256-channel tower; opt-in and OUTSIDE every parity claim, policy.tower_flags) is honoured per agent, pooled or not: a match between the same weights at the
     two precisions is two agents that differ in that attribute.  `info`: optional dict that receives, per agent
-    index, its engine's kernel_info() (which tower and heads kernels played)."""
+    index, its engine's kernel_info() (which tower and heads kernels played).
+    `openings`: an opening book, a list of move lists (tile + 1 in play order, colour 1 first; engine.all_openings
+    makes the usual ones), handed to every match or to the one tournament: game u -- pair s plays u = s * num_rounds
+    .. (s + 1) * num_rounds - 1 -- starts from opening (u >> 1) % len(openings), so rounds 2j and 2j + 1 of a pair are
+    one opening with the colours swapped.  Use an EVEN num_rounds: with an odd one a pair's last opening is played
+    one way round only and the following pairs' openings fall out of step with their colours.  Pooled or not, the
+    games are the same; `games[pair]` gains "opening", the opening index of each game.  NOT the reference's
+    behaviour, whose evaluation games all start from the empty board; off by default.  A ValueError with the
+    library's message, before any engine is made, for a book the rules refuse (engine.openings_check)."""
     import torch
     from . import engine as _eng
     from .policy import SearchTreeFull, external_evaluator, tower_flags
@@ -257,6 +265,8 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     if len(agents) > 256 or len(pairs) * num_rounds >= 1 << 32 or not 0 <= int(seed) < 1 << 24:
         raise ValueError("evaluate_throughput: at most 256 agents, 2^32 games and a seed below 2^24")
     n = agents[0].game.board_size
+    openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
+    _eng.openings_check(n, openings)
     opponents = max(1, len(agents) - 1)
     if n_slots is None:
         n_slots = min((opponents if pooled else 1) * num_rounds, int(os.environ.get("AZX_GAMES", "4096")))
@@ -313,7 +323,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
             tour = _eng.Tournament(engines)
             try:
                 results = tour.play(pairs, num_rounds, tables_per_pair=tables_per_pair, moves=games is not None,
-                                    collect=collect is not None)
+                                    collect=collect is not None, openings=openings)
             finally:
                 tour.close()
         for s, (i, j) in enumerate(pairs):
@@ -321,7 +331,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                 match = _eng.Match(engines[i], engines[j])
                 try:
                     results[(i, j)] = match.play(num_rounds, first_game=s * num_rounds, moves=games is not None,
-                                                 collect=collect is not None)
+                                                 collect=collect is not None, openings=openings)
                 finally:
                     match.close()
             res = results[(i, j)]
@@ -330,7 +340,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                 raise SearchTreeFull("too many nodes")
             outcomes[(i, j)] = [int(st["wins"][0]), 0, int(st["wins"][1])]
             if games is not None:
-                games[(i, j)] = {k: res[k] for k in ("outcome", "length", "moves")}
+                games[(i, j)] = {k: res[k] for k in ("outcome", "length", "moves", "opening") if k in res}
             if collect is not None:
                 if pooled:                               # one queue for all pairs: pair s owns a range of uids
                     uid = results["rows"]["game_uid"]

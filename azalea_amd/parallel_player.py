@@ -75,7 +75,8 @@ class Player:
     MATCH_CHUNK = 2                   # device_match: games per Match.play call, in units of n_games
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
-                 external_batch: bool = False, device_match: bool = False, random_reflect: bool = False):
+                 external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
+                 openings=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -98,9 +99,17 @@ class Player:
         throughput mode and of device_match (engine.FLAG_TOWER_F16: the plain-f16 tower, one MFMA per product).  A
         ValueError -- here, before any engine is made -- when "f16" is asked for but the games would run through
         the host loop or an external evaluator, or the network's shape has no plain-f16 tower (the 6x64-class fused
-        tower's shapes and the wide tower's -- 128 / 256 channels, up to 13x13 -- have one, given at least one block)."""
+        tower's shapes and the wide tower's -- 128 / 256 channels, up to 13x13 -- have one, given at least one block).
+        `openings` (NOT in the reference, whose games all start from the empty board; off by default): an opening
+        book for device_match, a list of move lists as engine.Match.set_openings takes it -- with agents[0] always
+        first, game u starts from opening u % len(openings) and its rows begin at that position.  A ValueError
+        -- here, before any engine is made -- in any other mode, or for a book the rules refuse."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
+        self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
+        if self.openings and not device_match:
+            raise ValueError("openings are a device_match option: only the device match starts its games from an "
+                             "opening book (self-play and the host loop start from the empty board)")
         self.agents = agents
         self.running = True
         self.gather = gather
@@ -108,6 +117,8 @@ class Player:
         self.device_match = bool(device_match)
         if self.device_match:
             self._match_policies()
+            if self.openings:
+                _eng.openings_check(self.agents[0].game.board_size, self.openings)
         elif self.external_batch:
             self._external_policy()
         self.random_reflect = bool(random_reflect)
@@ -463,6 +474,8 @@ class Player:
                 torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
         if match is None:                                     # (a match wants its engines ready: weights / evaluator)
             match = _eng.Match(a, b)
+            if self.openings:
+                match.set_openings(self.openings)
             self._match = (a, b, match)
         chunk = self.MATCH_CHUNK * self.n_games
         res = match.play(chunk, first_game=self._match_next, collect=True, first_mover=0)

@@ -613,6 +613,52 @@ int azx_tournament_set_harvest(azx_tournament *t, int sink_engine);
 int azx_tournament_set_first_mover(azx_tournament *t, int mode);
 int azx_tournament_rows(azx_tournament *t, int64_t *rows_out);
 
+/* ---- opening books: matches and tournaments from a set of opening positions ---------------------------------------
+ * Additions WITHIN ABI revision 7 (azx_version stays 7): callers detect them by symbol (dlsym azx_match_set_openings).
+ * NOT in the reference: its evaluation games all start from game.reset() (play_game.py:44-47).  Two greedy agents
+ * (move_sampling off: no noise, temperature 0) then play nearly the same two games over and over, and the empty Hex
+ * board favours the first mover.  With a book every game starts from a given short move sequence instead, and every
+ * opening is played with the colours both ways round.  Opt-in and off by default.
+ *
+ * Opening format: moves[o * stride + p] is the p-th move of opening o as tile + 1, in play order -- a row of a game
+ * record (azx_match_play's `moves`), so a record's prefix can be fed back; colour 1 plays the even plies.  lengths[o]
+ * moves count, 0 <= lengths[o] <= stride; 0 is the empty board.
+ *   azx_openings_check(board_size, n_openings, stride, moves, lengths, bad_opening, bad_ply)
+ *       host only (no device call).  AZX_OK when board_size is in [2, AZX_MAX_BOARD], every length is in [0, stride],
+ *       every move is in 1 .. cells, no opening plays a tile twice, and the game is UNDECIDED after every move of every
+ *       opening (a won position cannot be searched; an undecided one always has a legal move).  Else AZX_EINVAL:
+ *       azx_last_error names the opening, the ply and the reason, and *bad_opening / *bad_ply (either may be NULL)
+ *       receive the first offending opening and ply (ply = -1 for a bad length).  Both are untouched on success.
+ *       n_openings in [0, 1 << 20]; the tables may be NULL only when n_openings == 0.
+ *   azx_match_set_openings(m, n_openings, stride, moves, lengths)
+ *   azx_tournament_set_openings(t, ...)
+ *       check the arguments (null handle, n_openings outside [0, 1 << 20], stride < 0, null tables with n_openings > 0:
+ *       AZX_EINVAL before any device work), then the book as azx_openings_check does for the handle's board size, then
+ *       copy it to device memory the handle owns, until it is replaced or the handle destroyed.  n_openings == 0
+ *       clears the book.  A call that fails leaves the previous book in place.
+ * Which game plays which opening: with the alternating first mover (azx_match_set_first_mover -1, the default) game u
+ * starts from opening (u >> 1) % n_openings, so games 2j and 2j + 1 are the same opening with the two agents' colours
+ * swapped; with a fixed first mover (0 or 1) from opening u % n_openings.  The rule is keyed on the absolute game index
+ * u -- not on u - first_game, the slot or the pool size -- so a tournament pair still plays, bit for bit, the games of
+ * the match over its own range of u.  Colour-balanced pairs therefore need an EVEN first_game (first_game + s * rounds
+ * for pair s of a tournament) and an even number of games / rounds; this is not enforced.
+ * A game from an opening of length L: the stones are placed, ply = L, colour and winner as the moves leave them, both
+ * engines' trees fresh over the position's cells - L legal moves -- the state azx_reset leaves for that prefix.  The
+ * agent to move is first ^ (L & 1), `first` (the game's first mover under the rules above) owning the even plies;
+ * draws stay keyed by (engine seed + u, ply), and the temperature gate ply < exploration_depth counts from the empty
+ * board, as after azx_reset with a prefix.  Records: moves[u - first_game] begins with the L opening moves followed by
+ * the played ones and length[] is the total ply count (a voided game: L + the plies played), so a record still
+ * replays under the rules; azx_match_stats.plies counts only the moves searched and played (total length - L, summed).
+ * Harvested rows (azx_match_set_harvest) begin at ply L: length - L rows per won game, color and reward sign from the
+ * ply counted from the empty board, metric 3 on the row of ply L.
+ * With no book -- never set, or cleared -- every call enqueues the same kernels and returns the same bytes as before
+ * these entry points existed. */
+int azx_openings_check(int board_size, int n_openings, int stride, const int16_t *moves, const int32_t *lengths,
+                       int32_t *bad_opening, int32_t *bad_ply);
+int azx_match_set_openings(azx_match *m, int n_openings, int stride, const int16_t *moves, const int32_t *lengths);
+int azx_tournament_set_openings(azx_tournament *t, int n_openings, int stride, const int16_t *moves,
+                                const int32_t *lengths);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

@@ -54,7 +54,16 @@ profiler as above.
 
     python tools/bench_match.py --collect [--big-rounds 16384] [--big-slots 4096] [--repeats 3]
                                           [--player-slots 256,4096] [--chunks 1,2,4] [--host-games 2]
-One JSON line (profiles/match_rows_bench.json)."""
+One JSON line (profiles/match_rows_bench.json).
+
+`--openings N`: the match from an opening book against the same match from the empty board (nothing of the above):
+  (l) one engine.Match of two 6x64 agents, `--big-rounds` games in `--big-slots` slots, `--repeats` times alternately
+      without a book and from the first N of engine.all_openings(11, 1) (game u from opening (u >> 1) % N), medians of
+      the device time of the call and of the wall time, the spread of either, and plies per second (a game from an
+      opening is a move shorter, so games per second alone would flatter the book)
+
+    python tools/bench_match.py --openings 121 [--big-rounds 16384] [--big-slots 4096] [--repeats 3]
+One JSON line (profiles/match_openings_bench.json, when measured)."""
 import argparse
 import json
 import os
@@ -361,8 +370,44 @@ def collect_main(args):
     print(json.dumps(res))
 
 
+def openings_main(args):
+    two = agents(args.sims, 2)
+    med = statistics.median
+    spread = lambda xs: (max(xs) - min(xs)) / med(xs)
+    G, S = args.big_rounds, args.big_slots
+    book = eng.all_openings(BOARD, 1)[:args.openings]
+    res = {"board": BOARD, "net": "6x64 random-init", "sims": args.sims, "move_sampling": True, "exploration_noise": False,
+           "device": torch.cuda.get_device_name(0), "repeats": args.repeats, "games": G, "slots": S,
+           "openings": len(book), "opening_plies": 1}
+    a, b = match_engines(two, S)
+    m = eng.Match(a, b)
+    m.play(min(G, 2 * S), openings=book)                     # warm: allocator, kernel load
+    keys = ("empty_board", "book")
+    wall = {k: [] for k in keys}
+    dev = {k: [] for k in keys}
+    plies = {k: 0 for k in keys}
+    for _ in range(args.repeats):
+        for k in keys:
+            t, out = timed(lambda: m.play(G, openings=book if k == "book" else None))
+            print("match of %d games in %d slots, %s: wall %.2f s, device %.2f s, %d plies" % (
+                G, S, k, t, out["stats"]["seconds"], out["stats"]["plies"]), file=sys.stderr, flush=True)
+            wall[k].append(t)
+            dev[k].append(out["stats"]["seconds"])
+            plies[k] = out["stats"]["plies"]
+    for k in keys:
+        res[k] = {"device_seconds": dev[k], "wall_seconds": wall[k], "plies": plies[k],
+                  "games_per_sec": G / med(dev[k]), "plies_per_sec": plies[k] / med(dev[k]), "spread": spread(dev[k])}
+    res["book_over_empty_board_plies_per_sec"] = res["book"]["plies_per_sec"] / res["empty_board"]["plies_per_sec"]
+    m.close()
+    a.close()
+    b.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--openings", type=int, default=0, metavar="N",
+                    help="the match from the first N one-move openings against the match from the empty board")
     ap.add_argument("--collect", action="store_true")
     ap.add_argument("--no-harvest", action="store_true", help="--collect --trace-run: the same match without harvesting")
     ap.add_argument("--warm-games", type=int, default=-1)
@@ -385,6 +430,8 @@ def main():
     ap.add_argument("--tour-agents", type=int, default=8)
     ap.add_argument("--tour-rounds", type=int, default=20)
     args = ap.parse_args()
+    if args.openings > 0:
+        return openings_main(args)
     if args.collect:
         return collect_main(args)
     if args.external:
