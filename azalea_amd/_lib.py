@@ -151,6 +151,10 @@ SYMBOLS = {
     "azx_openings_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p, _i32p, _i32p]),
     "azx_match_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
     "azx_tournament_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
+    # playout cap randomisation of throughput self-play (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_playout_cap": (C.c_int, [_vp, C.c_double, C.c_int]),
+    "azx_playout_cap_is_full": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_double]),
+    "azx_playout_cap_stats": (C.c_int, [_vp, _i64p]),
 }
 
 class TrainConfig(C.Structure):

@@ -23,6 +23,7 @@
 #include "replay_kernels.h"
 #include "ext_kernels.h"
 #include "match_kernels.h"
+#include "playout_cap.h"
 
 #ifndef AZX_SRC_SHA
 #define AZX_SRC_SHA "unknown"      // the Makefile passes the digest of the kernel sources (profiles are keyed to it)
@@ -127,6 +128,26 @@ struct azx_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
     int32_t *stagger_ctr = nullptr;     // azx_net_eval_rows_behind's count and azx_debug_stagger's counters (4 ints)
     int64_t dbg_qcap = 0;               // azx_debug_set_queue_cap
+    // playout cap (azx_set_playout_cap): e->d carries "off" except inside the throughput self-play calls (CapScope)
+    bool cap_on = false;
+    double cap_full_prob = 1.0;
+    int cap_fast_sims = 0;
+    unsigned long long cap_base[3] = {0, 0, 0};   // CTR_CAP_* sums when the cap was last set
+};
+
+// The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
+// (azx_search, the phase API, matches) reads "off" from e->d.
+struct CapScope {
+    DevEngine &d;
+    explicit CapScope(azx_engine *e) : d(e->d) {
+        if (e->cap_on) {
+            d.cap_fast_batches = e->cap_fast_sims / e->cfg.search_batch_size + 1;   // mcts.py:268 applied to fast_simulations
+            d.cap_thr_m1 = azx_cap_threshold_m1(e->cap_full_prob);
+        }
+    }
+    ~CapScope() { d.cap_fast_batches = 0; d.cap_thr_m1 = 0u; }
+    CapScope(const CapScope &) = delete;
+    CapScope &operator=(const CapScope &) = delete;
 };
 
 template <typename T>
@@ -407,6 +428,13 @@ static int pipeline_streams(azx_engine *e) {
     return AZX_OK;
 }
 
+static std::string cap_text(const azx_engine *e) {
+    if (!e->cap_on) return "off";
+    char t[64];
+    snprintf(t, sizeof t, "%.6g/%d", e->cap_full_prob, e->cap_fast_sims);
+    return t;
+}
+
 extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
     if (!e || !buf || cap < 1) return fail(AZX_EINVAL, "null argument");
     const DevEngine &d = e->d;
@@ -434,6 +462,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " AZX_PIPELINE_STAGGER=" + (e->stagger ? "1" : "0") +
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
                        " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
+                       " cap=" + cap_text(e) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -1354,6 +1383,7 @@ extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stat
     if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
         return fail(AZX_ESTATE, "play mode needs a device evaluator");
     memset(stats, 0, sizeof *stats);
+    CapScope cap_scope(e);
     TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 16), 1));
     TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
     CounterSnap a, b;
@@ -1400,6 +1430,7 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
                       unsigned long long *rows_out) {
     DevEngine &d = e->d;
     memset(stats, 0, sizeof *stats);
+    CapScope cap_scope(e);
     const int64_t worst = min_positions + (int64_t)d.G * d.ncells;
     TRY(play_setup(e, worst, 0));
     if (e->dbg_qcap > 0)                                // tests (azx_debug_set_queue_cap): a queue too small, so that slots get parked
@@ -1892,6 +1923,45 @@ extern "C" int azx_debug_choose(azx_engine *e, int32_t *move_id, float *moves_pr
     return AZX_OK;
 }
 
+// ---- playout cap randomisation (include/azx.h; NOT the reference's behaviour) ---------------
+extern "C" int azx_playout_cap_is_full(uint64_t seed, int64_t uid, int ply, double full_prob) {
+    if (!(full_prob > 0.0 && full_prob <= 1.0)) return fail(AZX_EINVAL, "full_prob %g outside (0, 1]", full_prob);
+    if (ply < 0) return fail(AZX_EINVAL, "ply %d is negative", ply);
+    return azx_cap_is_full(seed, uid, ply, azx_cap_threshold_m1(full_prob)) ? 1 : 0;
+}
+
+extern "C" int azx_set_playout_cap(azx_engine *e, double full_prob, int fast_simulations) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (!(full_prob > 0.0 && full_prob <= 1.0))
+        return fail(AZX_EINVAL, "playout cap: full_prob %g outside (0, 1]", full_prob);
+    const bool named_clear = full_prob == 1.0 && fast_simulations == 0;
+    if (!named_clear && (fast_simulations < 1 || fast_simulations > e->cfg.simulations))
+        return fail(AZX_EINVAL, "playout cap: fast_simulations %d outside [1, simulations = %d] (0 with full_prob 1 clears the cap)",
+                    fast_simulations, e->cfg.simulations);
+    ENGINE_GUARD(e);
+    CounterSnap now;
+    TRY(snap_counters(e, &now));
+    e->cap_on = !(named_clear || (full_prob == 1.0 && fast_simulations == e->cfg.simulations));
+    e->cap_full_prob = e->cap_on ? full_prob : 1.0;
+    e->cap_fast_sims = e->cap_on ? fast_simulations : 0;
+    e->cap_base[0] = now.c[CTR_CAP_FULL];
+    e->cap_base[1] = now.c[CTR_CAP_FAST];
+    e->cap_base[2] = now.c[CTR_CAP_EMPTY];
+    return AZX_OK;
+}
+
+extern "C" int azx_playout_cap_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    CounterSnap now;
+    TRY(snap_counters(e, &now));
+    out4[0] = (int64_t)(now.c[CTR_CAP_FULL] - e->cap_base[0]);
+    out4[1] = (int64_t)(now.c[CTR_CAP_FAST] - e->cap_base[1]);
+    out4[2] = (int64_t)(now.c[CTR_CAP_EMPTY] - e->cap_base[2]);
+    out4[3] = 0;
+    return AZX_OK;
+}
+
 extern "C" int azx_debug_counters_raw(azx_engine *e, uint64_t *out, int64_t n_games) {
     if (!e || !out) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -2204,6 +2274,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (!m) return fail(AZX_EINVAL, "null match");
     if (first_game < 0 || n_games < 1) return fail(AZX_EINVAL, "first_game must be >= 0 and n_games >= 1");
     azx_engine *a = m->a, *b = m->b;
+    if (a->cap_on || b->cap_on)
+        return fail(AZX_EINVAL, "engine %s has a playout cap set: a match records one row per moved ply "
+                                "(clear it with azx_set_playout_cap(e, 1.0, 0))", a->cap_on ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2463,6 +2536,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     if (first_game < 0 || rounds < 1 || tables_per_pair < 1)
         return fail(AZX_EINVAL, "first_game must be >= 0, rounds >= 1 and tables_per_pair >= 1");
     const int K = (int)t->eng.size(), P = n_pairs, T = tables_per_pair;
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->cap_on)
+            return fail(AZX_EINVAL, "engine %d has a playout cap set: a tournament records one row per moved ply "
+                                    "(clear it with azx_set_playout_cap(e, 1.0, 0))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

@@ -58,7 +58,8 @@ struct alignas(64) GameHdr {
     int32_t gen;       // games this slot has started so far: uid = slot + n_games * gen (a fixed
                        // seed reproduces every game whatever order the GPU schedules the slots in)
     int32_t ply0;      // ply the game started from (azx_reset with a move prefix; 0 for restarts): its replay
-                       // row r was recorded at ply ply0 + r
+                       // row r was recorded at ply ply0 + r (self-play keeps each row's ply in row_meta: with a
+                       // playout cap only the full plies record a row)
     int32_t parked;    // play mode: the game is finished but the harvest queue had no room for its rows; the slot
                        // waits (active = 0) until the host has drained the queue (k_advance in unpark mode)
     int32_t pad[5];
@@ -68,6 +69,9 @@ enum {   // counters[] slots
     CTR_SELECTS = 0, CTR_SUM_DEPTH, CTR_SUM_K_INT, CTR_SUM_K_LEAF, CTR_EVALS, CTR_TERM_EVALS,
     CTR_GAMES, CTR_ERRORS, CTR_PLIES, CTR_ROWS, CTR_COUNT = 16
 };
+// playout cap (azx_set_playout_cap; counted only while the cap is on): plies searched in full, plies searched fast,
+// games harvested with no recorded row.  (Slots 10-12 belong to the AZX_STAMP_PLAY diagnostic build.)
+enum { CTR_CAP_FULL = 13, CTR_CAP_FAST = 14, CTR_CAP_EMPTY = 15 };
 
 struct DevEngine {
     int32_t N, ncells, G, bs, cap, slots;
@@ -116,7 +120,8 @@ struct DevEngine {
     float *row_prob;        // [G][ncells][AZX_CELL_STRIDE] moves_prob dense by child index
     int32_t *row_k;         // [G][ncells]
     float *row_meta;        // [G][ncells][8] per-ply search metrics of the game in progress: search_value, root
-                            // width, log-probability of the move drawn, (first-row flag), mean root-child visits,
+                            // width, log-probability of the move drawn, (the row's ply as int bits here; first-row
+                            // flag once harvested), mean root-child visits,
                             // tree nodes (search_tree.py:109-112; play_game.py:41-43 averages them per game)
     // ... and the output queue finished games are appended to (whole games only)
     int64_t q_cap;
@@ -129,6 +134,10 @@ struct DevEngine {
     float *q_meta;          // [Q][8] the rows' per-ply search metrics (AZX_ROW_METRICS floats per row)
     unsigned long long *q_count;   // [1] rows appended
     double *stat_sums;      // [G][8] per game: search_value, root_width, action_logprob, reward_last
+    // playout cap randomisation (azx_set_playout_cap; NOT the reference's behaviour).  The host hands the configured
+    // values to the launches of throughput self-play only and "off" (cap_fast_batches == 0) to every other launch.
+    int32_t cap_fast_batches;   // 0: off; else the select batches of a fast search (fast_simulations / bs + 1)
+    uint32_t cap_thr_m1;        // the ply is a full search iff azx_cap_word(seed, uid, ply) <= cap_thr_m1 (playout_cap.h)
 };
 
 // ---- wave64 reductions on DPP (no LDS crossbar round trips) ---------------------------------

@@ -20,6 +20,7 @@
 
 #include "azx_dev.h"
 #include "mcts_kernels.h"
+#include "playout_cap.h"
 
 __constant__ uint64_t c_geo[AZX_GEO_CELLS * 4];
 __constant__ float c_sqrt[AZX_SQRT_TAB];
@@ -473,8 +474,15 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     const GammaConst gconst = gamma_const(E.noise_alpha, L.gtab);
     const uint32_t noise_base = mix32(ph.k0 ^ mix32(ph.k1 + (uint32_t)ply * 0x632be5abu));
 
+    // Playout cap randomisation (azx_set_playout_cap; NOT the reference's behaviour, off unless the host hands a
+    // play-mode launch its values): one bit per (game, ply), wave-uniform, from the game's key on a stream of its own
+    // (playout_cap.h).  A fast ply runs cap_fast_batches select batches and takes no root noise; a slot whose batches
+    // are used up selects nothing and queues no rows in the move's remaining launches.
+    bool cap_full = true;
+    if (E.cap_fast_batches != 0) cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
+
     if (mode & MODE_BEGIN) {
-        batches_left = num_batches;
+        batches_left = cap_full ? num_batches : E.cap_fast_batches;
         select_count = 0;
         search_value = 0.0f;
         pending = 0;
@@ -962,7 +970,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             const int sumn = root_sumn;
             const float sq_tab = c_sqrt[sumn < AZX_SQRT_TAB ? sumn : AZX_SQRT_TAB - 1];
             float nz[SLOTS] = {};
-            const bool noisy = E.noise_scale != 0.0;
+            const bool noisy = E.noise_scale != 0.0 && cap_full;
             float Pn[SLOTS];
 #pragma unroll
             for (int s = 0; s < RS; ++s) Pn[s] = rst[s].z;
@@ -1592,17 +1600,19 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
                        nr * (AZX_CELL_STRIDE / 4));
             }
             const int64_t uid = gh->uid;
-            const int ply0 = gh->ply0;                         // row r was recorded at ply ply0 + r
+            // row r was recorded at the ply choose_body left in its metrics (ply0 + r unless a playout cap skipped plies)
+            const float4 *gms = reinterpret_cast<const float4 *>(E.row_meta) + (size_t)g * E.ncells * 2;
             for (int r = lane; r < rows; r += 64) {
                 const size_t q = (size_t)((pos + r) % (unsigned long long)E.q_cap);
-                E.q_color[q] = (ply0 + r) & 1;
+                const float4 *ms = gms + (size_t)r * 2;
+                float4 mt = ms[0];
+                const int rply = __float_as_int(mt.w);
+                E.q_color[q] = rply & 1;
                 E.q_k[q] = E.row_k[(size_t)g * E.ncells + r];
                 float rew = (float)(result - 2);               // play_game.py:64-65
-                if ((ply0 + r) & 1) rew = -rew;
+                if (rply & 1) rew = -rew;
                 E.q_reward[q] = rew;
                 E.q_uid[q] = uid;
-                const float4 *ms = reinterpret_cast<const float4 *>(E.row_meta) + ((size_t)g * E.ncells + r) * 2;
-                float4 mt = ms[0];
                 mt.w = r == 0 ? 1.0f : 0.0f;                   // marks the first row of a game
                 reinterpret_cast<float4 *>(E.q_meta)[q * 2] = mt;
                 reinterpret_cast<float4 *>(E.q_meta)[q * 2 + 1] = ms[1];
@@ -1610,9 +1620,13 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
             if (lane == 0) {
                 E.counters[(size_t)g * CTR_COUNT + CTR_GAMES] += 1ull;
                 E.counters[(size_t)g * CTR_COUNT + CTR_ROWS] += (unsigned long long)rows;
-                float last = (float)(result - 2);
-                if ((ply0 + rows - 1) & 1) last = -last;
-                E.stat_sums[(size_t)g * 8 + 3] += (double)last;       // metrics['reward']
+                if (rows > 0) {
+                    float last = (float)(result - 2);
+                    if (__float_as_int(gms[(size_t)(rows - 1) * 2].w) & 1) last = -last;
+                    E.stat_sums[(size_t)g * 8 + 3] += (double)last;   // metrics['reward']
+                } else if (E.cap_fast_batches != 0) {
+                    E.counters[(size_t)g * CTR_COUNT + CTR_CAP_EMPTY] += 1ull;   // no ply of the game was a full search
+                }
                 E.stat_sums[(size_t)g * 8 + 4] += (double)ply;        // game length from the empty board
             }
         }
@@ -1775,6 +1789,15 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
             }
         }
     }
+    // playout cap (azx_set_playout_cap): a fast ply moves the game on and records nothing
+    if (E.cap_fast_batches != 0) {
+        const bool cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
+        if (lane == 0) E.counters[(size_t)g * CTR_COUNT + (cap_full ? CTR_CAP_FULL : CTR_CAP_FAST)] += 1ull;
+        if (!cap_full) {
+            if (lane == 0) gh->move_id = chosen;
+            return;
+        }
+    }
     // replay row (play_game.py:92-94): pre-move board and moves_prob
     const int row = gh->n_rows;
     const size_t rb = ((size_t)g * E.ncells + row) * AZX_CELL_STRIDE;
@@ -1796,7 +1819,7 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         E.stat_sums[(size_t)g * 8 + 2] += (double)logp;
         // search_tree.py:109-112: width, mean child visits, nodes ever allocated, children
         float4 *meta = reinterpret_cast<float4 *>(E.row_meta) + ((size_t)g * E.ncells + row) * 2;
-        meta[0] = make_float4(sval, (float)width, logp, 0.0f);
+        meta[0] = make_float4(sval, (float)width, logp, __int_as_float(ply));   // .w: the row's ply until the harvest flags the first row there
         meta[1] = make_float4(nv_sum / (float)mk.k, (float)(th->num_nodes + th->dropped), (float)mk.k, 0.0f);
     }
 }

@@ -536,6 +536,30 @@ class Engine:
         self._check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))
         return st.as_dict()
 
+    # ---- playout cap randomisation (azx_set_playout_cap; NOT the reference's behaviour) ------------
+    def set_playout_cap(self, full_prob, fast_simulations):
+        """azx_set_playout_cap: every ply of the following play / play_device / replay_fill / play_steps calls is with
+        probability `full_prob` a full search (cfg.simulations, Dirichlet noise, one replay row) and otherwise a fast
+        one of `fast_simulations` (no noise, no row; the move is drawn as always).  search(), the phase API and
+        forward() are untouched; Match / Tournament refuse a capped engine.  ValueError, with the library's message,
+        for full_prob outside (0, 1] or fast_simulations outside [1, simulations]; the setting before stays then.
+        (1.0, simulations) and (1.0, 0) clear the cap."""
+        rc = self.L.azx_set_playout_cap(self.h, float(full_prob), int(fast_simulations))
+        if rc == -1:                # AZX_EINVAL
+            raise ValueError(self.L.azx_last_error().decode(errors="replace"))
+        check(rc)
+
+    def clear_playout_cap(self):
+        """Self-play as before set_playout_cap: the same kernels, the same bytes."""
+        check(self.L.azx_set_playout_cap(self.h, 1.0, 0))
+
+    def playout_cap_stats(self):
+        """azx_playout_cap_stats since the cap was last set: dict(full_plies, fast_plies, empty_games) -- empty_games
+        are the finished games none of whose plies was a full search (they contributed no rows)."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_playout_cap_stats(self.h, _p(out, C.c_int64)))
+        return dict(full_plies=int(out[0]), fast_plies=int(out[1]), empty_games=int(out[2]))
+
 
 def _collected(out, sink, n_rows, collect):
     """What a collecting Match / Tournament play adds to its result: the rows now in `sink`'s harvest queue."""
@@ -797,6 +821,17 @@ class Tournament:
             check(self.L.azx_tournament_rows(self.h, C.byref(rows)))
             _collected(out, self.engines[int(sink)], rows.value, collect)
         return out
+
+
+def playout_cap_is_full(seed, uid, ply, full_prob):
+    """azx_playout_cap_is_full: whether ply `ply` (from the empty board) of game `uid` of an engine created with
+    `seed` is a full search under set_playout_cap(full_prob, ...) -- the function the kernels use, on the host (no
+    GPU is needed).  ValueError for full_prob outside (0, 1] or a negative ply."""
+    L = _lib.lib()
+    rc = L.azx_playout_cap_is_full(int(seed) & 0xFFFFFFFFFFFFFFFF, int(uid), int(ply), float(full_prob))
+    if rc < 0:
+        raise ValueError(L.azx_last_error().decode(errors="replace"))
+    return bool(rc)
 
 
 def hex_replay(board_size, moves, lengths, device=0):

@@ -76,7 +76,7 @@ class Player:
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
-                 openings=None):
+                 openings=None, playout_cap=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -103,7 +103,14 @@ class Player:
         `openings` (NOT in the reference, whose games all start from the empty board; off by default): an opening
         book for device_match, a list of move lists as engine.Match.set_openings takes it -- with agents[0] always
         first, game u starts from opening u % len(openings) and its rows begin at that position.  A ValueError
-        -- here, before any engine is made -- in any other mode, or for a book the rules refuse."""
+        -- here, before any engine is made -- in any other mode, or for a book the rules refuse.
+        `playout_cap` (NOT the reference's behaviour, which searches and records every ply alike; off by default):
+        (full_prob, fast_simulations) -- playout cap randomisation (Engine.set_playout_cap, include/azx.h) for the
+        self-play engine this Player builds, device self-play or external_batch: every ply is with probability
+        full_prob a full search that records a row and otherwise a fast search of fast_simulations, without noise,
+        that records nothing.  A ValueError -- here, before any engine is made -- with device_match=True (a match
+        records one row per moved ply), when the games would run through the host loop, or for values outside
+        (0, 1] x [1, simulations]."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -128,6 +135,7 @@ class Player:
                              "through the host loop, which does not reflect")
         self._engine_flags = _eng.FLAG_RANDOM_REFLECT if self.random_reflect else 0
         self._check_tower_precision()
+        self.playout_cap = self._check_playout_cap(playout_cap)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -262,6 +270,23 @@ class Player:
                 raise ValueError("agent %d asks for tower_precision='f16', but these games run through the host loop, "
                                  "which does not launch the device tower" % i)
 
+    def _check_playout_cap(self, cap):
+        """`playout_cap` as (full_prob, fast_simulations), or None; a ValueError naming what does not hold."""
+        if cap is None:
+            return None
+        full_prob, fast = normalize_playout_cap(cap)
+        if self.device_match:
+            raise ValueError("playout_cap is a self-play option: a device match records one row per moved ply "
+                             "(engine.Match refuses an engine with a cap)")
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("playout_cap needs the games to run in a device engine (a single agent whose Policy "
+                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
+                             "which searches every ply in full")
+        if fast > pol.simulations:
+            raise ValueError("playout_cap: fast_simulations %d above the policy's simulations %d" % (fast, pol.simulations))
+        return full_prob, fast
+
     def _external_policy(self) -> Policy:
         """The Policy whose duck-typed net evaluates the pool's leaf batches (external_batch=True); a ValueError
         naming what does not hold otherwise -- there is no silent fall-back to the host loop."""
@@ -392,6 +417,8 @@ class Player:
                 num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                 flags=self._engine_flags | tower_flags(pol),
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
+            if self.playout_cap is not None:
+                self._engine.set_playout_cap(*self.playout_cap)
             self._engine_key = key
         return self._engine
 
@@ -514,6 +541,30 @@ class Player:
             eng.set_weights({k: (v.contiguous().data_ptr(), v.numel()) for k, v in sd.items()}, on_device=True)
         else:
             eng.set_weights({k: v.detach().cpu().numpy() for k, v in sd.items()})
+
+
+def normalize_playout_cap(cap):
+    """(full_prob, fast_simulations) of a pair or of a {"full_prob": ..., "fast_simulations": ...} mapping; a
+    ValueError unless full_prob is in (0, 1] and fast_simulations a whole number >= 1."""
+    try:
+        if isinstance(cap, dict):
+            if set(cap) != {"full_prob", "fast_simulations"}:
+                raise ValueError
+            full_prob, fast = cap["full_prob"], cap["fast_simulations"]
+        else:
+            full_prob, fast = cap
+        full_prob = float(full_prob)
+        if isinstance(fast, bool) or int(fast) != fast:
+            raise ValueError
+        fast = int(fast)
+    except (TypeError, ValueError, KeyError):
+        raise ValueError("playout_cap must be (full_prob, fast_simulations) or a dict with exactly these two keys, "
+                         "got %r" % (cap,)) from None
+    if not 0.0 < full_prob <= 1.0:
+        raise ValueError("playout_cap: full_prob %r outside (0, 1]" % full_prob)
+    if fast < 1:
+        raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
+    return full_prob, fast
 
 
 def _net_device(net) -> torch.device:

@@ -313,7 +313,23 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     outside every parity claim): the self-play engine of the training policy runs the plain-f16 tower, one MFMA per
     product instead of three (engine.FLAG_TOWER_F16; include/azx.h has the definition, DESIGN 7.8 the measured
     errors; the 6x64-class fused tower and the wide tower of 128 / 256 channels have one).  It sets the policy's `tower_precision` for its self-play side only (apply_selfplay_tower); the training
-    step, the checkpoints and Policy's own parity-mode engine are untouched."""
+    step, the checkpoints and Policy's own parity-mode engine are untouched.
+
+    config["playout_cap"] = {"full_prob": p, "fast_simulations": n} (default absent; NOT the reference's behaviour, and
+    outside every parity claim): playout cap randomisation of self-play (Wu 2019; Engine.set_playout_cap, include/azx.h
+    has the definition).  It goes to the one Player built here (Player(playout_cap=...)), so the lock-step ranks and
+    the actors play under it too: every ply is with probability p a full search that records a training row, and
+    otherwise a search of n simulations without Dirichlet noise that records nothing.  exploration_depth and the
+    temperature are untouched.  A ValueError, before anything is built, for values outside (0, 1] x [1, simulations];
+    Player refuses it where the games would run through the host loop.  Its effect on playing strength and on
+    training efficiency is not measured."""
+    playout_cap = None
+    if config.get("playout_cap") is not None:
+        from .parallel_player import normalize_playout_cap
+        playout_cap = normalize_playout_cap(config["playout_cap"])
+        if playout_cap[1] > policy.simulations:
+            raise ValueError("config['playout_cap']: fast_simulations %d above simulations %d"
+                             % (playout_cap[1], policy.simulations))
     apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])
@@ -350,7 +366,12 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     lockstep_role = ("leader" if leader else "follower") if mode == "lockstep" else None
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
-                    random_reflect=bool(config.get("random_reflect", False)))
+                    random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap)
+    if leader:
+        logging.info("playout cap randomisation (config['playout_cap']): %s",
+                     "off" if playout_cap is None else
+                     "on -- NOT the reference's behaviour: a ply is a full search with probability %g, else %d "
+                     "simulations without noise and without a training row" % playout_cap)
     if mode == "actor_learner" and player._device_policy() is None:
         raise ValueError("selfplay_mode 'actor_learner' needs a Policy that holds a HexNetwork; use 'lockstep'")
     from_ring = False

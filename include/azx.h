@@ -425,6 +425,46 @@ int azx_replay_set_mover_view(azx_engine *e, int on);
  * (dlsym azx_replay_set_reflect). */
 int azx_replay_set_reflect(azx_engine *e, int on, uint64_t seed);
 
+/* Playout cap randomisation for throughput self-play (Wu 2019, "Accelerating Self-Play Learning in Go", 3.1).  NOT the
+ * reference's behaviour (off by default, outside every parity claim): the reference searches every ply with
+ * `simulations` and records every ply.  With the cap set, every ply of a self-play game is with probability full_prob
+ * a FULL search -- exactly today's ply: cfg.simulations / search_batch_size + 1 select batches, Dirichlet noise, one
+ * replay row -- and otherwise a FAST search of fast_simulations / search_batch_size + 1 batches (the reference's
+ * rounding rule, mcts.py:268, applied to fast_simulations) that takes NO Dirichlet noise whatever noise_scale is,
+ * writes NO replay row and no per-row metrics, and only keeps the game moving: its move is drawn exactly as a full
+ * ply's (temperature while ply < exploration_depth, then the most-visited child, from the same Philox words) and the
+ * tree is carried to the next ply as always.
+ *   The draw is one bit per ply, a pure function of (cfg.seed, the game's uid, the ply counted from the empty board),
+ * from the game's key on a stream of its own: nothing of it is shared with the Dirichlet words, the reflection bits
+ * or the move draw, and it does not depend on the slot, n_games, the half-pool or the launch.  The ply is full iff
+ * the 32-bit word is below the integer threshold ceil(full_prob * 2^32), clamped to [1, 2^32]; device and host use
+ * the same function, azx_playout_cap_is_full is it on the host.
+ *   It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move launches,
+ * the pipelined half-pools, a registered external evaluator) and to nothing else: azx_search, the phase API and
+ * azx_forward run cfg.simulations whatever the cap is, and azx_match_play / azx_tournament_play refuse an engine whose
+ * cap is on with AZX_EINVAL before touching any engine (their harvest assumes one row per moved ply).
+ *   A game's recorded rows stay contiguous with plies ascending; colour and the sign of the reward come from each
+ * row's own ply; row metric 3 flags the game's first RECORDED row; search_value is normalised by the full search's
+ * select count.  A game with no full ply counts in azx_play_stats.games and sum_game_length and contributes no rows
+ * and nothing to sum_reward_last.  plies, selects and evals count every ply; sum_search_value, sum_root_width and
+ * sum_action_logprob cover the recorded plies only (they stay sums over the rows).
+ *   full_prob must be in (0, 1] and fast_simulations in [1, cfg.simulations]; anything else is AZX_EINVAL before any
+ * device work and leaves the previous setting in place.  (1.0, cfg.simulations) clears the cap, and so does the named
+ * form (1.0, 0).  With the cap never set, or cleared, every call launches the same kernels and returns the same bytes
+ * as without this entry point.  May be called between calls, for any evaluator.  azx_kernel_info reports cap=off or
+ * cap=<full_prob>/<fast_simulations>.  A play call waits for recorded rows: with a full_prob so small that hardly any
+ * ply is full, give azx_play / azx_play_device / azx_replay_fill a max_plies.  Playing strength and training
+ * efficiency under a cap are not measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_playout_cap). */
+int azx_set_playout_cap(azx_engine *e, double full_prob, int fast_simulations);
+/* host only, no device call: 1 if ply `ply` of game `uid` under engine seed `seed` is a full search at full_prob, else
+ * 0; AZX_EINVAL (negative) for full_prob outside (0, 1] or ply < 0. */
+int azx_playout_cap_is_full(uint64_t seed, int64_t uid, int ply, double full_prob);
+/* out4 = {full plies, fast plies, games harvested with zero rows, 0}, counted since the cap was last set (all 0 while
+ * it has never been set). */
+int azx_playout_cap_stats(azx_engine *e, int64_t out4[4]);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,
