@@ -155,6 +155,12 @@ SYMBOLS = {
     "azx_set_playout_cap": (C.c_int, [_vp, C.c_double, C.c_int]),
     "azx_playout_cap_is_full": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_double]),
     "azx_playout_cap_stats": (C.c_int, [_vp, _i64p]),
+    # resignation for throughput self-play (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_resign": (C.c_int, [_vp, C.c_double, C.c_int, C.c_double]),
+    "azx_clear_resign": (C.c_int, [_vp]),
+    "azx_resign_is_exempt": (C.c_int, [C.c_uint64, C.c_int64, C.c_double]),
+    "azx_resign_stats": (C.c_int, [_vp, _i64p]),
+    "azx_resign_value": (C.c_int, [_vp, C.POINTER(C.c_float)]),
 }
 
 class TrainConfig(C.Structure):

@@ -24,6 +24,7 @@
 #include "ext_kernels.h"
 #include "match_kernels.h"
 #include "playout_cap.h"
+#include "resign.h"
 
 #ifndef AZX_SRC_SHA
 #define AZX_SRC_SHA "unknown"      // the Makefile passes the digest of the kernel sources (profiles are keyed to it)
@@ -133,10 +134,14 @@ struct azx_engine {
     double cap_full_prob = 1.0;
     int cap_fast_sims = 0;
     unsigned long long cap_base[3] = {0, 0, 0};   // CTR_CAP_* sums when the cap was last set
+    // resignation (azx_set_resign): handed to the same launches, by the same scope
+    bool resign_on = false;
+    double resign_thr = -1.0, resign_keep = 0.0;
+    int resign_min_ply = 0;
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
-// (azx_search, the phase API, matches) reads "off" from e->d.
+// (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) travels the same way.
 struct CapScope {
     DevEngine &d;
     explicit CapScope(azx_engine *e) : d(e->d) {
@@ -144,8 +149,17 @@ struct CapScope {
             d.cap_fast_batches = e->cap_fast_sims / e->cfg.search_batch_size + 1;   // mcts.py:268 applied to fast_simulations
             d.cap_thr_m1 = azx_cap_threshold_m1(e->cap_full_prob);
         }
+        if (e->resign_on) {
+            d.resign_mode = e->resign_keep > 0.0 ? AZX_RESIGN_DRAW_EXEMPT : AZX_RESIGN_NONE_EXEMPT;
+            d.resign_min_ply = e->resign_min_ply;
+            d.resign_thr = (float)e->resign_thr;
+            d.resign_keep_m1 = e->resign_keep > 0.0 ? azx_resign_threshold_m1(e->resign_keep) : 0u;
+        }
     }
-    ~CapScope() { d.cap_fast_batches = 0; d.cap_thr_m1 = 0u; }
+    ~CapScope() {
+        d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
+        d.resign_mode = AZX_RESIGN_OFF; d.resign_min_ply = 0; d.resign_thr = 0.0f; d.resign_keep_m1 = 0u;
+    }
     CapScope(const CapScope &) = delete;
     CapScope &operator=(const CapScope &) = delete;
 };
@@ -272,6 +286,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.ev_board, E * AZX_CELL_STRIDE); A(d.ev_src, E); A(d.ev_flip, E);
     A(d.ev_value, E); A(d.ev_prior, E * AZX_CELL_STRIDE); A(d.n_eval, 4);   // (n_eval[1]: the second half-pool's count)
     A(d.counters, G * CTR_COUNT); A(d.q_count, 2); A(d.stat_sums, G * 8);
+    A(d.resign_ctr, G * RS_COUNT);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
     A(e->g_rv, G); A(e->g_rw, G); A(e->g_sv, G);
@@ -409,6 +424,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     if (v.noise) v.noise += b * d.n_select * d.noise_stride;
     v.counters += b * CTR_COUNT;
     v.stat_sums += b * 8;
+    v.resign_ctr += b * RS_COUNT;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
     if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
     if (v.row_k) v.row_k += b * nc;
@@ -426,6 +442,13 @@ static int pipeline_streams(azx_engine *e) {
     if (!e->ev_stagger) HIPCHECK(hipEventCreateWithFlags(&e->ev_stagger, hipEventDisableTiming));
     if (!e->stagger_ctr) TRY(dev_alloc(e, &e->stagger_ctr, 4));     // (zeroed on the engine stream, where half A uses it)
     return AZX_OK;
+}
+
+static std::string resign_text(const azx_engine *e) {
+    if (!e->resign_on) return "off";
+    char t[96];
+    snprintf(t, sizeof t, "%.6g/%d/%.6g", e->resign_thr, e->resign_min_ply, e->resign_keep);
+    return t;
 }
 
 static std::string cap_text(const azx_engine *e) {
@@ -463,6 +486,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
                        " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
                        " cap=" + cap_text(e) +
+                       " resign=" + resign_text(e) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -1962,6 +1986,75 @@ extern "C" int azx_playout_cap_stats(azx_engine *e, int64_t out4[4]) {
     return AZX_OK;
 }
 
+// ---- resignation for throughput self-play (include/azx.h; NOT the reference's behaviour) ------
+static const char *resign_keep_problem(double keep_prob) {
+    return (std::isfinite(keep_prob) && keep_prob >= 0.0 && keep_prob <= 1.0) ? nullptr : "keep_prob outside [0, 1]";
+}
+
+extern "C" int azx_resign_is_exempt(uint64_t seed, int64_t uid, double keep_prob) {
+    if (resign_keep_problem(keep_prob)) return fail(AZX_EINVAL, "resign: keep_prob %g outside [0, 1]", keep_prob);
+    if (keep_prob == 0.0) return 0;
+    return azx_resign_exempt(seed, uid, AZX_RESIGN_DRAW_EXEMPT, azx_resign_threshold_m1(keep_prob)) ? 1 : 0;
+}
+
+// the games in progress leave the statistics, which start again from zero
+static int resign_restart_stats(azx_engine *e) {
+    azx_launch_resign_mark(e->d, e->stream);
+    HIPCHECK(hipMemsetAsync(e->d.resign_ctr, 0, (size_t)e->d.G * RS_COUNT * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
+}
+
+extern "C" int azx_set_resign(azx_engine *e, double threshold, int min_ply, double keep_prob) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (!(std::isfinite(threshold) && threshold >= -1.0 && threshold <= 1.0))
+        return fail(AZX_EINVAL, "resign: threshold %g outside [-1, 1]", threshold);
+    if (min_ply < 0) return fail(AZX_EINVAL, "resign: min_ply %d is negative", min_ply);
+    if (resign_keep_problem(keep_prob)) return fail(AZX_EINVAL, "resign: keep_prob %g outside [0, 1]", keep_prob);
+    ENGINE_GUARD(e);
+    TRY(resign_restart_stats(e));
+    e->resign_on = true;
+    e->resign_thr = threshold;
+    e->resign_min_ply = min_ply;
+    e->resign_keep = keep_prob;
+    return AZX_OK;
+}
+
+extern "C" int azx_clear_resign(azx_engine *e) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    ENGINE_GUARD(e);
+    e->resign_on = false;
+    e->resign_thr = -1.0;
+    e->resign_min_ply = 0;
+    e->resign_keep = 0.0;
+    return AZX_OK;
+}
+
+extern "C" int azx_resign_stats(azx_engine *e, int64_t out8[8]) {
+    if (!e || !out8) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * RS_COUNT);
+    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.resign_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < 8; ++j) out8[j] = 0;
+    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
+        for (int j = 0; j < RS_COUNT; ++j) out8[j] += (int64_t)hc[g * RS_COUNT + j];
+    out8[7] = 0;
+    return AZX_OK;
+}
+
+extern "C" int azx_resign_value(azx_engine *e, float *v) {
+    if (!e || !v) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    azx_launch_resign_value(e->d, e->g_sv, e->stream);      // (g_sv: azx_get_root's per-slot float scratch)
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(v, e->g_sv, (size_t)e->d.G * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
+}
+
 extern "C" int azx_debug_counters_raw(azx_engine *e, uint64_t *out, int64_t n_games) {
     if (!e || !out) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -2277,6 +2370,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (a->cap_on || b->cap_on)
         return fail(AZX_EINVAL, "engine %s has a playout cap set: a match records one row per moved ply "
                                 "(clear it with azx_set_playout_cap(e, 1.0, 0))", a->cap_on ? "a" : "b");
+    if (a->resign_on || b->resign_on)
+        return fail(AZX_EINVAL, "engine %s has resignation set: a match plays every game to the end and records one "
+                                "row per moved ply (clear it with azx_clear_resign)", a->resign_on ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2540,6 +2636,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->cap_on)
             return fail(AZX_EINVAL, "engine %d has a playout cap set: a tournament records one row per moved ply "
                                     "(clear it with azx_set_playout_cap(e, 1.0, 0))", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->resign_on)
+            return fail(AZX_EINVAL, "engine %d has resignation set: a tournament plays every game to the end and "
+                                    "records one row per moved ply (clear it with azx_clear_resign)", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

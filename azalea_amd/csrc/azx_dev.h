@@ -62,8 +62,17 @@ struct alignas(64) GameHdr {
                        // playout cap only the full plies record a row)
     int32_t parked;    // play mode: the game is finished but the harvest queue had no room for its rows; the slot
                        // waits (active = 0) until the host has drained the queue (k_advance in unpark mode)
-    int32_t pad[5];
+    int32_t rs_state;  // resignation (azx_set_resign), one word so that a slot starting a game clears it with one store:
+                       // AZX_RS_CROSS bits: exempt game, 1 + the first ply at which the resign rule's other conditions
+                       // held (0: none yet); AZX_RS_SKIP: the game was in progress when azx_set_resign was called and
+                       // counts in no resign statistic; AZX_RS_DONE: the game ended by resignation (a parked slot's
+                       // harvest needs it)
+    int32_t pad[4];
 };
+#define AZX_RS_CROSS 0xFFFF
+#define AZX_RS_SKIP 0x10000
+#define AZX_RS_DONE 0x20000
+#define AZX_MOVE_RESIGN (-2)   // GameHdr.move_id: the mover resigns (choose_body to advance_body, play mode 1 only)
 
 enum {   // counters[] slots
     CTR_SELECTS = 0, CTR_SUM_DEPTH, CTR_SUM_K_INT, CTR_SUM_K_LEAF, CTR_EVALS, CTR_TERM_EVALS,
@@ -138,7 +147,15 @@ struct DevEngine {
     // values to the launches of throughput self-play only and "off" (cap_fast_batches == 0) to every other launch.
     int32_t cap_fast_batches;   // 0: off; else the select batches of a fast search (fast_simulations / bs + 1)
     uint32_t cap_thr_m1;        // the ply is a full search iff azx_cap_word(seed, uid, ply) <= cap_thr_m1 (playout_cap.h)
+    // resignation (azx_set_resign; NOT the reference's behaviour), handed to the same launches only: resign_mode is
+    // AZX_RESIGN_OFF in every other launch (resign.h)
+    int32_t resign_mode;
+    int32_t resign_min_ply;
+    float resign_thr;           // the mover resigns iff root.total_value / root.num_visits < resign_thr
+    uint32_t resign_keep_m1;    // the game is exempt iff azx_resign_word(seed, uid) <= resign_keep_m1 (mode DRAW_EXEMPT)
+    unsigned long long *resign_ctr;   // [G][RS_COUNT] per game (no atomics), azx_resign_stats' array; the host sums
 };
+enum { RS_RESIGNED = 0, RS_PLAYED_OUT, RS_EXEMPT, RS_EXEMPT_CROSSED, RS_FALSE_POS, RS_SUM_RESIGN_PLY, RS_SUM_SAVED, RS_COUNT = 8 };
 
 // ---- wave64 reductions on DPP (no LDS crossbar round trips) ---------------------------------
 // row_shr 1/2/4/8 build an inclusive scan inside each 16-lane row, row_bcast15 / row_bcast31

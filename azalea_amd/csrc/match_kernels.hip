@@ -76,6 +76,7 @@ __device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t
         gh->n_rows = 0;
         gh->ply0 = ply;
         gh->parked = 0;
+        gh->rs_state = 0;
         if (uid >= 0) gh->uid = uid;
         if (opened) E.thdr[g].arena = 0;
     }

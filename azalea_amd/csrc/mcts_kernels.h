@@ -19,6 +19,9 @@ bool azx_launch_play(const DevEngine &E, int num_batches, int steps, hipStream_t
 void azx_launch_reset(const DevEngine &E, const int32_t *slots, int n_slots, const int32_t *moves,
                       const int32_t *n_moves, int stride, int assign_uid, hipStream_t st);
 void azx_launch_advance(const DevEngine &E, const int32_t *move_ids, int play_mode, hipStream_t st);
+// resignation (azx_set_resign): the statistic of every slot's current root; mark the games in progress as uncounted
+void azx_launch_resign_value(const DevEngine &E, float *out, hipStream_t st);
+void azx_launch_resign_mark(const DevEngine &E, hipStream_t st);
 void azx_launch_gather_root(const DevEngine &E, int32_t *k_out, int32_t *legal, float *cv, float *cw,
                             float *cp, float *rv, float *rw, int32_t *nn, float *sv, hipStream_t st);
 void azx_launch_choose(const DevEngine &E, hipStream_t st);

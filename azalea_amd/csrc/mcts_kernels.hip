@@ -21,6 +21,7 @@
 #include "azx_dev.h"
 #include "mcts_kernels.h"
 #include "playout_cap.h"
+#include "resign.h"
 
 __constant__ uint64_t c_geo[AZX_GEO_CELLS * 4];
 __constant__ float c_sqrt[AZX_SQRT_TAB];
@@ -413,8 +414,10 @@ __device__ __forceinline__ void compact_tree(const DevEngine &E, int g, TreeHdr 
 
 #ifdef AZX_WPE
 #define AZX_MCTS_ATTR __attribute__((amdgpu_waves_per_eu(AZX_WPE, AZX_WPE)))
+#define AZX_PLAY_ATTR(S) AZX_MCTS_ATTR
 #else
 #define AZX_MCTS_ATTR
+#define AZX_PLAY_ATTR(S) __attribute__((amdgpu_waves_per_eu((S) == 2 ? 4 : 2)))     // k_play, see there
 #endif
 template <int SLOTS, bool FAST>
 __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int num_batches, bool stage_tables = true) {
@@ -1457,6 +1460,7 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
         gh->n_rows = 0;
         gh->parked = 0;
         gh->ply0 = ply;
+        gh->rs_state = 0;
         if (assign_uid) { gh->uid = game_uid(E, g, gh->gen); gh->gen += 1; }
         th->arena = 0;
     }
@@ -1469,6 +1473,30 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
 // kept subtree compacted into the other arena (the reference never reclaims nodes).
 // In play mode a finished game is appended to the output queue and the slot restarts.
 // ============================================================================================
+// resignation statistics (azx_resign_stats) of a game being harvested, over the games that started after
+// azx_set_resign; one lane, from the header alone, after the rows are copied and before the slot restarts
+__device__ __forceinline__ void resign_count(const DevEngine &E, int g, const GameHdr *gh) {
+    const int st = gh->rs_state;
+    if (st & AZX_RS_SKIP) return;
+    const int winner = gh->winner, ply = gh->ply;
+    unsigned long long *rs = E.resign_ctr + (size_t)g * RS_COUNT;
+    const int cross = st & AZX_RS_CROSS;
+    if (st & AZX_RS_DONE) {
+        rs[RS_RESIGNED] += 1ull;
+        rs[RS_SUM_RESIGN_PLY] += (unsigned long long)ply;
+    } else if (!azx_resign_exempt(E.seed, gh->uid, E.resign_mode, E.resign_keep_m1)) {
+        rs[RS_PLAYED_OUT] += 1ull;
+    } else {
+        rs[RS_EXEMPT] += 1ull;
+        if (cross > 0) {
+            rs[RS_EXEMPT_CROSSED] += 1ull;
+            rs[RS_SUM_SAVED] += (unsigned long long)(ply - (cross - 1));
+            // the mover of ply p is colour 1 + (p & 1): a win of the would-be resigner is a false positive
+            if (winner == 1 + ((cross - 1) & 1)) rs[RS_FALSE_POS] += 1ull;
+        }
+    }
+}
+
 template <int SLOTS>
 __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const int32_t *move_ids, int play_mode) {
     __shared__ int sh_old[64];         // compaction: old first-child ids of a group's parents, by rank
@@ -1481,7 +1509,9 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
     if (play_mode == 2 ? !parked : !gh->active) return;
     int status = th->status;
     const int mid = move_ids ? move_ids[g] : gh->move_id;
-    if (!parked && mid < 0 && status == 0) return;
+    // resignation (azx_set_resign): choose_body left the sentinel; only throughput self-play (play mode 1) ever sees it
+    const bool resign = !parked && status == 0 && play_mode == 1 && mid == AZX_MOVE_RESIGN;
+    if (!parked && mid < 0 && status == 0 && !resign) return;
 
     HexWave<SLOTS> h;
     h.load(E.cells + (size_t)g * SLOTS * 64, lane);
@@ -1491,7 +1521,18 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
     int ply = gh->ply;
     bool finished = parked, errored = !parked && status != 0;
 
-    if (!errored && !parked) {
+    if (resign) {
+        // no stone and no tree move: the game ends here and the colour that did not resign has won.  The winner goes
+        // into the header before the harvest, so that a slot parked below unparks with it.
+        h.winner = 3 - h.color;
+        finished = true;
+        if (lane == 0) {
+            gh->winner = h.winner;
+            gh->move_id = -1;
+            gh->rs_state |= AZX_RS_DONE;
+            E.counters[(size_t)g * CTR_COUNT + CTR_PLIES] += 1ull;    // the ply was searched
+        }
+    } else if (!errored && !parked) {
         const Masks<SLOTS> mk = make_masks<SLOTS>(h, lane, E.ncells);
         // the mid-th legal move in ascending tile order (search_tree.py:306)
         int cell = -1;
@@ -1638,12 +1679,15 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
         z.clear();
         z.store(E.cells + (size_t)g * SLOTS * 64, lane);
         if (lane == 0) {
+            // (the header still holds the finished game: its winner, its length, its resign marks)
+            if (finished && E.resign_mode != AZX_RESIGN_OFF) resign_count(E, g, gh);
             gh->color = 1;
             gh->winner = 0;
             gh->ply = 0;
             gh->move_id = -1;
             gh->n_rows = 0;
             gh->ply0 = 0;
+            gh->rs_state = 0;
             if (parked) { gh->parked = 0; gh->active = 1; }
             gh->uid = game_uid(E, g, gh->gen);
             gh->gen += 1;
@@ -1697,6 +1741,51 @@ __global__ __launch_bounds__(64) void k_gather_root(DevEngine E, int32_t *k_out,
         if (nn) nn[g] = th->num_nodes;
         if (sv) sv[g] = th->search_value;
     }
+}
+
+// The resign statistic (azx_set_resign, azx_resign_value): the root's mean backed-up value for the player to move,
+// one IEEE float32 division.  Precondition: rootn.nv > 0 -- an unvisited root gives NaN or an infinity.  The rule
+// tests num_visits > 0 itself, and row metric 7 is written after a ply's search only, where the root has been visited
+// (choose_body returns early for an unevaluated root); azx_resign_value's kernel checks before it divides.
+__device__ __forceinline__ float resign_value(const Node &rootn) {
+    return rootn.tv / rootn.nv;
+}
+
+__global__ void k_resign_value(DevEngine E, float *out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    const TreeHdr *th = E.thdr + g;
+    const Node *arena = E.arena[th->arena] + (size_t)g * E.cap;
+    const Node rootn = arena[th->root_id];
+    // azx_resign_value: NaN where the root is unevaluated or unvisited
+    out[g] = (rootn.link == AZX_LINK_UNEVAL || !(rootn.nv > 0.0f)) ? __int_as_float(0x7fc00000) : resign_value(rootn);
+}
+
+// azx_set_resign: the games in progress (a ply played, a row written, or parked) count in no resign statistic
+__global__ void k_resign_mark(DevEngine E) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    GameHdr *gh = E.ghdr + g;
+    gh->rs_state = (gh->ply != gh->ply0 || gh->n_rows != 0 || gh->parked != 0) ? AZX_RS_SKIP : 0;
+}
+
+// Resignation (azx_set_resign; NOT the reference's behaviour): judged by one lane where the drawn move is stored, so a
+// resigning ply has consumed the same Philox words and writes the same row as the ply that plays on.  Returns the move
+// id to store (the drawn child, or AZX_MOVE_RESIGN) and in *v row metric 7 (0 while resignation is off); marks an
+// exempt game's crossing.
+__device__ __forceinline__ int resign_judge(const DevEngine &E, int g, GameHdr *gh, const TreeHdr *th, int ply,
+                                            int chosen, float *v) {
+    *v = 0.0f;
+    if (E.resign_mode == AZX_RESIGN_OFF) return chosen;
+    const Node rootn = (E.arena[th->arena] + (size_t)g * E.cap)[th->root_id];
+    const float rv = resign_value(rootn);
+    *v = rv;
+    if (ply >= E.resign_min_ply && rootn.nv > 0.0f && rv < E.resign_thr) {
+        if (!azx_resign_exempt(E.seed, gh->uid, E.resign_mode, E.resign_keep_m1)) return AZX_MOVE_RESIGN;
+        const int st = gh->rs_state;
+        if ((st & AZX_RS_CROSS) == 0) gh->rs_state = st | (ply + 1);      // the exempt game's crossing
+    }
+    return chosen;
 }
 
 // ============================================================================================
@@ -1794,7 +1883,10 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         const bool cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
         if (lane == 0) E.counters[(size_t)g * CTR_COUNT + (cap_full ? CTR_CAP_FULL : CTR_CAP_FAST)] += 1ull;
         if (!cap_full) {
-            if (lane == 0) gh->move_id = chosen;
+            if (lane == 0) {
+                float rs_v;
+                gh->move_id = resign_judge(E, g, gh, th, ply, chosen, &rs_v);
+            }
             return;
         }
     }
@@ -1811,7 +1903,8 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
     if (lane == 0) {
         E.row_k[(size_t)g * E.ncells + row] = mk.k;
         gh->n_rows = row + 1;
-        gh->move_id = chosen;
+        float rs_v;
+        gh->move_id = resign_judge(E, g, gh, th, ply, chosen, &rs_v);
         const float logp = __logf(chosen_w / tot);
         const float sval = th->search_value / (float)E.selects_per_search;   // mcts.py:291 (as azx_get_root reports it)
         E.stat_sums[(size_t)g * 8 + 0] += (double)sval;
@@ -1820,7 +1913,7 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         // search_tree.py:109-112: width, mean child visits, nodes ever allocated, children
         float4 *meta = reinterpret_cast<float4 *>(E.row_meta) + ((size_t)g * E.ncells + row) * 2;
         meta[0] = make_float4(sval, (float)width, logp, __int_as_float(ply));   // .w: the row's ply until the harvest flags the first row there
-        meta[1] = make_float4(nv_sum / (float)mk.k, (float)(th->num_nodes + th->dropped), (float)mk.k, 0.0f);
+        meta[1] = make_float4(nv_sum / (float)mk.k, (float)(th->num_nodes + th->dropped), (float)mk.k, rs_v);
     }
 }
 
@@ -1837,8 +1930,14 @@ __global__ __launch_bounds__(64) void k_choose(DevEngine E) {
 // but the harvest queue's counter is shared between games, so there is no reason to line all games
 // up at three launch boundaries per move: each wave runs its own search -> choose -> advance loop,
 // and the harvest copies and arena compactions of some games overlap the searches of the others.
+// (The occupancy the kernel has had since the playout cap -- 4 waves per SIMD on boards up to 11x11, 2 above -- is
+// pinned: left to itself the register allocator trades it away for two registers of scheduling slack when the move
+// draw or the game step grows by a few instructions.  profiles/resign_resources.txt: no VGPR spilled, scratch unchanged.
+// k_play<2> now sits exactly ON the 128-VGPR limit of 4 waves: with the bound stated, anything further added to the
+// play loop -- here, in choose_body or in advance_body -- spills VGPRs to scratch instead of losing occupancy.  Check
+// the compiler's resource remarks (VGPRs Spill, ScratchSize) after any such change, and make room first.)
 template <int SLOTS>
-__global__ __launch_bounds__(64) AZX_MCTS_ATTR void k_play(DevEngine E, int num_batches, int steps) {
+__global__ __launch_bounds__(64) AZX_PLAY_ATTR(SLOTS) void k_play(DevEngine E, int num_batches, int steps) {
 #ifdef AZX_STAMP_PLAY     // diagnostic build: per-wave cycles in the search, the move draw and the game step (slots 10-12)
     unsigned long long tp_[3] = {0, 0, 0};
 #define TP(i, stmt) { const unsigned long long a_ = __builtin_amdgcn_s_memtime(); stmt; tp_[i] += __builtin_amdgcn_s_memtime() - a_; }
@@ -2072,6 +2171,14 @@ void azx_launch_reset(const DevEngine &E, const int32_t *slots, int n_slots, con
 #define CALL(S) hipLaunchKernelGGL((k_reset<S>), dim3(n_slots), dim3(64), 0, st, E, slots, n_slots, moves, n_moves, stride, assign_uid)
     DISPATCH_SLOTS(E.slots, CALL);
 #undef CALL
+}
+
+void azx_launch_resign_value(const DevEngine &E, float *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_resign_value, dim3((E.G + 255) / 256), dim3(256), 0, st, E, out);
+}
+
+void azx_launch_resign_mark(const DevEngine &E, hipStream_t st) {
+    hipLaunchKernelGGL(k_resign_mark, dim3((E.G + 255) / 256), dim3(256), 0, st, E);
 }
 
 void azx_launch_advance(const DevEngine &E, const int32_t *move_ids, int play_mode, hipStream_t st) {

@@ -390,7 +390,7 @@ class Engine:
 
     def kernel_info(self):
         """azx_kernel_info: which kernels this engine launches (and the diagnostic switches it was created under)."""
-        buf = C.create_string_buffer(1024)
+        buf = C.create_string_buffer(2048)
         n = self.L.azx_kernel_info(self.h, buf, len(buf))
         if n < 0:
             check(n)
@@ -559,6 +559,44 @@ class Engine:
         out = np.zeros(4, np.int64)
         check(self.L.azx_playout_cap_stats(self.h, _p(out, C.c_int64)))
         return dict(full_plies=int(out[0]), fast_plies=int(out[1]), empty_games=int(out[2]))
+
+    # ---- resignation with no-resign calibration games (azx_set_resign; NOT the reference's behaviour) ------------
+    def set_resign(self, threshold, min_ply=0, keep_prob=0.1):
+        """azx_set_resign: in the following play / play_device / replay_fill / play_steps calls the mover of a game
+        that is not exempt resigns at a ply >= `min_ply` whose root value v = root_value / root_visits (the mover's
+        view, one float32 division) is below `threshold`; the game ends there, lost by the resigner, and is harvested
+        like any finished game.  A share `keep_prob` of the games -- a pure function of (seed, uid),
+        resign_is_exempt() -- is exempt, plays to the end and only remembers its first crossing.  Row metric 7 carries
+        v while resignation is set.  search(), the phase API and advance() never resign; Match / Tournament refuse a
+        resigning engine.  ValueError, with the library's message, for a threshold outside [-1, 1], a negative min_ply
+        or a keep_prob outside [0, 1]; the setting before stays then.  Zeroes resign_stats()."""
+        rc = self.L.azx_set_resign(self.h, float(threshold), int(min_ply), float(keep_prob))
+        if rc == -1:                # AZX_EINVAL
+            raise ValueError(self.L.azx_last_error().decode(errors="replace"))
+        check(rc)
+
+    def clear_resign(self):
+        """Self-play as before set_resign: the same kernels, the same bytes."""
+        check(self.L.azx_clear_resign(self.h))
+
+    RESIGN_STATS = ("resigned", "played_out", "exempt", "exempt_crossed", "false_positives", "sum_resign_ply",
+                    "sum_plies_saved")
+
+    def resign_stats(self):
+        """azx_resign_stats since the last set_resign, over the games that started and finished after it:
+        dict(resigned, played_out, exempt, exempt_crossed, false_positives, sum_resign_ply, sum_plies_saved) --
+        false_positives are the exempt games whose crossing mover went on to win, sum_plies_saved the plies between
+        the exempt games' crossings and their ends."""
+        out = np.zeros(8, np.int64)
+        check(self.L.azx_resign_stats(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(self.RESIGN_STATS)}
+
+    def resign_values(self):
+        """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
+        is unevaluated or unvisited), by the device function the move draw uses."""
+        out = np.zeros(self.G, np.float32)
+        check(self.L.azx_resign_value(self.h, _p(out, C.c_float)))
+        return out
 
 
 def _collected(out, sink, n_rows, collect):
@@ -829,6 +867,17 @@ def playout_cap_is_full(seed, uid, ply, full_prob):
     GPU is needed).  ValueError for full_prob outside (0, 1] or a negative ply."""
     L = _lib.lib()
     rc = L.azx_playout_cap_is_full(int(seed) & 0xFFFFFFFFFFFFFFFF, int(uid), int(ply), float(full_prob))
+    if rc < 0:
+        raise ValueError(L.azx_last_error().decode(errors="replace"))
+    return bool(rc)
+
+
+def resign_is_exempt(seed, uid, keep_prob):
+    """azx_resign_is_exempt: whether game `uid` of an engine created with `seed` is exempt from resigning under
+    set_resign(..., keep_prob=keep_prob) -- the function the kernels use, on the host (no GPU is needed).  ValueError
+    for a keep_prob that is not a finite number in [0, 1]."""
+    L = _lib.lib()
+    rc = L.azx_resign_is_exempt(int(seed) & 0xFFFFFFFFFFFFFFFF, int(uid), float(keep_prob))
     if rc < 0:
         raise ValueError(L.azx_last_error().decode(errors="replace"))
     return bool(rc)

@@ -76,7 +76,7 @@ class Player:
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
-                 openings=None, playout_cap=None):
+                 openings=None, playout_cap=None, resign=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -110,7 +110,15 @@ class Player:
         full_prob a full search that records a row and otherwise a fast search of fast_simulations, without noise,
         that records nothing.  A ValueError -- here, before any engine is made -- with device_match=True (a match
         records one row per moved ply), when the games would run through the host loop, or for values outside
-        (0, 1] x [1, simulations]."""
+        (0, 1] x [1, simulations].
+        `resign` (NOT the reference's behaviour, which plays every game to the end; off by default):
+        (threshold, min_ply, keep_prob), or a dict with exactly these keys -- resignation (Engine.set_resign,
+        include/azx.h) for the self-play engine this Player builds, device self-play or external_batch: the mover of a
+        game gives up at a ply >= min_ply whose root value is below threshold, except in the share keep_prob of the
+        games that is exempt and measures the false positives (resign_stats()).  It is applied again whenever the
+        engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True (resign is a
+        self-play option), when the games would run through the host loop, or for values outside
+        [-1, 1] x [0, ...) x [0, 1]."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -136,6 +144,7 @@ class Player:
         self._engine_flags = _eng.FLAG_RANDOM_REFLECT if self.random_reflect else 0
         self._check_tower_precision()
         self.playout_cap = self._check_playout_cap(playout_cap)
+        self.resign = self._check_resign(resign)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -287,6 +296,27 @@ class Player:
             raise ValueError("playout_cap: fast_simulations %d above the policy's simulations %d" % (fast, pol.simulations))
         return full_prob, fast
 
+    def _check_resign(self, resign):
+        """`resign` as (threshold, min_ply, keep_prob), or None; a ValueError naming what does not hold."""
+        if resign is None:
+            return None
+        resign = normalize_resign(resign)
+        if self.device_match:
+            raise ValueError("resign is a self-play option: a device match plays every game to the end "
+                             "(engine.Match refuses an engine with resignation set)")
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("resign needs the games to run in a device engine (a single agent whose Policy holds a "
+                             "HexNetwork, or external_batch=True): these agents play through the host loop, which "
+                             "plays every game to the end")
+        return resign
+
+    def resign_stats(self):
+        """Engine.resign_stats() of the self-play engine, or None while there is none or resign is not set."""
+        if self.resign is None or self._engine is None:
+            return None
+        return self._engine.resign_stats()
+
     def _external_policy(self) -> Policy:
         """The Policy whose duck-typed net evaluates the pool's leaf batches (external_batch=True); a ValueError
         naming what does not hold otherwise -- there is no silent fall-back to the host loop."""
@@ -419,6 +449,8 @@ class Player:
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
             if self.playout_cap is not None:
                 self._engine.set_playout_cap(*self.playout_cap)
+            if self.resign is not None:
+                self._engine.set_resign(*self.resign)
             self._engine_key = key
         return self._engine
 
@@ -565,6 +597,32 @@ def normalize_playout_cap(cap):
     if fast < 1:
         raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
     return full_prob, fast
+
+
+def normalize_resign(resign):
+    """(threshold, min_ply, keep_prob) of a triple or of a {"threshold": ..., "min_ply": ..., "keep_prob": ...}
+    mapping; a ValueError unless threshold is in [-1, 1], min_ply a whole number >= 0 and keep_prob in [0, 1]."""
+    try:
+        if isinstance(resign, dict):
+            if set(resign) != {"threshold", "min_ply", "keep_prob"}:
+                raise ValueError
+            thr, min_ply, keep = resign["threshold"], resign["min_ply"], resign["keep_prob"]
+        else:
+            thr, min_ply, keep = resign
+        thr, keep = float(thr), float(keep)
+        if isinstance(min_ply, bool) or int(min_ply) != min_ply:
+            raise ValueError
+        min_ply = int(min_ply)
+    except (TypeError, ValueError, KeyError):
+        raise ValueError("resign must be (threshold, min_ply, keep_prob) or a dict with exactly these three keys, "
+                         "got %r" % (resign,)) from None
+    if not -1.0 <= thr <= 1.0:              # (false for NaN)
+        raise ValueError("resign: threshold %r outside [-1, 1]" % thr)
+    if min_ply < 0:
+        raise ValueError("resign: min_ply %d is negative" % min_ply)
+    if not 0.0 <= keep <= 1.0:
+        raise ValueError("resign: keep_prob %r outside [0, 1]" % keep)
+    return thr, min_ply, keep
 
 
 def _net_device(net) -> torch.device:

@@ -276,6 +276,22 @@ def apply_selfplay_tower(policy, config) -> None:
         raise
 
 
+def log_resign(player) -> None:
+    """One line on the self-play engine's azx_resign_stats so far: the false-positive rate of the exempt games and
+    the share of the finished games that were resigned (nothing where this process plays no games itself).
+    azx_resign_stats copies on the engine's stream and waits for it: train() does not call this while a play-ahead
+    thread (config["selfplay_overlap"]) is queuing self-play on that stream, where the trainer would wait for every
+    move already queued; there the statistics are logged once, after that thread has stopped."""
+    st = player.resign_stats()
+    if st is None:
+        return
+    games = st["resigned"] + st["played_out"] + st["exempt"]
+    logging.info("resign: false-positive rate %.4f (%d of %d exempt games with a crossing), %.4f of %d games resigned, "
+                 "mean resign ply %.1f", st["false_positives"] / max(st["exempt_crossed"], 1), st["false_positives"],
+                 st["exempt_crossed"], st["resigned"] / max(games, 1), games,
+                 st["sum_resign_ply"] / max(st["resigned"], 1))
+
+
 def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False, history=None) -> str:
     """The reference training loop (policy_trainer.py:23-119) over this package's Player.
     `history`: optional dict; receives the learning rate each epoch trained with under "lr", the name of the training
@@ -322,7 +338,21 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     otherwise a search of n simulations without Dirichlet noise that records nothing.  exploration_depth and the
     temperature are untouched.  A ValueError, before anything is built, for values outside (0, 1] x [1, simulations];
     Player refuses it where the games would run through the host loop.  Its effect on playing strength and on
-    training efficiency is not measured."""
+    training efficiency is not measured.
+
+    config["resign"] = {"threshold": t, "min_ply": m, "keep_prob": k} (default absent; NOT the reference's behaviour,
+    and outside every parity claim): resignation of self-play games with no-resign calibration games
+    (Engine.set_resign, include/azx.h has the definition).  It goes to the one self-play Player built here
+    (Player(resign=...)), so the lock-step ranks and the actors play under it too; the random-mover player that fills
+    the first buffer does NOT get it.  After every refill one log line gives the running false-positive rate of the
+    exempt games (exempt games whose would-be resigner won / exempt games with a crossing) and the share of games
+    resigned.  A ValueError, before anything is built, for values outside [-1, 1] x [0, ...) x [0, 1]; Player refuses
+    it where the games would run through the host loop.  Its effect on playing strength and on training efficiency is
+    not measured."""
+    resign = None
+    if config.get("resign") is not None:
+        from .parallel_player import normalize_resign
+        resign = normalize_resign(config["resign"])
     playout_cap = None
     if config.get("playout_cap") is not None:
         from .parallel_player import normalize_playout_cap
@@ -366,7 +396,13 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     lockstep_role = ("leader" if leader else "follower") if mode == "lockstep" else None
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
-                    random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap)
+                    random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
+                    resign=resign)
+    if leader:
+        logging.info("resignation (config['resign']): %s",
+                     "off" if resign is None else
+                     "on -- NOT the reference's behaviour: the mover resigns below a root value of %g from ply %d on; "
+                     "a share %g of the games is exempt and measures the false positives" % resign)
     if leader:
         logging.info("playout cap randomisation (config['playout_cap']): %s",
                      "off" if playout_cap is None else
@@ -503,7 +539,9 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
                     learner.after_step()
                 if ahead is not None:
                     ahead.after_step()
-                replaybuf.consume(batch_size / oversampling, player)
+                refilled = replaybuf.consume(batch_size / oversampling, player)
+                if refilled and resign is not None and leader and ahead is None:
+                    log_resign(player)
                 if config.get("log_interval") and step % config["log_interval"] == 0:
                     if loss_dev is not None:
                         loss, loss_dev = loss + float(loss_dev.item()), None
@@ -530,6 +568,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     if ahead is not None:
         ahead.stop()
         replaybuf.ahead = None
+        if resign is not None and leader:
+            log_resign(player)
         if history is not None:
             history["play_ahead"] = ahead.counters()
     if history is not None and learner is not None:

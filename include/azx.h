@@ -465,6 +465,59 @@ int azx_playout_cap_is_full(uint64_t seed, int64_t uid, int ply, double full_pro
  * it has never been set). */
 int azx_playout_cap_stats(azx_engine *e, int64_t out4[4]);
 
+/* Resignation for throughput self-play, with no-resign calibration games (AlphaGo Zero, Methods "Self-play").  NOT the
+ * reference's behaviour (off by default, outside every parity claim): the reference plays every game to the end.
+ *   The resign statistic of a ply is v = root.total_value / root.num_visits of the slot's root after the ply's search:
+ * ONE float32 IEEE division of the two numbers azx_get_root returns as root_value and root_visits.  total_value is kept
+ * in the node's own perspective, so v is the mean backed-up value for the player to move: positive is good for the
+ * mover.  The decision is taken in the move draw, after the move is drawn: a ply that resigns has consumed the same
+ * Philox words and has written the same replay row as the ply that plays on.
+ *   The mover resigns at a ply iff resignation is set, the game is not exempt, ply >= min_ply (ply counted from the
+ * empty board), root.num_visits > 0 and v < threshold.  Every searched ply is judged, the fast plies of a playout cap
+ * included.  A resigning ply places no stone: the game ends there and the winner is the colour that did not resign.
+ * The ply's replay row is recorded as always (one row on a full ply, none on a fast ply of a playout cap): a searched
+ * position with a known outcome.  The game is harvested exactly as a won game is: rows contiguous with plies
+ * ascending, colour and reward sign from each row's own ply, metric 3 on the first recorded row, games,
+ * sum_reward_last and the queue-full parking path as always.  azx_play_stats.plies, selects and evals count the
+ * resigning ply (it was searched); sum_game_length adds the stones on the board at resignation.
+ *   Exempt games: one bit per game, a pure function of (cfg.seed, the game's uid), from the game's key on a stream of
+ * its own -- nothing of it is shared with the Dirichlet words, the reflection bits, the playout-cap word or the move
+ * draw, and it does not depend on the slot, n_games, the half-pool or the launch.  The game is exempt iff the 32-bit
+ * word is <= ceil(keep_prob * 2^32) - 1: keep_prob == 0 exempts none, keep_prob == 1 all.  Device and host use the same
+ * function; azx_resign_is_exempt is it on the host.  An exempt game plays to the end, bit for bit as with resignation
+ * off, and remembers the first ply at which the rule's other conditions held: its "crossing".
+ *   Row metric 7 (always 0 otherwise) carries v for every recorded row while resignation is set, exempt games included.
+ *   It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move launches,
+ * the pipelined half-pools, a registered external evaluator) and to nothing else: azx_search, the phase API and
+ * azx_advance never resign, and azx_match_play / azx_tournament_play refuse an engine whose resignation is set with
+ * AZX_EINVAL before touching any engine (their harvest assumes one row per moved ply).
+ *   threshold must be in [-1, 1], min_ply >= 0 and keep_prob in [0, 1], all finite; anything else is AZX_EINVAL before
+ * any device work and leaves the previous setting in place.  May be called between calls, for any evaluator; games in
+ * progress are judged from their next ply on.  The call zeroes the statistics of azx_resign_stats.  With resignation
+ * never set, or cleared (azx_clear_resign), every call launches the same kernels and returns the same bytes as without
+ * these entry points.  azx_kernel_info reports resign=off or resign=<threshold>/<min_ply>/<keep_prob>.  The effect on
+ * playing strength and training efficiency is NOT measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_resign). */
+int azx_set_resign(azx_engine *e, double threshold, int min_ply, double keep_prob);
+int azx_clear_resign(azx_engine *e);
+/* host only, no device call: 1 if game `uid` under engine seed `seed` is exempt from resigning at keep_prob, else 0;
+ * AZX_EINVAL (negative) for a keep_prob that is not a finite number in [0, 1]. */
+int azx_resign_is_exempt(uint64_t seed, int64_t uid, double keep_prob);
+/* Counted since the last azx_set_resign, over the games that both started and finished after it (a game is in progress
+ * once a ply of it has been played; SearchTreeFull games count in none):
+ *   out8[0] games resigned                        out8[1] non-exempt games played to the end
+ *   out8[2] exempt games finished                 out8[3] exempt games with a crossing
+ *   out8[4] of those, games the crossing mover went on to WIN (the false positives)
+ *   out8[5] sum of the ply at resignation over [0]
+ *   out8[6] sum over [3] of (final length - crossing ply): the plies resignation would have saved
+ *   out8[7] 0
+ * They live in an array of their own: azx_debug_counters keeps its 16 words. */
+int azx_resign_stats(azx_engine *e, int64_t out8[8]);
+/* tests and analysis: v[n_games] = the resign statistic of every slot's current root, by the device function the move
+ * draw uses, whatever the setting; NaN where the root is unevaluated or unvisited. */
+int azx_resign_value(azx_engine *e, float *v);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,
