@@ -161,6 +161,9 @@ SYMBOLS = {
     "azx_resign_is_exempt": (C.c_int, [C.c_uint64, C.c_int64, C.c_double]),
     "azx_resign_stats": (C.c_int, [_vp, _i64p]),
     "azx_resign_value": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    # early stop of decided searches in throughput self-play (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_early_stop": (C.c_int, [_vp, C.c_int]),
+    "azx_early_stop_stats": (C.c_int, [_vp, _i64p]),
 }
 
 class TrainConfig(C.Structure):

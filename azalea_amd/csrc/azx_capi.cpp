@@ -138,10 +138,13 @@ struct azx_engine {
     bool resign_on = false;
     double resign_thr = -1.0, resign_keep = 0.0;
     int resign_min_ply = 0;
+    // early stop (azx_set_early_stop): handed to the same launches, by the same scope
+    bool estop_on = false;
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
-// (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) travels the same way.
+// (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) and early stop
+// (azx_set_early_stop) travel the same way.
 struct CapScope {
     DevEngine &d;
     explicit CapScope(azx_engine *e) : d(e->d) {
@@ -155,10 +158,12 @@ struct CapScope {
             d.resign_thr = (float)e->resign_thr;
             d.resign_keep_m1 = e->resign_keep > 0.0 ? azx_resign_threshold_m1(e->resign_keep) : 0u;
         }
+        if (e->estop_on) d.early_stop = 1;
     }
     ~CapScope() {
         d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
         d.resign_mode = AZX_RESIGN_OFF; d.resign_min_ply = 0; d.resign_thr = 0.0f; d.resign_keep_m1 = 0u;
+        d.early_stop = 0;
     }
     CapScope(const CapScope &) = delete;
     CapScope &operator=(const CapScope &) = delete;
@@ -287,6 +292,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.ev_value, E); A(d.ev_prior, E * AZX_CELL_STRIDE); A(d.n_eval, 4);   // (n_eval[1]: the second half-pool's count)
     A(d.counters, G * CTR_COUNT); A(d.q_count, 2); A(d.stat_sums, G * 8);
     A(d.resign_ctr, G * RS_COUNT);
+    A(d.estop_ctr, G * ES_COUNT);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
     A(e->g_rv, G); A(e->g_rw, G); A(e->g_sv, G);
@@ -425,6 +431,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.counters += b * CTR_COUNT;
     v.stat_sums += b * 8;
     v.resign_ctr += b * RS_COUNT;
+    v.estop_ctr += b * ES_COUNT;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
     if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
     if (v.row_k) v.row_k += b * nc;
@@ -487,6 +494,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
                        " cap=" + cap_text(e) +
                        " resign=" + resign_text(e) +
+                       " estop=" + (e->estop_on ? "on" : "off") +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -2045,6 +2053,31 @@ extern "C" int azx_resign_stats(azx_engine *e, int64_t out8[8]) {
     return AZX_OK;
 }
 
+// ---- early stop for throughput self-play (include/azx.h; NOT the reference's behaviour) ------
+extern "C" int azx_set_early_stop(azx_engine *e, int on) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (on != 0 && on != 1) return fail(AZX_EINVAL, "early stop: on must be 0 or 1, got %d", on);
+    ENGINE_GUARD(e);
+    HIPCHECK(hipMemsetAsync(e->d.estop_ctr, 0, (size_t)e->d.G * ES_COUNT * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->estop_on = on != 0;
+    return AZX_OK;
+}
+
+extern "C" int azx_early_stop_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * ES_COUNT);
+    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.estop_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < 4; ++j) out4[j] = 0;
+    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
+        for (int j = 0; j < ES_COUNT; ++j) out4[j] += (int64_t)hc[g * ES_COUNT + j];
+    out4[3] = 0;
+    return AZX_OK;
+}
+
 extern "C" int azx_resign_value(azx_engine *e, float *v) {
     if (!e || !v) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -2373,6 +2406,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (a->resign_on || b->resign_on)
         return fail(AZX_EINVAL, "engine %s has resignation set: a match plays every game to the end and records one "
                                 "row per moved ply (clear it with azx_clear_resign)", a->resign_on ? "a" : "b");
+    if (a->estop_on || b->estop_on)
+        return fail(AZX_EINVAL, "engine %s has early stop set: a match searches every ply in full "
+                                "(clear it with azx_set_early_stop(e, 0))", a->estop_on ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2640,6 +2676,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->resign_on)
             return fail(AZX_EINVAL, "engine %d has resignation set: a tournament plays every game to the end and "
                                     "records one row per moved ply (clear it with azx_clear_resign)", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->estop_on)
+            return fail(AZX_EINVAL, "engine %d has early stop set: a tournament searches every ply in full "
+                                    "(clear it with azx_set_early_stop(e, 0))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

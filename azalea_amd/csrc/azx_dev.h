@@ -154,7 +154,14 @@ struct DevEngine {
     float resign_thr;           // the mover resigns iff root.total_value / root.num_visits < resign_thr
     uint32_t resign_keep_m1;    // the game is exempt iff azx_resign_word(seed, uid) <= resign_keep_m1 (mode DRAW_EXEMPT)
     unsigned long long *resign_ctr;   // [G][RS_COUNT] per game (no atomics), azx_resign_stats' array; the host sums
+    // early stop (azx_set_early_stop; NOT the reference's behaviour), handed to the same launches only and 0 in every
+    // other: a ply drawn at temperature 0 ends its search at the first batch boundary at which the most-visited root
+    // child leads the second by more than the selects still to come (include/azx.h states the rule)
+    int32_t early_stop;
+    unsigned long long *estop_ctr;    // [G][ES_COUNT] per game (no atomics), azx_early_stop_stats' array; the host sums
 };
+// T = 0 plies searched under the option, plies stopped before their last batch, batches skipped (batches_left at the stops)
+enum { ES_T0_PLIES = 0, ES_STOPPED, ES_SKIPPED, ES_COUNT = 4 };
 enum { RS_RESIGNED = 0, RS_PLAYED_OUT, RS_EXEMPT, RS_EXEMPT_CROSSED, RS_FALSE_POS, RS_SUM_RESIGN_PLY, RS_SUM_SAVED, RS_COUNT = 8 };
 
 // ---- wave64 reductions on DPP (no LDS crossbar round trips) ---------------------------------

@@ -419,6 +419,11 @@ __device__ __forceinline__ void compact_tree(const DevEngine &E, int g, TreeHdr 
 #define AZX_MCTS_ATTR
 #define AZX_PLAY_ATTR(S) __attribute__((amdgpu_waves_per_eu((S) == 2 ? 4 : 2)))     // k_play, see there
 #endif
+// The ply's move is drawn at temperature 0 (policy.py:142-149): choose_body's T and the early stop's gate
+__device__ __forceinline__ bool draw_is_greedy(const DevEngine &E, int ply) {
+    return ply >= E.exploration_depth || !(E.temperature > 0.0f);
+}
+
 template <int SLOTS, bool FAST>
 __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int num_batches, bool stage_tables = true) {
     const int mode = FAST ? (MODE_BEGIN | MODE_INLINE) : mode_arg;
@@ -881,7 +886,61 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
 
     // =================================== SELECT (+ inline evaluate/expand/backup) =========
     const bool do_select = (mode & (MODE_SELECT | MODE_INLINE)) != 0;
-    T_DECL
+    // Early stop (azx_set_early_stop; NOT the reference's behaviour, 0 unless the host hands a play-mode launch the
+    // option): a ply drawn at temperature 0 (draw_is_greedy, the expression choose_body uses) ends its search at the
+    // first batch boundary at which n1 - n2 > batches_left * bs, n1 and n2 the largest and second-largest num_visits
+    // among the root's children: the selects still to come can change neither the move nor the one-hot row.
+    // Three wave-uniform integers follow (n1, the leader's rank, n2) through the launch.  They are set here, at the
+    // boundary the launch starts at (earlier batches expanded and backed up, virtual losses undone: the phase API's
+    // launches select one batch each, so this is their only boundary), by two wave reductions over the counts: a max,
+    // then a max with the first maximal lane removed.  After every batch this launch backs up itself, es_update reads
+    // the batch's root children again: between two boundaries a root child's count never falls, so "leader overtaken,
+    // else second overtaken" keeps the pair exact with scalar work alone.  (A second pair of reductions, or any exit,
+    // in the select loop's header cost every tree kernel 14-22 vector registers and an occupancy step; so the loop's
+    // header is untouched, the rule is tested where a batch ends, and the statistics are counted in the epilogue.)
+    // An all-zero root gives 0 - 0, which never exceeds batches_left * bs > 0.
+    // es_r1: -1 not tracking (option off, T > 0, no root children); <= -2 stopped: -1 - the batches skipped
+    int es_n1 = 0, es_n2 = 0, es_r1 = -1;
+    if (E.early_stop != 0 && draw_is_greedy(E, ply) && root_link >= 0 && k_root > 0) {
+        uint32_t a = 0u;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) a = max(a, lane_bit(rootrm[s]) ? (uint32_t)(int)rst[s].x : 0u);
+        es_n1 = (int)wave_max_u32(a);
+        uint32_t b = 0u;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            uint32_t x = lane_bit(rootrm[s]) ? (uint32_t)(int)rst[s].x : 0u;
+            const uint64_t eq = __ballot(lane_bit(rootrm[s]) && x == (uint32_t)es_n1);
+            if (es_r1 < 0 && eq) {
+                es_r1 = s * 64 + (int)__ffsll((long long)eq) - 1;
+                if (lane == (es_r1 & 63)) x = 0u;
+            }
+            b = max(b, x);
+        }
+        es_n2 = (int)wave_max_u32(b);
+    }
+    auto es_update = [&]() __attribute__((always_inline)) {
+        for (int i = 0; i < bs; ++i) {
+            const int r = rl(m_cells, i) & 0xffff;         // the rank of leaf i's root child
+            int c = 0;
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const int v = __builtin_amdgcn_readlane((int)rst[s].x, r & 63);
+                if (s == (r >> 6)) c = v;
+            }
+            if (r == es_r1) es_n1 = c;
+            else if (c > es_n1) { es_n2 = es_n1; es_n1 = c; es_r1 = r; }
+            else if (c > es_n2) es_n2 = c;
+        }
+    };
+    // the rule at a boundary with batches still to run (counted in the epilogue); the select loop then finds none left
+    auto es_check = [&]() __attribute__((always_inline)) {
+        if (batches_left > 0 && status == 0 && es_n1 - es_n2 > batches_left * bs) {
+            es_r1 = -1 - batches_left;
+            batches_left = 0;
+        }
+    };
+    if (es_r1 >= 0 && do_select && pending == 0) es_check();
     while (do_select && batches_left > 0 && status == 0 && pending == 0) {
         if (root_link < 0) break;   // unevaluated or terminal root: nothing to search
         // The SIMD's issue arbiter favours its oldest waves, which then finish early and leave the
@@ -1284,6 +1343,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             wave_mem_sync();   // the children written by rank above are read by other lanes from here on
             if (status == 0) search_value += np_sum_vals(nu);   // mcts.py:287
             T_MARK(5)
+            if (es_r1 >= 0) { es_update(); es_check(); }
             continue;
         }
         // undo the virtual losses in list order (mcts.py:72)
@@ -1328,6 +1388,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             wave_mem_sync();   // the children written by rank above are read by other lanes from here on
             if (status == 0) search_value += np_sum_vals(nu);   // mcts.py:287
             T_MARK(5)
+            if (es_r1 >= 0) { es_update(); es_check(); }
         } else {
             // hand the unique leaves to the evaluator: scratch + packed requests
             int n_nt = 0;
@@ -1383,6 +1444,11 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         th->select_count = select_count;
         th->search_value = search_value;
         if (!FAST) th->slow_div = slow_div ? 1 : 0;
+        if (es_r1 < -1) {
+            unsigned long long *es = E.estop_ctr + (size_t)g * ES_COUNT;
+            es[ES_STOPPED] += 1ull;
+            es[ES_SKIPPED] += (unsigned long long)(-1 - es_r1);
+        }
     }
     // the six per-game tallies, one lane each (as six scalar read-modify-writes the compiler waited
     // for each load in turn: six memory round trips at the end of every launch)
@@ -1878,6 +1944,8 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
             }
         }
     }
+    // early stop (azx_set_early_stop): the T = 0 plies searched under the option, fast plies included
+    if (E.early_stop != 0 && lane == 0 && draw_is_greedy(E, ply)) E.estop_ctr[(size_t)g * ES_COUNT + ES_T0_PLIES] += 1ull;
     // playout cap (azx_set_playout_cap): a fast ply moves the game on and records nothing
     if (E.cap_fast_batches != 0) {
         const bool cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
@@ -1906,7 +1974,10 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         float rs_v;
         gh->move_id = resign_judge(E, g, gh, th, ply, chosen, &rs_v);
         const float logp = __logf(chosen_w / tot);
-        const float sval = th->search_value / (float)E.selects_per_search;   // mcts.py:291 (as azx_get_root reports it)
+        // mcts.py:291 (as azx_get_root reports it); under early stop the mean is over the selects the ply made
+        // (0 where a stopped ply made none: the carried subtree's leader was already out of reach)
+        const int sval_n = E.early_stop != 0 ? th->select_count : E.selects_per_search;
+        const float sval = sval_n > 0 ? th->search_value / (float)sval_n : 0.0f;
         E.stat_sums[(size_t)g * 8 + 0] += (double)sval;
         E.stat_sums[(size_t)g * 8 + 1] += (double)width;
         E.stat_sums[(size_t)g * 8 + 2] += (double)logp;

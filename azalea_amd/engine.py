@@ -591,6 +591,30 @@ class Engine:
         check(self.L.azx_resign_stats(self.h, _p(out, C.c_int64)))
         return {k: int(out[i]) for i, k in enumerate(self.RESIGN_STATS)}
 
+    # ---- early stop of decided searches (azx_set_early_stop; NOT the reference's behaviour) ------------
+    def set_early_stop(self, on=True):
+        """azx_set_early_stop: in the following play / play_device / replay_fill / play_steps calls the search of a ply
+        that is drawn at temperature 0 (ply >= exploration_depth, or temperature 0) stops at the first batch boundary at
+        which the most-visited root child leads the second by more than the selects still to come: they could change
+        neither the move nor the one-hot row (include/azx.h states the rule).  The carried subtree is thinner for it.
+        NOT the reference's behaviour, which runs every search to its last simulation; off by default.  search(), the
+        phase API and matches are untouched; Match / Tournament refuse an engine with the option set.
+        set_early_stop(False) clears it: the same kernels, the same bytes as before.  Zeroes early_stop_stats().  What
+        it buys is given in DESIGN 7.11; its effect on playing strength and training efficiency is not measured."""
+        if on not in (True, False, 0, 1):
+            raise ValueError("early stop: on must be True or False, got %r" % (on,))
+        check(self.L.azx_set_early_stop(self.h, 1 if on else 0))
+
+    EARLY_STOP_STATS = ("t0_plies", "stopped_plies", "batches_skipped")
+
+    def early_stop_stats(self):
+        """azx_early_stop_stats since the last set_early_stop: dict(t0_plies, stopped_plies, batches_skipped) -- the
+        temperature-0 plies searched under the option, those stopped before their last batch, and the sum of the
+        batches they had left."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_early_stop_stats(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(self.EARLY_STOP_STATS)}
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""

@@ -76,7 +76,7 @@ class Player:
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
-                 openings=None, playout_cap=None, resign=None):
+                 openings=None, playout_cap=None, resign=None, early_stop=False):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -118,7 +118,14 @@ class Player:
         games that is exempt and measures the false positives (resign_stats()).  It is applied again whenever the
         engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True (resign is a
         self-play option), when the games would run through the host loop, or for values outside
-        [-1, 1] x [0, ...) x [0, 1]."""
+        [-1, 1] x [0, ...) x [0, 1].
+        `early_stop` (NOT the reference's behaviour, which runs every search to its last simulation; off by default):
+        True sets Engine.set_early_stop (include/azx.h has the rule) on the self-play engine this Player builds, device
+        self-play or external_batch: the search of a ply drawn at temperature 0 stops once the most-visited root child
+        leads by more than the selects still to come.  It is applied again whenever the engine is made again.  A
+        ValueError -- here, before any engine is made -- with device_match=True (a match searches every ply in full),
+        when the games would run through the host loop, or for a value that is not a bool.  Its effect on playing
+        strength and training efficiency is not measured."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -145,6 +152,7 @@ class Player:
         self._check_tower_precision()
         self.playout_cap = self._check_playout_cap(playout_cap)
         self.resign = self._check_resign(resign)
+        self.early_stop = self._check_early_stop(early_stop)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -311,6 +319,27 @@ class Player:
                              "plays every game to the end")
         return resign
 
+    def _check_early_stop(self, early_stop):
+        """`early_stop` as a bool; a ValueError naming what does not hold."""
+        early_stop = normalize_early_stop(early_stop)
+        if not early_stop:
+            return False
+        if self.device_match:
+            raise ValueError("early_stop is a self-play option: a device match searches every ply in full "
+                             "(engine.Match refuses an engine with early stop set)")
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("early_stop needs the games to run in a device engine (a single agent whose Policy holds "
+                             "a HexNetwork, or external_batch=True): these agents play through the host loop, which "
+                             "runs every search to its last simulation")
+        return True
+
+    def early_stop_stats(self):
+        """Engine.early_stop_stats() of the self-play engine, or None while there is none or early_stop is not set."""
+        if not self.early_stop or self._engine is None:
+            return None
+        return self._engine.early_stop_stats()
+
     def resign_stats(self):
         """Engine.resign_stats() of the self-play engine, or None while there is none or resign is not set."""
         if self.resign is None or self._engine is None:
@@ -451,6 +480,8 @@ class Player:
                 self._engine.set_playout_cap(*self.playout_cap)
             if self.resign is not None:
                 self._engine.set_resign(*self.resign)
+            if self.early_stop:
+                self._engine.set_early_stop(True)
             self._engine_key = key
         return self._engine
 
@@ -597,6 +628,15 @@ def normalize_playout_cap(cap):
     if fast < 1:
         raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
     return full_prob, fast
+
+
+def normalize_early_stop(early_stop):
+    """`early_stop` as a bool; a ValueError for anything but True / False (None counts as False)."""
+    if early_stop is None:
+        return False
+    if not isinstance(early_stop, (bool, np.bool_)):
+        raise ValueError("early_stop must be True or False, got %r" % (early_stop,))
+    return bool(early_stop)
 
 
 def normalize_resign(resign):

@@ -348,7 +348,20 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     exempt games (exempt games whose would-be resigner won / exempt games with a crossing) and the share of games
     resigned.  A ValueError, before anything is built, for values outside [-1, 1] x [0, ...) x [0, 1]; Player refuses
     it where the games would run through the host loop.  Its effect on playing strength and on training efficiency is
-    not measured."""
+    not measured.
+
+    config["early_stop"] = True (default absent / False; NOT the reference's behaviour, and outside every parity
+    claim): the search of a self-play ply that is drawn at temperature 0 stops once the most-visited root child leads
+    by more than the selects still to come (Engine.set_early_stop, include/azx.h has the rule).  It goes to the one
+    self-play Player built here (Player(early_stop=True)), so the lock-step ranks and the actors play under it too;
+    the random-mover player that fills the first buffer does NOT get it.  One log line says whether it is on.  A
+    ValueError, before anything is built, for a value that is not a bool; Player refuses it where the games would run
+    through the host loop.  Its effect on playing strength and on training efficiency is not measured."""
+    from .parallel_player import normalize_early_stop
+    try:
+        early_stop = normalize_early_stop(config.get("early_stop"))
+    except ValueError as exc:
+        raise ValueError("config['early_stop']: %s" % exc) from None
     resign = None
     if config.get("resign") is not None:
         from .parallel_player import normalize_resign
@@ -397,7 +410,11 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
                     random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
-                    resign=resign)
+                    resign=resign, early_stop=early_stop)
+    if leader:
+        logging.info("early stop (config['early_stop']): %s",
+                     "on -- NOT the reference's behaviour: a search drawn at temperature 0 stops once its leading root "
+                     "child cannot be caught" if early_stop else "off")
     if leader:
         logging.info("resignation (config['resign']): %s",
                      "off" if resign is None else

@@ -518,6 +518,46 @@ int azx_resign_stats(azx_engine *e, int64_t out8[8]);
  * draw uses, whatever the setting; NaN where the root is unevaluated or unvisited. */
 int azx_resign_value(azx_engine *e, float *v);
 
+/* Early stop of a search whose move can no longer change, for throughput self-play.  NOT the reference's behaviour
+ * (off by default, outside every parity claim): the reference runs every search to its last simulation.
+ *   From exploration_depth on the move is drawn at temperature 0: the most-visited root child is played, and the
+ * replay row is the same distribution, one-hot on that child.  Once the leading root child is further ahead than the
+ * selects still to come, those selects can change neither the move nor the row; they only deepen the subtree that is
+ * carried to the next ply.
+ *   The rule.  The search of a ply stops early iff all of the following hold:
+ *     - the option is set;
+ *     - the ply is drawn at temperature 0, i.e. ply >= exploration_depth or temperature == 0, the same expression the
+ *       move draw uses;
+ *     - at a batch boundary, n1 - n2 > batches_left * search_batch_size.
+ *   A batch boundary means all earlier batches are expanded and backed up and their virtual losses undone (the top of
+ * the select loop with nothing pending).  n1 and n2 are the largest and second-largest num_visits among the root's
+ * children; n2 = 0 with one child.  The counts are integers held in float32, so the comparison is exact.  The
+ * inequality is strict: at a stop the leader is unique, and no tie can form later, because a select adds at most one
+ * visit to one root child.  An unevaluated root (all counts 0) never satisfies the rule.
+ *   Stopping means batches_left = 0: the slot then behaves as a slot whose batches are used up already does -- no
+ * selects and no queued rows in the move's remaining launches, the same launch structure.  Everything else is as
+ * always: Dirichlet noise per select, the Philox move draw, the row, the carried subtree.  Resignation's judgement
+ * (azx_set_resign) is then made on the stopped search's root.  A playout cap's fast plies stop early too when they are
+ * temperature-0 plies.  While the option is on, row metric 0 and azx_play_stats.sum_search_value are divided by the
+ * selects the ply made, not by the full search's select count (0 where a stopped ply made none).
+ *   It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move launches,
+ * the pipelined half-pools, a registered external evaluator) and to nothing else: azx_search and the phase API run
+ * cfg.simulations whatever the option is, and azx_match_play / azx_tournament_play refuse an engine with the option
+ * set with AZX_EINVAL before touching any engine.
+ *   on must be 0 or 1; anything else is AZX_EINVAL and leaves the setting in place.  May be called between calls, for
+ * any evaluator.  The call zeroes the statistics of azx_early_stop_stats.  With the option never set, or cleared
+ * (on = 0), every call launches the same kernels and returns the same bytes as without these entry points.
+ * azx_kernel_info reports estop=on or estop=off.  What the option buys in plies per second depends on the network and
+ * is given in DESIGN 7.11; its effect on playing strength and training efficiency (the cost is a thinner carried
+ * subtree) is not measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_early_stop). */
+int azx_set_early_stop(azx_engine *e, int on);
+/* out4 = {temperature-0 plies searched under the option, plies stopped before their last batch, batches skipped (the
+ * sum of batches_left at the stops), 0}, counted since the last azx_set_early_stop.  They live in an array of their
+ * own: azx_debug_counters keeps its 16 words. */
+int azx_early_stop_stats(azx_engine *e, int64_t out4[4]);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,
