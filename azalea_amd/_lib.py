@@ -164,6 +164,11 @@ SYMBOLS = {
     # early stop of decided searches in throughput self-play (additions within revision 7; NOT the reference's behaviour)
     "azx_set_early_stop": (C.c_int, [_vp, C.c_int]),
     "azx_early_stop_stats": (C.c_int, [_vp, _i64p]),
+    # training targets of the recorded rows: visit-share rows, z/q-blended rewards (additions within revision 7; NOT the
+    # reference's behaviour)
+    "azx_set_train_targets": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "azx_get_train_targets": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "azx_train_targets_stats": (C.c_int, [_vp, _i64p]),
 }
 
 class TrainConfig(C.Structure):

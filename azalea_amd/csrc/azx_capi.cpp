@@ -140,11 +140,15 @@ struct azx_engine {
     int resign_min_ply = 0;
     // early stop (azx_set_early_stop): handed to the same launches, by the same scope
     bool estop_on = false;
+    // training targets (azx_set_train_targets): handed to the same launches, by the same scope
+    int tt_rows = AZX_ROWS_REFERENCE;
+    float tt_mix = 0.0f;
+    bool tt_on() const { return tt_rows != AZX_ROWS_REFERENCE || tt_mix > 0.0f; }
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
 // (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) and early stop
-// (azx_set_early_stop) travel the same way.
+// (azx_set_early_stop) travel the same way, and so do the training targets (azx_set_train_targets).
 struct CapScope {
     DevEngine &d;
     explicit CapScope(azx_engine *e) : d(e->d) {
@@ -159,11 +163,13 @@ struct CapScope {
             d.resign_keep_m1 = e->resign_keep > 0.0 ? azx_resign_threshold_m1(e->resign_keep) : 0u;
         }
         if (e->estop_on) d.early_stop = 1;
+        d.tt_rows = e->tt_rows; d.tt_mix = e->tt_mix;
     }
     ~CapScope() {
         d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
         d.resign_mode = AZX_RESIGN_OFF; d.resign_min_ply = 0; d.resign_thr = 0.0f; d.resign_keep_m1 = 0u;
         d.early_stop = 0;
+        d.tt_rows = AZX_ROWS_REFERENCE; d.tt_mix = 0.0f;
     }
     CapScope(const CapScope &) = delete;
     CapScope &operator=(const CapScope &) = delete;
@@ -293,6 +299,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.counters, G * CTR_COUNT); A(d.q_count, 2); A(d.stat_sums, G * 8);
     A(d.resign_ctr, G * RS_COUNT);
     A(d.estop_ctr, G * ES_COUNT);
+    A(d.tt_ctr, G * TT_COUNT);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
     A(e->g_rv, G); A(e->g_rw, G); A(e->g_sv, G);
@@ -432,6 +439,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.stat_sums += b * 8;
     v.resign_ctr += b * RS_COUNT;
     v.estop_ctr += b * ES_COUNT;
+    v.tt_ctr += b * TT_COUNT;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
     if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
     if (v.row_k) v.row_k += b * nc;
@@ -455,6 +463,13 @@ static std::string resign_text(const azx_engine *e) {
     if (!e->resign_on) return "off";
     char t[96];
     snprintf(t, sizeof t, "%.6g/%d/%.6g", e->resign_thr, e->resign_min_ply, e->resign_keep);
+    return t;
+}
+
+static std::string targets_text(const azx_engine *e) {
+    if (!e->tt_on()) return "off";
+    char t[64];
+    snprintf(t, sizeof t, "%s/%.9g", e->tt_rows == AZX_ROWS_VISITS ? "visits" : "reference", (double)e->tt_mix);
     return t;
 }
 
@@ -495,6 +510,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " cap=" + cap_text(e) +
                        " resign=" + resign_text(e) +
                        " estop=" + (e->estop_on ? "on" : "off") +
+                       " targets=" + targets_text(e) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -2078,6 +2094,42 @@ extern "C" int azx_early_stop_stats(azx_engine *e, int64_t out4[4]) {
     return AZX_OK;
 }
 
+// ---- training targets of the recorded rows (include/azx.h; NOT the reference's behaviour) ------
+extern "C" int azx_set_train_targets(azx_engine *e, int policy_rows, float value_mix) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (policy_rows != AZX_ROWS_REFERENCE && policy_rows != AZX_ROWS_VISITS)
+        return fail(AZX_EINVAL, "train targets: policy_rows must be AZX_ROWS_REFERENCE (0) or AZX_ROWS_VISITS (1), got %d", policy_rows);
+    if (!(value_mix >= 0.0f && value_mix <= 1.0f))      // NaN fails both comparisons
+        return fail(AZX_EINVAL, "train targets: value_mix must be in [0, 1], got %g", (double)value_mix);
+    ENGINE_GUARD(e);
+    HIPCHECK(hipMemsetAsync(e->d.tt_ctr, 0, (size_t)e->d.G * TT_COUNT * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->tt_rows = policy_rows;
+    e->tt_mix = value_mix;
+    return AZX_OK;
+}
+
+extern "C" int azx_get_train_targets(azx_engine *e, int *policy_rows, float *value_mix) {
+    if (!e || !policy_rows || !value_mix) return fail(AZX_EINVAL, "null argument");
+    *policy_rows = e->tt_rows;
+    *value_mix = e->tt_mix;
+    return AZX_OK;
+}
+
+extern "C" int azx_train_targets_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * TT_COUNT);
+    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.tt_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < 4; ++j) out4[j] = 0;
+    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
+        for (int j = 0; j < TT_COUNT; ++j) out4[j] += (int64_t)hc[g * TT_COUNT + j];
+    out4[3] = 0;
+    return AZX_OK;
+}
+
 extern "C" int azx_resign_value(azx_engine *e, float *v) {
     if (!e || !v) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -2409,6 +2461,10 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (a->estop_on || b->estop_on)
         return fail(AZX_EINVAL, "engine %s has early stop set: a match searches every ply in full "
                                 "(clear it with azx_set_early_stop(e, 0))", a->estop_on ? "a" : "b");
+    if (a->tt_on() || b->tt_on())
+        return fail(AZX_EINVAL, "engine %s has training targets set: a match's harvest records the reference's rows and "
+                                "the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))",
+                    a->tt_on() ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2680,6 +2736,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->estop_on)
             return fail(AZX_EINVAL, "engine %d has early stop set: a tournament searches every ply in full "
                                     "(clear it with azx_set_early_stop(e, 0))", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->tt_on())
+            return fail(AZX_EINVAL, "engine %d has training targets set: a tournament's harvest records the reference's "
+                                    "rows and the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

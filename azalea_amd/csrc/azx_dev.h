@@ -159,7 +159,14 @@ struct DevEngine {
     // child leads the second by more than the selects still to come (include/azx.h states the rule)
     int32_t early_stop;
     unsigned long long *estop_ctr;    // [G][ES_COUNT] per game (no atomics), azx_early_stop_stats' array; the host sums
+    // training targets of the recorded rows (azx_set_train_targets; NOT the reference's behaviour), handed to the same
+    // launches only and "off" (AZX_ROWS_REFERENCE, 0.0f) in every other (include/azx.h has the definition)
+    int32_t tt_rows;            // AZX_ROWS_VISITS: the row is counts / sum(counts) at every recorded ply, whatever T
+    float tt_mix;               // lambda: the harvest stores (1 - lambda) * z + lambda * v, v = row metric 7
+    unsigned long long *tt_ctr;       // [G][TT_COUNT] per game (no atomics), azx_train_targets_stats' array; the host sums
 };
+// rows recorded while the option is on; of those, rows of greedy plies; of those, rows with more than one visited child
+enum { TT_ROWS = 0, TT_GREEDY, TT_GREEDY_WIDE, TT_COUNT = 4 };
 // T = 0 plies searched under the option, plies stopped before their last batch, batches skipped (batches_left at the stops)
 enum { ES_T0_PLIES = 0, ES_STOPPED, ES_SKIPPED, ES_COUNT = 4 };
 enum { RS_RESIGNED = 0, RS_PLAYED_OUT, RS_EXEMPT, RS_EXEMPT_CROSSED, RS_FALSE_POS, RS_SUM_RESIGN_PLY, RS_SUM_SAVED, RS_COUNT = 8 };

@@ -1709,6 +1709,10 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
             const int64_t uid = gh->uid;
             // row r was recorded at the ply choose_body left in its metrics (ply0 + r unless a playout cap skipped plies)
             const float4 *gms = reinterpret_cast<const float4 *>(E.row_meta) + (size_t)g * E.ncells * 2;
+            // azx_set_train_targets (NOT the reference's behaviour; 0 unless the host hands a play-mode launch the option):
+            // the stored reward is (1 - mix) * z + mix * v, v the search's own estimate choose_body left in metric 7,
+            // both in the mover's view; two products and a sum, unfused.  z itself where v is not finite or mix is 0.
+            const float tt_mix = E.tt_mix;
             for (int r = lane; r < rows; r += 64) {
                 const size_t q = (size_t)((pos + r) % (unsigned long long)E.q_cap);
                 const float4 *ms = gms + (size_t)r * 2;
@@ -1718,6 +1722,10 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
                 E.q_k[q] = E.row_k[(size_t)g * E.ncells + r];
                 float rew = (float)(result - 2);               // play_game.py:64-65
                 if (rply & 1) rew = -rew;
+                if (tt_mix > 0.0f) {
+                    const float v = reinterpret_cast<const float *>(ms)[7];      // row metric 7
+                    if (isfinite(v)) rew = (1.0f - tt_mix) * rew + tt_mix * v;
+                }
                 E.q_reward[q] = rew;
                 E.q_uid[q] = uid;
                 mt.w = r == 0 ? 1.0f : 0.0f;                   // marks the first row of a game
@@ -1838,15 +1846,20 @@ __global__ void k_resign_mark(DevEngine E) {
 // Resignation (azx_set_resign; NOT the reference's behaviour): judged by one lane where the drawn move is stored, so a
 // resigning ply has consumed the same Philox words and writes the same row as the ply that plays on.  Returns the move
 // id to store (the drawn child, or AZX_MOVE_RESIGN) and in *v row metric 7 (0 while resignation is off); marks an
-// exempt game's crossing.
+// exempt game's crossing.  The training targets (azx_set_train_targets) want the same v in metric 7, from the same load
+// of the root, with resignation set or not; they never change the judgement.
+__device__ __forceinline__ bool train_targets_on(const DevEngine &E) {
+    return E.tt_rows != AZX_ROWS_REFERENCE || E.tt_mix > 0.0f;
+}
+
 __device__ __forceinline__ int resign_judge(const DevEngine &E, int g, GameHdr *gh, const TreeHdr *th, int ply,
                                             int chosen, float *v) {
     *v = 0.0f;
-    if (E.resign_mode == AZX_RESIGN_OFF) return chosen;
+    if (E.resign_mode == AZX_RESIGN_OFF && !train_targets_on(E)) return chosen;
     const Node rootn = (E.arena[th->arena] + (size_t)g * E.cap)[th->root_id];
     const float rv = resign_value(rootn);
     *v = rv;
-    if (ply >= E.resign_min_ply && rootn.nv > 0.0f && rv < E.resign_thr) {
+    if (E.resign_mode != AZX_RESIGN_OFF && ply >= E.resign_min_ply && rootn.nv > 0.0f && rv < E.resign_thr) {
         if (!azx_resign_exempt(E.seed, gh->uid, E.resign_mode, E.resign_keep_m1)) return AZX_MOVE_RESIGN;
         const int st = gh->rs_state;
         if ((st & AZX_RS_CROSS) == 0) gh->rs_state = st | (ply + 1);      // the exempt game's crossing
@@ -1958,14 +1971,18 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
             return;
         }
     }
-    // replay row (play_game.py:92-94): pre-move board and moves_prob
+    // replay row (play_game.py:92-94): pre-move board and moves_prob.  Under AZX_ROWS_VISITS (azx_set_train_targets;
+    // NOT the reference's behaviour) the row is the visit shares nv / nv_sum whatever T drew the move: the expression
+    // w / tot already is at T = 1, one IEEE division either way.  (An unvisited root keeps the reference row.)
     const int row = gh->n_rows;
     const size_t rb = ((size_t)g * E.ncells + row) * AZX_CELL_STRIDE;
+    const bool tt_vis = E.tt_rows == AZX_ROWS_VISITS && nv_sum > 0.0f;
+    const float row_den = tt_vis ? nv_sum : tot;
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
         const int cell = s * 64 + lane;
         if (cell < AZX_CELL_STRIDE) E.row_board[rb + cell] = (unsigned char)(h.c[s] & 3u);
-        if (lane_bit(mk.m[s])) E.row_prob[rb + rk[s]] = w[s] / tot;
+        if (lane_bit(mk.m[s])) E.row_prob[rb + rk[s]] = (tt_vis ? nv[s] : w[s]) / row_den;
     }
     for (int o = mk.k + lane; o < AZX_CELL_STRIDE; o += 64) E.row_prob[rb + o] = 0.0f;
     if (lane == 0) {
@@ -1985,6 +2002,16 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         float4 *meta = reinterpret_cast<float4 *>(E.row_meta) + ((size_t)g * E.ncells + row) * 2;
         meta[0] = make_float4(sval, (float)width, logp, __int_as_float(ply));   // .w: the row's ply until the harvest flags the first row there
         meta[1] = make_float4(nv_sum / (float)mk.k, (float)(th->num_nodes + th->dropped), (float)mk.k, rs_v);
+        // azx_train_targets_stats: rows recorded under the option, those of greedy plies, those of them with more than
+        // one visited child (the rows that differ from the reference's)
+        if (train_targets_on(E)) {
+            unsigned long long *tc = E.tt_ctr + (size_t)g * TT_COUNT;
+            tc[TT_ROWS] += 1ull;
+            if (draw_is_greedy(E, ply)) {
+                tc[TT_GREEDY] += 1ull;
+                if (width > 1) tc[TT_GREEDY_WIDE] += 1ull;
+            }
+        }
     }
 }
 

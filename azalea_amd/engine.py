@@ -615,6 +615,49 @@ class Engine:
         check(self.L.azx_early_stop_stats(self.h, _p(out, C.c_int64)))
         return {k: int(out[i]) for i, k in enumerate(self.EARLY_STOP_STATS)}
 
+    # ---- training targets of the recorded rows (azx_set_train_targets; NOT the reference's behaviour) ----
+    POLICY_ROWS = ("reference", "visits")      # AZX_ROWS_REFERENCE, AZX_ROWS_VISITS
+
+    def set_train_targets(self, policy_rows="reference", value_mix=0.0):
+        """azx_set_train_targets: what the rows of the following play / play_device / replay_fill / play_steps calls
+        teach.  policy_rows="visits": the row of every recorded ply is counts / sum(counts) of the root's children,
+        whatever temperature drew the move (the reference's row is one-hot on the most-visited child from
+        exploration_depth on).  value_mix = lambda in [0, 1]: the stored reward is (1 - lambda) * z + lambda * v, z the
+        game's outcome and v = root.total_value / root.num_visits after the ply's search, both in the mover's view; row
+        metric 7 carries v.  The move draw is untouched: the games are the games of the same seed with the option off
+        (include/azx.h has the definition).  NOT the reference's behaviour; off by default.  search(), the phase API
+        and matches are untouched; Match / Tournament refuse an engine with the option set.  ("reference", 0.0) is
+        "off": the same kernels, the same bytes as before.  Zeroes train_targets_stats().  DESIGN 7.12 has what is
+        measured of its effect."""
+        if policy_rows not in self.POLICY_ROWS:
+            raise ValueError("train targets: policy_rows must be 'reference' or 'visits', got %r" % (policy_rows,))
+        value_mix = float(value_mix)
+        if not 0.0 <= value_mix <= 1.0:
+            raise ValueError("train targets: value_mix must be in [0, 1], got %r" % (value_mix,))
+        check(self.L.azx_set_train_targets(self.h, self.POLICY_ROWS.index(policy_rows), value_mix))
+
+    def clear_train_targets(self):
+        """set_train_targets("reference", 0.0): the reference's rows and the game's outcome again."""
+        check(self.L.azx_set_train_targets(self.h, 0, 0.0))
+
+    def train_targets(self):
+        """azx_get_train_targets: the pair (policy_rows, value_mix) in force, ("reference", 0.0) when off."""
+        rows, mix = C.c_int(0), C.c_float(0.0)
+        if getattr(self.L, "azx_get_train_targets", None) is None:     # an older build (tools/lib_bench.py): never set
+            return self.POLICY_ROWS[0], 0.0
+        check(self.L.azx_get_train_targets(self.h, C.byref(rows), C.byref(mix)))
+        return self.POLICY_ROWS[rows.value], float(mix.value)
+
+    TRAIN_TARGETS_STATS = ("rows", "greedy_rows", "greedy_rows_wide")
+
+    def train_targets_stats(self):
+        """azx_train_targets_stats since the last set_train_targets: dict(rows, greedy_rows, greedy_rows_wide) -- the
+        rows recorded while the option is on, of those the rows of plies drawn at temperature 0, and of those the rows
+        with more than one visited child (the rows that differ from the reference's)."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_train_targets_stats(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(self.TRAIN_TARGETS_STATS)}
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""
@@ -689,6 +732,15 @@ def _opening_index(first_game, n_games, n_openings, first_mover):
     return ((u >> 1 if first_mover is None else u) % n_openings).astype(np.int32)
 
 
+def _refuse_train_targets(engines, what):
+    """ValueError for an engine with set_train_targets in force: the harvest of a match or tournament records the
+    reference's rows and the outcome (azx_match_play / azx_tournament_play refuse it too, with AZX_EINVAL)."""
+    for i, e in enumerate(engines):
+        if e.train_targets() != ("reference", 0.0):
+            raise ValueError("engine %d has training targets %r set: a %s's harvest records the reference's rows and "
+                             "the outcome (clear_train_targets() first)" % (i, e.train_targets(), what))
+
+
 class Match:
     """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
     agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
@@ -745,6 +797,7 @@ class Match:
         each game, int32[n]."""
         if collect not in (False, True, "device"):
             raise ValueError("collect must be False, True or 'device'")
+        _refuse_train_targets((self.a, self.b), "match")
         if openings is not _KEEP and _book_key(openings) != self._book:
             self.set_openings(openings)
         # (set only when they change: a plain play touches none of the later entry points of the library)
@@ -833,6 +886,7 @@ class Tournament:
         `openings`: as Match.play; with a book every pair's dict gains "opening"."""
         if collect not in (False, True, "device"):
             raise ValueError("collect must be False, True or 'device'")
+        _refuse_train_targets(self.engines, "tournament")
         if openings is not _KEEP and _book_key(openings) != self._book:
             self.set_openings(openings)
         want = (int(sink) if collect else -1, -1 if first_mover is None else int(first_mover))

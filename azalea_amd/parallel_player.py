@@ -76,7 +76,7 @@ class Player:
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
-                 openings=None, playout_cap=None, resign=None, early_stop=False):
+                 openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -125,7 +125,15 @@ class Player:
         leads by more than the selects still to come.  It is applied again whenever the engine is made again.  A
         ValueError -- here, before any engine is made -- with device_match=True (a match searches every ply in full),
         when the games would run through the host loop, or for a value that is not a bool.  Its effect on playing
-        strength and training efficiency is not measured."""
+        strength and training efficiency is not measured.
+        `train_targets` (NOT the reference's behaviour, whose rows are one-hot from exploration_depth on and carry the
+        game's outcome alone; off by default): "visits", a (policy_rows, value_mix) pair or a {"policy_rows": ...,
+        "value_mix": ...} dict sets Engine.set_train_targets (include/azx.h has the definition) on the self-play engine
+        this Player builds, device self-play or external_batch: the recorded rows are the root's visit shares at every
+        ply, and / or the reward is (1 - value_mix) * z + value_mix * v.  The games themselves are untouched.  It is
+        applied again whenever the engine is made again.  A ValueError -- here, before any engine is made -- with
+        device_match=True (a match's harvest records the reference's rows and the outcome), when the games would run
+        through the host loop, or for anything normalize_train_targets refuses.  DESIGN 7.12 has what is measured."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -153,6 +161,7 @@ class Player:
         self.playout_cap = self._check_playout_cap(playout_cap)
         self.resign = self._check_resign(resign)
         self.early_stop = self._check_early_stop(early_stop)
+        self.train_targets = self._check_train_targets(train_targets)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -334,6 +343,27 @@ class Player:
                              "runs every search to its last simulation")
         return True
 
+    def _check_train_targets(self, train_targets):
+        """`train_targets` as a (policy_rows, value_mix) pair, or None for off; a ValueError naming what does not hold."""
+        train_targets = normalize_train_targets(train_targets)
+        if train_targets is None:
+            return None
+        if self.device_match:
+            raise ValueError("train_targets is a self-play option: a device match's harvest records the reference's "
+                             "rows and the outcome (engine.Match refuses an engine with training targets set)")
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("train_targets needs the games to run in a device engine (a single agent whose Policy "
+                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
+                             "which records the reference's rows and the outcome")
+        return train_targets
+
+    def train_targets_stats(self):
+        """Engine.train_targets_stats() of the self-play engine, or None while there is none or train_targets is not set."""
+        if self.train_targets is None or self._engine is None:
+            return None
+        return self._engine.train_targets_stats()
+
     def early_stop_stats(self):
         """Engine.early_stop_stats() of the self-play engine, or None while there is none or early_stop is not set."""
         if not self.early_stop or self._engine is None:
@@ -482,6 +512,8 @@ class Player:
                 self._engine.set_resign(*self.resign)
             if self.early_stop:
                 self._engine.set_early_stop(True)
+            if self.train_targets is not None:
+                self._engine.set_train_targets(*self.train_targets)
             self._engine_key = key
         return self._engine
 
@@ -628,6 +660,39 @@ def normalize_playout_cap(cap):
     if fast < 1:
         raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
     return full_prob, fast
+
+
+def normalize_train_targets(train_targets):
+    """(policy_rows, value_mix) of "visits" (= ("visits", 0.0)), of a pair or of a {"policy_rows": ..., "value_mix": ...}
+    mapping; None for None / False and for the pair that is "off", ("reference", 0.0).  A ValueError unless policy_rows
+    is "reference" or "visits" and value_mix a number in [0, 1]."""
+    if train_targets is None or train_targets is False:
+        return None
+    if isinstance(train_targets, str):
+        if train_targets != "visits":
+            raise ValueError("train_targets must be 'visits', a (policy_rows, value_mix) pair or a dict with those "
+                             "keys, got %r" % (train_targets,))
+        return "visits", 0.0
+    if isinstance(train_targets, dict):
+        if set(train_targets) != {"policy_rows", "value_mix"}:
+            raise ValueError("train_targets as a dict needs exactly the keys 'policy_rows' and 'value_mix', got %r"
+                             % (sorted(map(str, train_targets)),))
+        rows, mix = train_targets["policy_rows"], train_targets["value_mix"]
+    elif isinstance(train_targets, (tuple, list)) and len(train_targets) == 2:
+        rows, mix = train_targets
+    else:
+        raise ValueError("train_targets must be 'visits', a (policy_rows, value_mix) pair or a dict with those keys, "
+                         "got %r" % (train_targets,))
+    if rows not in ("reference", "visits"):
+        raise ValueError("train_targets: policy_rows must be 'reference' or 'visits', got %r" % (rows,))
+    if isinstance(mix, (bool, np.bool_)) or not isinstance(mix, (int, float, np.integer, np.floating)):
+        raise ValueError("train_targets: value_mix must be a number in [0, 1], got %r" % (mix,))
+    mix = float(mix)
+    if not 0.0 <= mix <= 1.0:                  # (NaN fails both comparisons)
+        raise ValueError("train_targets: value_mix must be in [0, 1], got %r" % (mix,))
+    if rows == "reference" and mix == 0.0:
+        return None
+    return rows, mix
 
 
 def normalize_early_stop(early_stop):

@@ -356,8 +356,23 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     self-play Player built here (Player(early_stop=True)), so the lock-step ranks and the actors play under it too;
     the random-mover player that fills the first buffer does NOT get it.  One log line says whether it is on.  A
     ValueError, before anything is built, for a value that is not a bool; Player refuses it where the games would run
-    through the host loop.  Its effect on playing strength and on training efficiency is not measured."""
-    from .parallel_player import normalize_early_stop
+    through the host loop.  Its effect on playing strength and on training efficiency is not measured.
+
+    config["train_targets"] = "visits", (policy_rows, value_mix) or {"policy_rows": ..., "value_mix": ...} (default
+    absent; NOT the reference's behaviour, and outside every parity claim): what the recorded self-play rows teach.
+    policy_rows "visits" records the root's visit shares at every ply where the reference records a one-hot row from
+    exploration_depth on; value_mix = lambda in [0, 1] stores (1 - lambda) * z + lambda * v as the reward, v the
+    search's own root value for the mover (Engine.set_train_targets, include/azx.h has the definition).  The games
+    themselves are move for move the same.  It goes to the one self-play Player built here
+    (Player(train_targets=...)), so the lock-step ranks and the actors play under it too; the random-mover player
+    that fills the first buffer does NOT get it.  One log line says whether it is on.  A ValueError, before anything
+    is built, for anything normalize_train_targets refuses; Player refuses it where the games would run through the
+    host loop.  DESIGN 7.12 has what is measured of its effect."""
+    from .parallel_player import normalize_early_stop, normalize_train_targets
+    try:
+        train_targets = normalize_train_targets(config.get("train_targets"))
+    except ValueError as exc:
+        raise ValueError("config['train_targets']: %s" % exc) from None
     try:
         early_stop = normalize_early_stop(config.get("early_stop"))
     except ValueError as exc:
@@ -410,7 +425,12 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
                     random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
-                    resign=resign, early_stop=early_stop)
+                    resign=resign, early_stop=early_stop, train_targets=train_targets)
+    if leader:
+        logging.info("training targets (config['train_targets']): %s",
+                     "off" if train_targets is None else
+                     "on -- NOT the reference's behaviour: policy rows '%s', reward (1 - %g) * z + %g * v"
+                     % (train_targets[0], train_targets[1], train_targets[1]))
     if leader:
         logging.info("early stop (config['early_stop']): %s",
                      "on -- NOT the reference's behaviour: a search drawn at temperature 0 stops once its leading root "

@@ -558,6 +558,52 @@ int azx_set_early_stop(azx_engine *e, int on);
  * own: azx_debug_counters keeps its 16 words. */
 int azx_early_stop_stats(azx_engine *e, int64_t out4[4]);
 
+/* Training targets of the rows throughput self-play records: visit-share policy rows and z/q-blended rewards.  NOT the
+ * reference's behaviour (off by default, outside every parity claim): the reference records as_distribution(counts, T)
+ * with the T of the move draw -- one-hot on the most-visited child from exploration_depth on, because its
+ * Policy.choose_action has one `probs` array for the draw and for the row -- and gives every row of a game the final
+ * outcome z.  AlphaZero trains on the visit distribution at every ply and makes only the played move greedy.
+ *   The move draw is untouched: the same weights, the same total, the same Philox words, the same chosen child.  Row
+ * metric 2 stays the log-probability of the drawn move under the draw's distribution.  A game is move for move the game
+ * the same seed plays with the option off; only what its rows teach differs.
+ *   policy_rows = AZX_ROWS_VISITS: the row written at a recorded ply is row[j] = nv_j / nv_sum.  nv_j are the root
+ * children's num_visits, integers held in float32, and nv_sum is their sum, which is exact.  The division is ONE float32
+ * IEEE division: the expression the reference row already is at T = 1, so rows of T = 1 plies are bit for bit what they
+ * were.  Rows of greedy plies (ply >= exploration_depth or temperature == 0) and of plies with any other T become the
+ * visit shares.  A root with nv_sum == 0 cannot occur at a recorded ply; if it does, the reference row is written.
+ *   value_mix = lambda > 0: the move draw leaves v = root.total_value / root.num_visits in row metric 7 -- the resign
+ * statistic of azx_set_resign, the mover's view, the same float resignation stores there -- and the harvest stores
+ * reward = (1 - lambda) * z + lambda * v.  z is the reward as it is without the option, already in the mover's view, as
+ * v is.  The blend is two float32 products and one sum, unfused.  If v is not finite the reward is z; lambda = 0 stores
+ * z itself, with no arithmetic.  azx_play_stats.sum_reward_last keeps summing z.
+ *   Row metric 7 carries v whenever resignation or either part of this option is set, and 0 otherwise.
+ *   Beside the other options.  A fast ply of a playout cap still records nothing.  Resignation judges as before, and
+ * the rows of a resigned game blend the conceded z.  Under early stop the row is the visit shares AT THE STOP: early
+ * stop's statement that the skipped selects cannot change the row holds for the reference's one-hot row only, not for
+ * AZX_ROWS_VISITS -- the move is still the one a full search plays, the row is that of the shorter search.
+ *   It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move launches,
+ * the pipelined half-pools, a registered external evaluator) and to nothing else: every other launch reads "off", and
+ * azx_match_play / azx_tournament_play refuse an engine with the option set with AZX_EINVAL before touching any engine
+ * (their harvest records the reference's rows and the outcome).
+ *   value_mix must be in [0, 1]; NaN, a value outside [0, 1] or an unknown policy_rows is AZX_EINVAL and leaves the
+ * setting in place.  (AZX_ROWS_REFERENCE, 0.0f) is "off", the state of an engine on which the call was never made.  May
+ * be called between calls, for any evaluator; rows of games in progress are written under the new setting from their
+ * next ply on, and a game is harvested under the setting of the call that harvests it.  The call zeroes the statistics
+ * of azx_train_targets_stats.  With the option never set, or cleared, every call launches the same kernels and returns
+ * the same bytes as without these entry points: rows, rewards, metrics (metric 7 = 0), play statistics.
+ * azx_kernel_info reports targets=off or targets=<visits|reference>/<value_mix>.  What the option does to playing
+ * strength is given in DESIGN 7.12 as far as it is measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_train_targets). */
+#define AZX_ROWS_REFERENCE 0   /* row = as_distribution(counts, T of the move draw): today's rows */
+#define AZX_ROWS_VISITS    1   /* row = counts / sum(counts) at every recorded ply, whatever T */
+int azx_set_train_targets(azx_engine *e, int policy_rows, float value_mix);
+int azx_get_train_targets(azx_engine *e, int *policy_rows, float *value_mix);
+/* out4 = {rows recorded while the option is on, of those the rows of greedy plies, of those the rows with more than one
+ * visited child (the rows that differ from the reference's), 0}, counted since the last azx_set_train_targets by the
+ * lane that writes the row's metrics.  They live in an array of their own: azx_debug_counters keeps its 16 words. */
+int azx_train_targets_stats(azx_engine *e, int64_t out4[4]);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,

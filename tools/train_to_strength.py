@@ -15,6 +15,11 @@ settings, temperature-1 sampling for the first `exploration_depth` plies and no 
     ... --world 3           the same under torch.distributed with 3 processes ON THIS ONE GPU (gloo; a functional soak of
                             the actor / learner topology, not a benchmark): rank 0 trains and pulls, ranks 1-2 play ahead
 
+    ... --train-targets visits | visits:0.5 | reference:0.5
+                            config["train_targets"]: what the self-play rows teach (visit-share policy rows, reward
+                            (1 - mix) * z + mix * v) -- NOT the reference's behaviour; tools/strength_train_targets.py
+                            plays networks trained with and without it against each other
+
     ... --vs-shipped        also: the trained network against the REFERENCE'S SHIPPED MODEL (models/hex11-20180712-3362.policy.pth,
                             11x11 6x64: its tensors are the golden fixture tests/golden/g8_checkpoint.npz), same search
                             settings on both sides -- an absolute yardstick
@@ -60,6 +65,29 @@ def tournament(policies, n, rounds):
     return {"%d-%d" % k: [int(x) for x in v] for k, v in out.items()}
 
 
+def parse_train_targets(text):
+    """--train-targets: None, "visits" or "<policy_rows>:<value_mix>" as config["train_targets"] takes it."""
+    if not text or text == "off":
+        return None
+    if ":" in text:
+        rows, mix = text.split(":", 1)
+        return rows, float(mix)
+    return text
+
+
+def train_config(args):
+    """The config `train` gets: the reference's loop with everything on the device."""
+    config = dict(seed=args.seed, device="cuda:0", game="azalea_amd.game.hex.HexGame", board_size=args.board,
+                  replaybuf_size=args.replay, replaybuf_oversampling=args.oversampling, batch_size=128,
+                  lr_initial=args.lr, lr_decay=args.lr_decay, lr_decay_epochs=args.lr_decay_epochs or max(1, args.epochs - 1), momentum=0.9,
+                  l2_regularization=1e-4, total_epochs=args.epochs, selfplay_games=args.games, log_interval=args.log_interval,
+                  model_checkpoint_interval=0, train_mover_view=args.mover_view)
+    targets = parse_train_targets(getattr(args, "train_targets", None))
+    if targets is not None:
+        config["train_targets"] = targets
+    return config
+
+
 class LossLog(logging.Handler):
     """policy_trainer's "step %d loss %.4f steps/sec %.2f" lines (policy_trainer.py:101-107), kept as numbers."""
 
@@ -79,11 +107,7 @@ def run(args):
     logging.getLogger().setLevel(logging.INFO)
     policy = make_policy(args, args.seed)
     start = copy.deepcopy(policy.net.state_dict())
-    config = dict(seed=args.seed, device="cuda:0", game="azalea_amd.game.hex.HexGame", board_size=args.board,
-                  replaybuf_size=args.replay, replaybuf_oversampling=args.oversampling, batch_size=128,
-                  lr_initial=args.lr, lr_decay=args.lr_decay, lr_decay_epochs=args.lr_decay_epochs or max(1, args.epochs - 1), momentum=0.9,
-                  l2_regularization=1e-4, total_epochs=args.epochs, selfplay_games=args.games, log_interval=args.log_interval,
-                  model_checkpoint_interval=0, train_mover_view=args.mover_view)
+    config = train_config(args)
     steps = args.epochs * (args.replay // 128 + (1 if args.replay % 128 else 0))
     every = steps // args.checkpoints if args.checkpoints else 0
     config["model_checkpoint_interval"] = every
@@ -148,7 +172,8 @@ def run(args):
         curve = {"steps": [0] + marks + [steps], "elo": elos, "games_per_pair": args.curve_rounds, "tallies": tallies}
     return {"what": "train() on one GPU, then trained vs starting network (agent 1 vs agent 0), %d games" % games,
             "net": "%dx%d on %dx%d" % (args.blocks, args.chans, args.board, args.board), "sims": args.sims,
-            "train_step": history.get("train_step"), "train_mover_view": bool(args.mover_view), "epochs": args.epochs, "steps": steps, "train_seconds": secs,
+            "train_step": history.get("train_step"), "train_mover_view": bool(args.mover_view),
+            "train_targets": config.get("train_targets"), "epochs": args.epochs, "steps": steps, "train_seconds": secs,
             "steps_per_sec_incl_selfplay_and_fill": steps / secs, "selfplay_rows_consumed": steps * 128 / args.oversampling,
             "loss_by_step": losses.rows[1:],          # [step, mean loss over the interval, steps/s incl. self-play]
             "tally_untrained_draw_trained": [w_old, draws, w_new], "trained_win_rate": w_new / max(1, games),
@@ -180,6 +205,8 @@ def main():
     ap.add_argument("--lr-decay", type=float, default=0.1)
     ap.add_argument("--lr-decay-epochs", type=int, default=0, help="StepLR period in epochs (default: only the last epoch decays)")
     ap.add_argument("--mover-view", action="store_true", help="config['train_mover_view']: not the reference's batches")
+    ap.add_argument("--train-targets", default=None,
+                    help="config['train_targets']: visits, visits:0.5, reference:0.5 -- not the reference's rows")
     ap.add_argument("--overlap", action="store_true", help="config['selfplay_overlap']: self-play runs while the steps run")
     ap.add_argument("--world", type=int, default=1)
     ap.add_argument("--selfplay-mode", default="actor_learner")
