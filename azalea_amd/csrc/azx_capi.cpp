@@ -25,6 +25,7 @@
 #include "match_kernels.h"
 #include "playout_cap.h"
 #include "resign.h"
+#include "tower_tiles.h"
 
 #ifndef AZX_SRC_SHA
 #define AZX_SRC_SHA "unknown"      // the Makefile passes the digest of the kernel sources (profiles are keyed to it)
@@ -524,6 +525,20 @@ extern "C" int azx_debug_stagger(azx_engine *e, int32_t *out4) {
     HIPCHECK(hipMemcpyAsync(out4, e->stagger_ctr, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(hipStreamSynchronize(e->stream));
     return AZX_OK;
+}
+
+// host only: the position-tile map k_tower_f16x3_s16 would run with on this board size (tower_tiles.h)
+extern "C" int azx_debug_tower_tiles(int board_size, const char *map, uint8_t *rows256, uint32_t *skip4, int32_t *light_slot) {
+    if (!map || !rows256 || !skip4 || !light_slot) return fail(AZX_EINVAL, "null argument");
+    if (board_size < 2 || board_size * board_size > 121)
+        return fail(AZX_EINVAL, "tower tiles: board size %d outside the fused tower's 2..11", board_size);
+    if (strcmp(map, "edge") && strcmp(map, "rows")) return fail(AZX_EINVAL, "tower tiles: map '%s' is neither edge nor rows", map);
+    AzxTowerTiles t;
+    azx_tower_tiles_build(board_size, !strcmp(map, "edge"), &t);
+    memcpy(rows256, t.row, sizeof t.row);
+    for (int w = 0; w < 4; ++w) skip4[w] = t.skip[w];
+    *light_slot = AZX_TOWER_LIGHT_SLOT;
+    return t.edge;
 }
 
 extern "C" int azx_debug_set_queue_cap(azx_engine *e, int64_t rows) {

@@ -13,6 +13,7 @@
 // k_heads: value/policy heads + masked softmax, one block per board.
 // k_*_generic: plain VALU fallback for channel counts the MFMA tiling does not cover.
 #include "net_priv.h"
+#include "tower_tiles.h"
 
 // Diagnostic builds only (-DAZX_NET_ABLATE=bits): time the f16x3 tower without its A-fragment LDS
 // reads (1), MFMAs (2) or weight loads (4).  Outputs are garbage; the shipped build uses 0.
@@ -318,15 +319,24 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
     const int lrow = li < 8 ? li ^ 4 : li;
     const int lchunk = 128 * (lh & 1) + 16 * (lh >> 1);
 
+    // Which cell a lane owns in tile slot m comes from the network's tile map (tower_tiles.h): LDS row 128 * board +
+    // cell of the block's image, so the board, too, is per lane.  The identity map (AZX_TOWER_TILES=rows) gives the
+    // wave the rows 64 wh + 16 m + lrow of board wb.  Under the edge map the wave's slot LT holds 16 cells of one edge
+    // of the two boards: `skip` names the taps that are padding for all of them (wave-uniform, on the scalar unit).
+    constexpr int LT = AZX_TOWER_LIGHT_SLOT;
+    static_assert(LT == MT - 1, "the k-loop skips the lagging last tile");
+    const uint8_t *tmap = P.tile_map + 64 * wave + lrow;
+    const uint32_t skip = __builtin_amdgcn_readfirstlane((uint32_t)(P.tile_skip >> (9 * wave)) & 0x1ffu);
     unsigned long long tapok = 0ull;                     // bit tap*4 + m
-    int rbase[MT], ry_[MT], rx_[MT];
+    int rbase[MT], cell0_[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-        const int r = 64 * wh + 16 * m + lrow;
+        const int L = tmap[16 * m];
+        const int r = L & 127;
         const int ry = r / N, rx = r - ry * N;
-        ry_[m] = ry;
-        rx_[m] = rx;
-        rbase[m] = x_off + r * ROWB + lchunk;            // 8 channels (16 B) per k-group
+        // the stem's first neighbour of this cell in its board's staged (N + 2)^2 cells, -1 for a dead row
+        cell0_[m] = r < ncells ? 2 * ROWB + (L >> 7) * board_b + 121 * ROWB + ry * (N + 2) + rx : -1;
+        rbase[m] = 2 * ROWB + L * ROWB + lchunk;         // 8 channels (16 B) per k-group
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int yy = ry + tap / 3 - 1, xx = rx + tap % 3 - 1;
@@ -373,12 +383,18 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
                     if (kind != 0) res[m][n][j] = v;
                     v4[j] = v;
                 }
-                if (AZX_SAT_TRACK) satmax = fmaxf(fmaxf(satmax, v4[0]), fmaxf(v4[1], fmaxf(v4[2], v4[3])));
+                if (AZX_SAT_TRACK) {
+                    satmax = fmaxf(fmaxf(satmax, v4[0]), fmaxf(v4[1], fmaxf(v4[2], v4[3])));
+                    // taken here: with branches in the k-loop the compiler otherwise sinks the whole maximum of a
+                    // layer into the next layer's epilogue and keeps (spills) the 64 values until then
+                    asm volatile("" : "+v"(satmax));
+                }
                 uint2 h4, l4;
                 split2_f16(v4[0], v4[1], h4.x, l4.x);
                 split2_f16(v4[2], v4[3], h4.y, l4.y);
                 // channels cb..cb+3 = half a chunk: k-half n >> 1, k-group 2 (n & 1) + (lh >> 1), bytes 8 (lh & 1)..
-                unsigned char *pw = X + (64 * wh + 16 * m + lrow) * ROWB + 128 * (lh >> 1) + 16 * n + 8 * (lh & 1);
+                // of the lane's own row: rbase[m] without its lchunk
+                unsigned char *pw = smem + rbase[m] + (112 * (lh >> 1) - 120 * (lh & 1)) + 16 * n;
                 *reinterpret_cast<uint2 *>(pw) = h4;
                 *reinterpret_cast<uint2 *>(pw + 64) = l4;
             }
@@ -414,8 +430,8 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             uint32_t onehot = 0u;                        // bit k = 3*tap + colour of that neighbour
-            if (64 * wh + 16 * m + lrow < ncells) {
-                const unsigned char *c0 = cells + ry_[m] * NH + rx_[m];
+            if (cell0_[m] >= 0) {
+                const unsigned char *c0 = smem + cell0_[m];          // in the cells of the lane's own board
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) {
                     const uint32_t v = c0[(tap / 3) * NH + tap % 3];
@@ -437,7 +453,7 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
         }
         float4 sb4[NT];
         load_bias(P.stem_b, sb4);
-        __syncthreads();   // every wave has read the staged cells: the tail rows are free again
+        __syncthreads();   // every wave of the block has read the staged cells of both boards: the tail rows are free again
         epilogue(acc, sb4, std::integral_constant<int, 2>{});
     }
     __syncthreads();
@@ -477,16 +493,45 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
             if (part) xl[mm] = *reinterpret_cast<const f16x8 *>(pa);
             else xh[mm] = *reinterpret_cast<const f16x8 *>(pa);
         };
+        // asked where it is used, from the scalar word (opaque, so that no lane mask of it lives across the k-loop)
+        auto tap_skipped = [&](int tap) __attribute__((always_inline)) -> bool {
+            uint32_t s = skip;
+            asm volatile("" : "+s"(s));
+            return (s >> tap) & 1u;
+        };
+        auto fence = [&](int q) __attribute__((always_inline)) {
+#if AZX_S16_FENCE == 2
+            __builtin_amdgcn_sched_barrier(0);
+#elif AZX_S16_FENCE == 1
+            if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+#elif AZX_S16_FENCE == 3
+            if (q % 6 == 5) __builtin_amdgcn_sched_barrier(0);
+#elif AZX_S16_FENCE == 4
+            if (q % 2 == 1) __builtin_amdgcn_sched_barrier(0);
+#endif
+        };
+        // product j = 0..5 of position tile m in half h: channel tile 2 h + j / 3, operand pair j % 3
+        auto mfma1 = [&](int h, int m, int j) __attribute__((always_inline)) {
+            const int n = 2 * h + j / 3, p = j % 3;
+            const f16x8 wv = p == 1 ? wl_[n] : wh_[n];
+            const f16x8 xv = p == 2 ? xl[m] : xh[m];
+            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv, xv, acc[m][n], 0, 0, 0);
+        };
+        // k-step t = 0..17: tap t/2, channels 32 (t%2) .. +31: 2 x 24 MFMAs, 16 loads.  Where the tap is padding for
+        // every row of the light tile LT (= MT - 1; `skip`, a scalar bit test) the wave branches over that tile's 6
+        // MFMAs in both halves: each of those products would have added +-0 to an accumulator that started as +0,
+        // which leaves every bit as it is (x + (-0) = x, +0 + (-0) = +0), and the order of the others is unchanged.
+        // The next step's fragments of tile MT - 2, which sit in the shadow of those MFMAs, are requested all the same.
+        // The light tile's own two fragment loads stay where they are (for a skipped tap they read the zero rows): a
+        // branch of their own around them cost more than they do (measured, as did issuing the light tile's twelve
+        // MFMAs in one run under one branch: DESIGN 3.2).
 #pragma unroll
         for (int m = 0; m < MT - 1; ++m) { load_x(0, m, 0); load_x(0, m, 1); }
-        // k-step t = 0..17: tap t/2, channels 32 (t%2) .. +31: 2 x 24 MFMAs, 16 loads
 #pragma unroll
         for (int t = 0; t < 18; ++t) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int q = 0; q < 24; ++q) {
-                    const int m = q / 6, n = 2 * h + (q % 6) / 3, p = q % 3;
+                auto step_q = [&](int q) __attribute__((always_inline)) {
                     if (q == 1 || q == 4 || q == 7 || q == 10) {
                         const int idx = (q - 1) / 3;                       // 0..3: tile, part
                         if (h == 0) load_w(stage + t, 2 + (idx >> 1), idx & 1);
@@ -496,18 +541,17 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
                     } else if (h == 1 && q >= 8 && (q % 6 == 2 || q % 6 == 5)) {
                         if (t + 1 < 18) load_x(t + 1, q / 6 - 1, q % 6 == 5);   // tile q/6-1 is done for this step
                     }
-                    const f16x8 wv = p == 1 ? wl_[n] : wh_[n];
-                    const f16x8 xv = p == 2 ? xl[m] : xh[m];
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv, xv, acc[m][n], 0, 0, 0);
-#if AZX_S16_FENCE == 2
-                    __builtin_amdgcn_sched_barrier(0);
-#elif AZX_S16_FENCE == 1
-                    if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-#elif AZX_S16_FENCE == 3
-                    if (q % 6 == 5) __builtin_amdgcn_sched_barrier(0);
-#elif AZX_S16_FENCE == 4
-                    if (q % 2 == 1) __builtin_amdgcn_sched_barrier(0);
-#endif
+                    mfma1(h, q / 6, q % 6);
+                    fence(q);
+                };
+#pragma unroll
+                for (int q = 0; q < 6 * LT; ++q) step_q(q);
+                if (!tap_skipped(t >> 1)) {
+#pragma unroll
+                    for (int q = 6 * LT; q < 24; ++q) step_q(q);
+                } else if (h == 1 && t + 1 < 18) {
+                    load_x(t + 1, MT - 2, 0);
+                    load_x(t + 1, MT - 2, 1);
                 }
             }
         }
@@ -554,22 +598,22 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
                 hacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ks], xh, hacc, 0, 0, 0);
                 hacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], xl, hacc, 0, 0, 0);
             }
-            const int row = 64 * wh + 16 * m + lrow;
-            if (live && row < ncells) {
+            const int L = tmap[16 * m], row = L & 127, el = e0 + (L >> 7);     // the lane's own cell and board
+            if (el < n_eval && row < ncells) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = 4 * lh + r;
-                    if (o < 6) hfeat[((size_t)e * 6 + o) * ncells + row] = fmaxf(hacc[r] + hbv[r], 0.0f);
+                    if (o < 6) hfeat[((size_t)el * 6 + o) * ncells + row] = fmaxf(hacc[r] + hbv[r], 0.0f);
                 }
             }
         }
     }
-    if (live && act_out != nullptr) {
-        float *out = act_out + (size_t)e * ncells * C;
+    if (act_out != nullptr) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            const int row = 64 * wh + 16 * m + lrow;
-            if (row < ncells) {
+            const int L = tmap[16 * m], row = L & 127, el = e0 + (L >> 7);
+            float *out = act_out + (size_t)el * ncells * C;
+            if (el < n_eval && row < ncells) {
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
                     *reinterpret_cast<float4 *>(out + row * C + 16 * n + 4 * lh) =
@@ -2104,8 +2148,15 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     { const char *v = getenv("AZX_WIDE_STREAMS"); net->opt_wsplit = std::min(4, std::max(1, v ? atoi(v) : 2)); }
     { const char *v = getenv("AZX_HEADS"); net->opt_heads_mfma = !(v && !strcmp(v, "valu")); }
     { const char *v = getenv("AZX_PACK"); net->pack_on_host = v && !strcmp(v, "host"); }
+    // k_tower_f16x3_s16's position tiles: AZX_TOWER_TILES=rows keeps 16 consecutive cells per tile, the default (edge)
+    // gives every wave one tile of pure edge cells whose padding taps it skips (tower_tiles.h)
+    const bool x3 = net->tower_variant == 4 && !net->tower_f16;
+    AzxTowerTiles tiles;
+    bool want_edge = true;
+    { const char *v = getenv("AZX_TOWER_TILES"); want_edge = !(v && !strcmp(v, "rows")); }
+    azx_tower_tiles_build(N, x3 && want_edge, &tiles);
     {
-        char b[260];
+        char b[320];
         const char *tower = "k_stem_generic + k_conv_generic (VALU)";
         if (net->tower_variant == 4) tower = net->tower_f16 ? "k_tower_f16_s16" : "k_tower_f16x3_s16";
         else if (net->tower_variant == 5) tower = net->tower_f16 ? "k_stem_wide_f16 + k_conv_wide_f16_s16 per layer"
@@ -2114,8 +2165,10 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
         else if (net->tower_variant == 2) tower = "k_tower_mfma<64,6,1,2,2> (fp32 MFMA)";
         else if (net->tower_variant == 3) tower = "k_tower_mfma<32,6,2,2,1> (fp32 MFMA)";
         const bool hm = net->tower_variant == 4 && net->opt_heads_mfma && ncells <= 128;
-        snprintf(b, sizeof b, "%s + %s (%dx%d on %dx%d; AZX_TOWER=%s AZX_WIDE_STREAMS=%d AZX_HEADS=%s AZX_PACK=%s)",
+        snprintf(b, sizeof b, "%s + %s (%dx%d on %dx%d; AZX_TOWER=%s AZX_TOWER_TILES=%s AZX_WIDE_STREAMS=%d AZX_HEADS=%s AZX_PACK=%s)",
                  tower, hm ? "k_heads_mfma" : "k_heads", blocks, chans, N, N, want_fp32 ? "fp32" : net->tower_f16 ? "f16" : "default",
+                 // like the other switches, the setting is reported by every engine; only k_tower_f16x3_s16 has a tile map
+                 want_edge && (tiles.edge || !x3) ? "edge" : "rows",
                  net->opt_wsplit, net->opt_heads_mfma ? "mfma" : "valu", net->pack_on_host ? "host" : "device");
         net->info = b;
     }
@@ -2144,6 +2197,16 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     if (net->tower_variant == 4) net->lds_bytes = (size_t)F16X3_BPB * 128 * 272 + 2 * 272;   // boards + the zero rows (two in k_tower_f16x3_s16)
     if (net->tower_variant == 5) net->lds_bytes = (size_t)(ncells + 2) * WIDE_ROWB;   // two zero rows + the chunk image
     net->d.sat_flag = nalloc<uint32_t>(net, 4);
+    if (x3) {     // once per network: the kernel reads the table through NetDev
+        uint8_t *tm = nalloc<uint8_t>(net, sizeof tiles.row);
+        if (tm && hipMemcpy(tm, tiles.row, sizeof tiles.row, hipMemcpyHostToDevice) != hipSuccess) tm = nullptr;
+        if (!tm) {
+            azx_net_destroy(net);
+            return nfail(AZX_ENOMEM, "net: the tower's tile map could not be put on the device");
+        }
+        net->d.tile_map = tm;
+        for (int w = 0; w < 4; ++w) net->d.tile_skip |= (unsigned long long)(tiles.skip[w] & 0x1ffu) << (9 * w);
+    }
     if (!net->d.sat_flag || hipDeviceSynchronize() != hipSuccess) {     // (the zero fills ran on the null stream)
         azx_net_destroy(net);
         return nfail(AZX_ENOMEM, "net: hipMalloc failed");

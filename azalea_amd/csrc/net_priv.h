@@ -37,6 +37,10 @@ struct NetDev {
     // half.  The epilogues keep the largest `hi` they stored and OR 1 in here when it is not finite; the host reads
     // the word where it synchronises anyway and reports AZX_ERANGE (azx_net_check_range).
     uint32_t *sat_flag;
+    // k_tower_f16x3_s16's position tiles (tower_tiles.h): [wave][slot][tile row] -> LDS row 128 * board + cell, and the
+    // taps each wave skips for its light tile, 9 bits per wave (0 under AZX_TOWER_TILES=rows)
+    const uint8_t *tile_map;
+    unsigned long long tile_skip;
 };
 
 // The `lo` halves of the hi+lo f16 split (activations: split2_f16; weights: the packers) keep AZX_LO_BITS explicit

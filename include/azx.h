@@ -647,6 +647,15 @@ int azx_debug_set_queue_cap(azx_engine *e, int64_t rows);
  * moves so far, [3] = those whose second sub-launch found no row to evaluate.  All 0 before the first pipelined play.
  * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_stagger). */
 int azx_debug_stagger(azx_engine *e, int32_t *out4);
+/* tests, host only (no engine, no GPU): the position-tile map of the fused split-f16 tower k_tower_f16x3_s16 for a
+ * board size 2..11.  map = "edge" (the default of AZX_TOWER_TILES, read once per network like AZX_TOWER) or
+ * "rows".  rows256[64 * wave + 16 * slot + tile row] = the row 128 * board + cell of the block's two-board LDS image
+ * (cell >= board_size^2: a dead row); skip4[wave] = the taps (bit 3 * (dy + 1) + dx + 1) the wave does not compute for
+ * its tile in slot *light_slot, each of them padding for all 16 rows of that tile.  Returns 1 when the edge map exists
+ * for the size, 0 when the map is `rows` (always for "rows"), AZX_EINVAL otherwise.  azx_kernel_info names the map an
+ * engine runs (AZX_TOWER_TILES=edge|rows; engines on another tower report the setting, which they do not use).  Results do not depend on the map, bit for bit.
+ * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_tower_tiles). */
+int azx_debug_tower_tiles(int board_size, const char *map, uint8_t *rows256, uint32_t *skip4, int32_t *light_slot);
 
 /* ---- evaluation matches between two engines, entirely on the device -------------------------
  * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_match_create).

@@ -13,5 +13,6 @@ _lib.OPTIONAL.update(["azx_set_playout_cap", "azx_playout_cap_is_full", "azx_pla
 _lib.OPTIONAL.update(["azx_set_resign", "azx_clear_resign", "azx_resign_is_exempt", "azx_resign_stats", "azx_resign_value"])
 _lib.OPTIONAL.update(["azx_set_early_stop", "azx_early_stop_stats"])
 _lib.OPTIONAL.update(["azx_set_train_targets", "azx_get_train_targets", "azx_train_targets_stats"])
+_lib.OPTIONAL.update(["azx_debug_tower_tiles"])
 sys.argv = ["bench.py"] + sys.argv[2:]
 runpy.run_path(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), run_name="__main__")
