@@ -170,6 +170,10 @@ SYMBOLS = {
     "azx_set_train_targets": (C.c_int, [_vp, C.c_int, C.c_float]),
     "azx_get_train_targets": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "azx_train_targets_stats": (C.c_int, [_vp, _i64p]),
+    # forced playouts at the root and policy target pruning (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_forced_playouts": (C.c_int, [_vp, C.c_float, C.c_int]),
+    "azx_get_forced_playouts": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "azx_forced_playouts_stats": (C.c_int, [_vp, _i64p]),
 }
 
 class TrainConfig(C.Structure):

@@ -145,11 +145,15 @@ struct azx_engine {
     int tt_rows = AZX_ROWS_REFERENCE;
     float tt_mix = 0.0f;
     bool tt_on() const { return tt_rows != AZX_ROWS_REFERENCE || tt_mix > 0.0f; }
+    // forced playouts and policy target pruning (azx_set_forced_playouts): handed to the same launches, by the same scope
+    float fp_k = 0.0f;
+    int fp_prune = 0;
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
 // (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) and early stop
-// (azx_set_early_stop) travel the same way, and so do the training targets (azx_set_train_targets).
+// (azx_set_early_stop) travel the same way, and so do the training targets (azx_set_train_targets) and forced
+// playouts (azx_set_forced_playouts).
 struct CapScope {
     DevEngine &d;
     explicit CapScope(azx_engine *e) : d(e->d) {
@@ -165,12 +169,14 @@ struct CapScope {
         }
         if (e->estop_on) d.early_stop = 1;
         d.tt_rows = e->tt_rows; d.tt_mix = e->tt_mix;
+        d.fp_k = e->fp_k; d.fp_prune = e->fp_prune;
     }
     ~CapScope() {
         d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
         d.resign_mode = AZX_RESIGN_OFF; d.resign_min_ply = 0; d.resign_thr = 0.0f; d.resign_keep_m1 = 0u;
         d.early_stop = 0;
         d.tt_rows = AZX_ROWS_REFERENCE; d.tt_mix = 0.0f;
+        d.fp_k = 0.0f; d.fp_prune = 0;
     }
     CapScope(const CapScope &) = delete;
     CapScope &operator=(const CapScope &) = delete;
@@ -301,6 +307,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.resign_ctr, G * RS_COUNT);
     A(d.estop_ctr, G * ES_COUNT);
     A(d.tt_ctr, G * TT_COUNT);
+    A(d.fp_ctr, G * FP_COUNT);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
     A(e->g_rv, G); A(e->g_rw, G); A(e->g_sv, G);
@@ -441,6 +448,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.resign_ctr += b * RS_COUNT;
     v.estop_ctr += b * ES_COUNT;
     v.tt_ctr += b * TT_COUNT;
+    v.fp_ctr += b * FP_COUNT;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
     if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
     if (v.row_k) v.row_k += b * nc;
@@ -471,6 +479,13 @@ static std::string targets_text(const azx_engine *e) {
     if (!e->tt_on()) return "off";
     char t[64];
     snprintf(t, sizeof t, "%s/%.9g", e->tt_rows == AZX_ROWS_VISITS ? "visits" : "reference", (double)e->tt_mix);
+    return t;
+}
+
+static std::string forced_text(const azx_engine *e) {
+    if (!(e->fp_k > 0.0f)) return "off";
+    char t[64];
+    snprintf(t, sizeof t, "%.9g/%s", (double)e->fp_k, e->fp_prune ? "prune" : "noprune");
     return t;
 }
 
@@ -512,6 +527,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " resign=" + resign_text(e) +
                        " estop=" + (e->estop_on ? "on" : "off") +
                        " targets=" + targets_text(e) +
+                       " forced=" + forced_text(e) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -2145,6 +2161,42 @@ extern "C" int azx_train_targets_stats(azx_engine *e, int64_t out4[4]) {
     return AZX_OK;
 }
 
+// ---- forced playouts and policy target pruning (include/azx.h; NOT the reference's behaviour) ------
+extern "C" int azx_set_forced_playouts(azx_engine *e, float k, int prune) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (!(k >= 0.0f && k <= 64.0f))                     // NaN fails both comparisons
+        return fail(AZX_EINVAL, "forced playouts: k must be in [0, 64], got %g", (double)k);
+    if (prune != 0 && prune != 1) return fail(AZX_EINVAL, "forced playouts: prune must be 0 or 1, got %d", prune);
+    if (k == 0.0f && prune == 1)
+        return fail(AZX_EINVAL, "forced playouts: pruning needs forcing (k > 0): the prune gives back at most the forced quota");
+    ENGINE_GUARD(e);
+    HIPCHECK(hipMemsetAsync(e->d.fp_ctr, 0, (size_t)e->d.G * FP_COUNT * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->fp_k = k == 0.0f ? 0.0f : k;                     // (-0.0f is off too)
+    e->fp_prune = prune;
+    return AZX_OK;
+}
+
+extern "C" int azx_get_forced_playouts(azx_engine *e, float *k, int *prune) {
+    if (!e || !k || !prune) return fail(AZX_EINVAL, "null argument");
+    *k = e->fp_k;
+    *prune = e->fp_prune;
+    return AZX_OK;
+}
+
+extern "C" int azx_forced_playouts_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * FP_COUNT);
+    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.fp_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < 4; ++j) out4[j] = 0;
+    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
+        for (int j = 0; j < FP_COUNT; ++j) out4[j] += (int64_t)hc[g * FP_COUNT + j];
+    return AZX_OK;
+}
+
 extern "C" int azx_resign_value(azx_engine *e, float *v) {
     if (!e || !v) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
@@ -2480,6 +2532,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
         return fail(AZX_EINVAL, "engine %s has training targets set: a match's harvest records the reference's rows and "
                                 "the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))",
                     a->tt_on() ? "a" : "b");
+    if (a->fp_k > 0.0f || b->fp_k > 0.0f)
+        return fail(AZX_EINVAL, "engine %s has forced playouts set: a match searches and draws every ply as the "
+                                "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", a->fp_k > 0.0f ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2755,6 +2810,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->tt_on())
             return fail(AZX_EINVAL, "engine %d has training targets set: a tournament's harvest records the reference's "
                                     "rows and the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->fp_k > 0.0f)
+            return fail(AZX_EINVAL, "engine %d has forced playouts set: a tournament searches and draws every ply as the "
+                                    "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

@@ -164,7 +164,16 @@ struct DevEngine {
     int32_t tt_rows;            // AZX_ROWS_VISITS: the row is counts / sum(counts) at every recorded ply, whatever T
     float tt_mix;               // lambda: the harvest stores (1 - lambda) * z + lambda * v, v = row metric 7
     unsigned long long *tt_ctr;       // [G][TT_COUNT] per game (no atomics), azx_train_targets_stats' array; the host sums
+    // forced playouts and policy target pruning (azx_set_forced_playouts; NOT the reference's behaviour), handed to the
+    // same launches only and "off" (0.0f, 0) in every other (include/azx.h states the rule)
+    float fp_k;                 // > 0: a full search's root select descends into the lowest-index child with
+                                // n > 0 and n * n < (k * P) * S, if there is one, instead of the PUCT argmax
+    int32_t fp_prune;           // 1: the move draw and the row of a full ply are made from the pruned counts
+    unsigned long long *fp_ctr;       // [G][FP_COUNT] per game (no atomics), azx_forced_playouts_stats' array; the host sums
 };
+// full plies chosen under the option, selects whose forced set was non-empty, recorded rows with a reduced child,
+// visits removed from recorded rows
+enum { FP_PLIES = 0, FP_FORCED, FP_ROWS_PRUNED, FP_REMOVED, FP_COUNT = 4 };
 // rows recorded while the option is on; of those, rows of greedy plies; of those, rows with more than one visited child
 enum { TT_ROWS = 0, TT_GREEDY, TT_GREEDY_WIDE, TT_COUNT = 4 };
 // T = 0 plies searched under the option, plies stopped before their last batch, batches skipped (batches_left at the stops)

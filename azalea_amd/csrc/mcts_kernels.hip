@@ -488,6 +488,12 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     // are used up selects nothing and queues no rows in the move's remaining launches.
     bool cap_full = true;
     if (E.cap_fast_batches != 0) cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
+    // Forced playouts (azx_set_forced_playouts; NOT the reference's behaviour, 0 unless the host hands a play-mode
+    // launch the option): the root level of a FULL search's select descends into the lowest-index child with n > 0 and
+    // n * n < (k * P) * S, if there is one (include/azx.h states the rule).  Wave-uniform; c_forced counts such selects.
+    // (k travels as its bit pattern in one scalar register, tested as an integer: the host hands +0.0f for "off")
+    const int fp_kbits = __builtin_amdgcn_readfirstlane(cap_full ? __float_as_int(E.fp_k) : 0);
+    uint32_t c_forced = 0;
 
     if (mode & MODE_BEGIN) {
         batches_left = cap_full ? num_batches : E.cap_fast_batches;
@@ -1055,7 +1061,22 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                 }
             }
             const float sq = sqrt_of(sq_tab, sumn);
-            const int best_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq);
+            // the forced set, over the priors this select scores with and the counts it sees (virtual losses of the
+            // batch in flight included): its lowest-index member is taken in place of the argmax.  Found BEFORE the
+            // scores, into one scalar, so that its two temporaries are dead where the scoring's registers peak.
+            int forced_idx = -1;
+            if (fp_kbits != 0) {
+                const float S = (float)sumn, fp_k = __int_as_float(fp_kbits);
+#pragma unroll
+                for (int s = RS - 1; s >= 0; --s) {
+                    const float n = rst[s].x;
+                    const uint64_t fm = __ballot(n > 0.0f && n * n < (fp_k * Pn[s]) * S) & rootrm[s];
+                    if (fm) forced_idx = s * 64 + (int)__ffsll((long long)fm) - 1;
+                }
+                if (forced_idx >= 0) c_forced += 1;
+            }
+            const int argmax_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq);
+            const int best_idx = forced_idx >= 0 ? forced_idx : argmax_idx;
             const int bl = best_idx & 63, bsl = best_idx >> 6;
 #pragma unroll
             for (int s = 0; s < RS; ++s) {
@@ -1449,6 +1470,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             es[ES_STOPPED] += 1ull;
             es[ES_SKIPPED] += (unsigned long long)(-1 - es_r1);
         }
+        if (c_forced) E.fp_ctr[(size_t)g * FP_COUNT + FP_FORCED] += c_forced;
     }
     // the six per-game tallies, one lane each (as six scalar read-modify-writes the compiler waited
     // for each load in turn: six memory round trips at the end of every launch)
@@ -1905,6 +1927,62 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) nv_sum += nv[s];
     nv_sum = wave_sum(nv_sum);
+    // Forced playouts (azx_set_forced_playouts; NOT the reference's behaviour): a fast ply of a playout cap neither
+    // forces nor prunes.  Policy target pruning (include/azx.h states the rule): on a full ply whose draw or row is made
+    // from the counts, every child below the maximum gives back the visits that PUCT, measured against the most-visited
+    // child b, would not have spent on it -- at most its forced quota sqrtf((k * P) * S) -- and a child left with one
+    // visit loses that too.  The pruned counts replace nv[] for the draw and the row; width, the mean child visits and
+    // the resign value stay on the raw counts (fp_removed, fp_zeroed carry the difference).  float32, unfused, IEEE.
+    float fp_removed = 0.0f;
+    int fp_zeroed = 0;
+    const bool fp_full = E.fp_k > 0.0f && (E.cap_fast_batches == 0 || azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1));
+    if (fp_full && E.fp_prune != 0 && mx > 0.0f && (!draw_is_greedy(E, ply) || E.tt_rows == AZX_ROWS_VISITS)) {
+        float cw[SLOTS], cp[SLOTS];
+        float n_b = 0.0f, w_b = 0.0f, P_b = 0.0f;
+        bool have_b = false;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            cw[s] = 0.0f;
+            cp[s] = 0.0f;
+            if (lane_bit(mk.m[s])) {
+                const Node c = arena[rootn.link + rk[s]];
+                cw[s] = c.tv;
+                cp[s] = c.pp;
+            }
+            const uint64_t eq = __ballot(lane_bit(mk.m[s]) && nv[s] == mx);
+            if (eq && !have_b) {
+                const int l = (int)__ffsll((long long)eq) - 1;
+                n_b = readlane_f(nv[s], l);
+                w_b = readlane_f(cw[s], l);
+                P_b = readlane_f(cp[s], l);
+                have_b = true;
+            }
+        }
+        const float kf = E.fp_k, c32 = E.c_puct;
+        const float sq = sqrtf(nv_sum);
+        const float puct_b = (-w_b) / n_b + (c32 * P_b) * (sq / (1.0f + n_b));
+        float rem = 0.0f;
+        int zeroed = 0;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const float n = nv[s];
+            if (lane_bit(mk.m[s]) && n > 0.0f && n < mx) {
+                const float gap = puct_b - (-cw[s]) / n;
+                if (gap > 0.0f) {
+                    const float f = sqrtf((kf * cp[s]) * nv_sum);
+                    const float need = ((c32 * cp[s]) * sq) / gap - 1.0f;
+                    float r = ceilf(fmaxf(n - f, need));
+                    r = fminf(fmaxf(r, 0.0f), n);
+                    if (r < n && r <= 1.0f) r = 0.0f;
+                    rem += n - r;
+                    zeroed += r == 0.0f;
+                    nv[s] = r;
+                }
+            }
+        }
+        fp_removed = wave_sum(rem);                      // integers: exact in any order
+        fp_zeroed = wave_sum_i(zeroed);
+    }
     float tot = 0.0f;
     int width = 0;
 #pragma unroll
@@ -1920,7 +1998,7 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         tot += x;
     }
     tot = wave_sum(tot);
-    width = wave_sum_i(width);
+    width = wave_sum_i(width) + fp_zeroed;               // (the root's width is of the raw counts)
     // inclusive prefix sums in child order (slot-major, lane-minor)
     uint32_t r[4];
     game_rng(E, gh->uid).gen(0xC0FFEEu, (uint32_t)ply, 0u, 0x4D4F5645u, r);
@@ -1959,6 +2037,8 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
     }
     // early stop (azx_set_early_stop): the T = 0 plies searched under the option, fast plies included
     if (E.early_stop != 0 && lane == 0 && draw_is_greedy(E, ply)) E.estop_ctr[(size_t)g * ES_COUNT + ES_T0_PLIES] += 1ull;
+    // forced playouts (azx_set_forced_playouts): the full plies chosen under the option
+    if (fp_full && lane == 0) E.fp_ctr[(size_t)g * FP_COUNT + FP_PLIES] += 1ull;
     // playout cap (azx_set_playout_cap): a fast ply moves the game on and records nothing
     if (E.cap_fast_batches != 0) {
         const bool cap_full = azx_cap_is_full(E.seed, gh->uid, ply, E.cap_thr_m1);
@@ -1977,7 +2057,7 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
     const int row = gh->n_rows;
     const size_t rb = ((size_t)g * E.ncells + row) * AZX_CELL_STRIDE;
     const bool tt_vis = E.tt_rows == AZX_ROWS_VISITS && nv_sum > 0.0f;
-    const float row_den = tt_vis ? nv_sum : tot;
+    const float row_den = tt_vis ? nv_sum - fp_removed : tot;   // (nv[] holds the pruned counts: their sum, exact)
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
         const int cell = s * 64 + lane;
@@ -2011,6 +2091,12 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
                 tc[TT_GREEDY] += 1ull;
                 if (width > 1) tc[TT_GREEDY_WIDE] += 1ull;
             }
+        }
+        // azx_forced_playouts_stats: recorded rows with at least one reduced child, visits removed from them
+        if (fp_removed > 0.0f) {
+            unsigned long long *fc = E.fp_ctr + (size_t)g * FP_COUNT;
+            fc[FP_ROWS_PRUNED] += 1ull;
+            fc[FP_REMOVED] += (unsigned long long)fp_removed;
         }
     }
 }

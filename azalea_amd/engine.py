@@ -658,6 +658,50 @@ class Engine:
         check(self.L.azx_train_targets_stats(self.h, _p(out, C.c_int64)))
         return {k: int(out[i]) for i, k in enumerate(self.TRAIN_TARGETS_STATS)}
 
+    # ---- forced playouts and policy target pruning (azx_set_forced_playouts; NOT the reference's behaviour) ----
+    def set_forced_playouts(self, k=2.0, prune=True):
+        """azx_set_forced_playouts: in the following play / play_device / replay_fill / play_steps calls the root level
+        of every select of a full search descends into the lowest-index root child with n > 0 and n * n < (k * P) * S,
+        if there is one, instead of the PUCT argmax (n its visits as the select sees them, P the prior the select
+        scores with, S the children's visit sum); with prune=True the move draw and the recorded row of a full ply
+        that is not drawn greedily (and every full ply's row under set_train_targets("visits")) are made from the pruned
+        counts: each child below the maximum gives back the visits PUCT would not have spent on it (include/azx.h
+        states both rules).  A playout cap's fast plies neither force nor prune.  NOT the reference's behaviour; off by
+        default.  search(), the phase API and matches are untouched; Match / Tournament refuse an engine with the
+        option set.  set_forced_playouts(0, False) clears it: the same kernels, the same bytes as before.  Zeroes
+        forced_playouts_stats().  DESIGN 7.13 has what was measured; its effect on playing strength and training
+        efficiency is not measured."""
+        k = float(k)
+        if not 0.0 <= k <= 64.0:                    # NaN fails both comparisons
+            raise ValueError("forced playouts: k must be in [0, 64], got %r" % (k,))
+        if prune not in (True, False, 0, 1):
+            raise ValueError("forced playouts: prune must be True or False, got %r" % (prune,))
+        if k == 0.0 and prune:
+            raise ValueError("forced playouts: pruning needs forcing (k > 0)")
+        check(self.L.azx_set_forced_playouts(self.h, k, 1 if prune else 0))
+
+    def clear_forced_playouts(self):
+        """set_forced_playouts(0, False): PUCT selects and raw counts again."""
+        check(self.L.azx_set_forced_playouts(self.h, 0.0, 0))
+
+    def forced_playouts(self):
+        """azx_get_forced_playouts: the pair (k, prune) in force, (0.0, False) when off."""
+        k, prune = C.c_float(0.0), C.c_int(0)
+        if getattr(self.L, "azx_get_forced_playouts", None) is None:   # an older build (tools/lib_bench.py): never set
+            return 0.0, False
+        check(self.L.azx_get_forced_playouts(self.h, C.byref(k), C.byref(prune)))
+        return float(k.value), bool(prune.value)
+
+    FORCED_PLAYOUTS_STATS = ("full_plies", "forced_selects", "rows_pruned", "visits_removed")
+
+    def forced_playouts_stats(self):
+        """azx_forced_playouts_stats since the last set_forced_playouts: dict(full_plies, forced_selects, rows_pruned,
+        visits_removed) -- the full plies chosen under the option, the selects whose forced set was non-empty, the
+        recorded rows with at least one reduced child and the visits removed from recorded rows."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_forced_playouts_stats(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(self.FORCED_PLAYOUTS_STATS)}
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""

@@ -76,7 +76,8 @@ class Player:
 
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
-                 openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None):
+                 openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None,
+                 forced_playouts=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -133,7 +134,16 @@ class Player:
         ply, and / or the reward is (1 - value_mix) * z + value_mix * v.  The games themselves are untouched.  It is
         applied again whenever the engine is made again.  A ValueError -- here, before any engine is made -- with
         device_match=True (a match's harvest records the reference's rows and the outcome), when the games would run
-        through the host loop, or for anything normalize_train_targets refuses.  DESIGN 7.12 has what is measured."""
+        through the host loop, or for anything normalize_train_targets refuses.  DESIGN 7.12 has what is measured.
+        `forced_playouts` (NOT the reference's behaviour, which selects by PUCT alone and records every visit; off by
+        default): True (= (2.0, True)), a (k, prune) pair or a {"k": ..., "prune": ...} dict sets
+        Engine.set_forced_playouts (include/azx.h states the rules) on the self-play engine this Player builds, device
+        self-play or external_batch: a full search's root selects force sqrt(k * P * S) visits on every visited child,
+        and with prune the move draw and the recorded row are made from the pruned counts.  It is applied again
+        whenever the engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True
+        (a match searches and draws as the reference does), when the games would run through the host loop, or for
+        anything normalize_forced_playouts refuses.  Its effect on playing strength and training efficiency is not
+        measured."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -162,6 +172,7 @@ class Player:
         self.resign = self._check_resign(resign)
         self.early_stop = self._check_early_stop(early_stop)
         self.train_targets = self._check_train_targets(train_targets)
+        self.forced_playouts = self._check_forced_playouts(forced_playouts)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -358,6 +369,28 @@ class Player:
                              "which records the reference's rows and the outcome")
         return train_targets
 
+    def _check_forced_playouts(self, forced_playouts):
+        """`forced_playouts` as a (k, prune) pair, or None for off; a ValueError naming what does not hold."""
+        forced_playouts = normalize_forced_playouts(forced_playouts)
+        if forced_playouts is None:
+            return None
+        if self.device_match:
+            raise ValueError("forced_playouts is a self-play option: a device match searches and draws every ply as "
+                             "the reference does (engine.Match refuses an engine with forced playouts set)")
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("forced_playouts needs the games to run in a device engine (a single agent whose Policy "
+                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
+                             "which selects by PUCT alone and records every visit")
+        return forced_playouts
+
+    def forced_playouts_stats(self):
+        """Engine.forced_playouts_stats() of the self-play engine, or None while there is none or forced_playouts is
+        not set."""
+        if self.forced_playouts is None or self._engine is None:
+            return None
+        return self._engine.forced_playouts_stats()
+
     def train_targets_stats(self):
         """Engine.train_targets_stats() of the self-play engine, or None while there is none or train_targets is not set."""
         if self.train_targets is None or self._engine is None:
@@ -514,6 +547,8 @@ class Player:
                 self._engine.set_early_stop(True)
             if self.train_targets is not None:
                 self._engine.set_train_targets(*self.train_targets)
+            if self.forced_playouts is not None:
+                self._engine.set_forced_playouts(*self.forced_playouts)
             self._engine_key = key
         return self._engine
 
@@ -693,6 +728,37 @@ def normalize_train_targets(train_targets):
     if rows == "reference" and mix == 0.0:
         return None
     return rows, mix
+
+
+def normalize_forced_playouts(forced_playouts):
+    """(k, prune) of True (= (2.0, True)), a pair or a {"k": ..., "prune": ...} mapping, or None for off (None, False,
+    (0, False)); a ValueError unless k is a number in [0, 64], prune a bool, and k > 0 where prune is set."""
+    if forced_playouts is None or forced_playouts is False:
+        return None
+    if forced_playouts is True:
+        return 2.0, True
+    if isinstance(forced_playouts, dict):
+        if set(forced_playouts) != {"k", "prune"}:
+            raise ValueError("forced_playouts as a dict needs exactly the keys 'k' and 'prune', got %r"
+                             % (sorted(map(str, forced_playouts)),))
+        k, prune = forced_playouts["k"], forced_playouts["prune"]
+    elif isinstance(forced_playouts, (tuple, list)) and len(forced_playouts) == 2:
+        k, prune = forced_playouts
+    else:
+        raise ValueError("forced_playouts must be True, a (k, prune) pair or a dict with those keys, got %r"
+                         % (forced_playouts,))
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
+        raise ValueError("forced_playouts: k must be a number in [0, 64], got %r" % (k,))
+    k = float(k)
+    if not 0.0 <= k <= 64.0:                        # NaN fails both comparisons
+        raise ValueError("forced_playouts: k must be in [0, 64], got %r" % (k,))
+    if not isinstance(prune, (bool, np.bool_)):
+        raise ValueError("forced_playouts: prune must be True or False, got %r" % (prune,))
+    if k == 0.0:
+        if prune:
+            raise ValueError("forced_playouts: pruning needs forcing (k > 0), got k = 0 with prune = True")
+        return None
+    return k, bool(prune)
 
 
 def normalize_early_stop(early_stop):

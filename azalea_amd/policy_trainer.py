@@ -367,8 +367,21 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     (Player(train_targets=...)), so the lock-step ranks and the actors play under it too; the random-mover player
     that fills the first buffer does NOT get it.  One log line says whether it is on.  A ValueError, before anything
     is built, for anything normalize_train_targets refuses; Player refuses it where the games would run through the
-    host loop.  DESIGN 7.12 has what is measured of its effect."""
-    from .parallel_player import normalize_early_stop, normalize_train_targets
+    host loop.  DESIGN 7.12 has what is measured of its effect.
+
+    config["forced_playouts"] = true, (k, prune) or {"k": 2.0, "prune": true} (default absent; NOT the reference's
+    behaviour, and outside every parity claim): forced playouts at the root of every full self-play search and, with
+    prune, policy target pruning of the move draw and the recorded rows (Engine.set_forced_playouts, include/azx.h
+    states both rules).  It goes to the one self-play Player built here (Player(forced_playouts=...)), so the lock-step
+    ranks and the actors play under it too; the random-mover player that fills the first buffer does NOT get it.  One
+    log line says whether it is on.  A ValueError, before anything is built, for anything normalize_forced_playouts
+    refuses; Player refuses it where the games would run through the host loop.  Its effect on playing strength and
+    on training efficiency is not measured."""
+    from .parallel_player import normalize_early_stop, normalize_train_targets, normalize_forced_playouts
+    try:
+        forced_playouts = normalize_forced_playouts(config.get("forced_playouts"))
+    except ValueError as exc:
+        raise ValueError("config['forced_playouts']: %s" % exc) from None
     try:
         train_targets = normalize_train_targets(config.get("train_targets"))
     except ValueError as exc:
@@ -425,7 +438,13 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
                     random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
-                    resign=resign, early_stop=early_stop, train_targets=train_targets)
+                    resign=resign, early_stop=early_stop, train_targets=train_targets,
+                    forced_playouts=forced_playouts)
+    if leader:
+        logging.info("forced playouts (config['forced_playouts']): %s",
+                     "off" if forced_playouts is None else
+                     "on -- NOT the reference's behaviour: k = %g, policy target pruning %s"
+                     % (forced_playouts[0], "on" if forced_playouts[1] else "off"))
     if leader:
         logging.info("training targets (config['train_targets']): %s",
                      "off" if train_targets is None else

@@ -604,6 +604,57 @@ int azx_get_train_targets(azx_engine *e, int *policy_rows, float *value_mix);
  * lane that writes the row's metrics.  They live in an array of their own: azx_debug_counters keeps its 16 words. */
 int azx_train_targets_stats(azx_engine *e, int64_t out4[4]);
 
+/* Forced playouts at the root and policy target pruning, for throughput self-play (Wu 2019, "Accelerating Self-Play
+ * Learning in Go", section 3.2).  NOT the reference's behaviour (off by default, outside every parity claim): the
+ * reference selects by PUCT alone and records every visit.
+ *   Every root select draws fresh Dirichlet noise, so a child the noise lifts once gets one visit and is then usually
+ * dropped: the search never learns whether the move was good.  Forcing gives such a child about sqrt(k * P * S)
+ * visits; pruning then takes out of the move draw and of the recorded row the visits PUCT would not have spent.
+ *   All arithmetic is float32 and unfused, divide and sqrt IEEE; counts are integers held in float32.
+ *   Forcing, in the root level of every select of a FULL search (a playout cap's fast plies never force; with the cap
+ * off every search is full).  n_j = the root children's num_visits as that select sees them, virtual losses of the
+ * batch in flight included; S = their sum (the integer under the square root of mcts.py:132); P_j = the prior that
+ * select scores with (noised if noise is on, the stored prior otherwise).  The forced set is
+ *       { j : n_j > 0 and n_j * n_j < (k * P_j) * S }.
+ * If it is non-empty the select descends into its lowest-index member instead of the PUCT argmax.  Below the root
+ * nothing changes; virtual loss, dedup, expand and backup are as always.
+ *   Pruning (prune = 1), where the move is drawn, on full plies that are not drawn at temperature 0 and on every full
+ * ply under AZX_ROWS_VISITS.  n_i, w_i (total_value), P_i (the stored, un-noised prior) are the root's children at
+ * that time; S = sum n_i, sq = sqrtf(S), c = c_puct, n_max = max n_i, b = the first index with n_b == n_max,
+ *       puct_b = (-w_b) / n_b + (c * P_b) * (sq / (1 + n_b)).
+ * For each i with 0 < n_i < n_max:
+ *       Q_i  = (-w_i) / n_i
+ *       gap  = puct_b - Q_i                      ; if !(gap > 0): r_i = n_i
+ *       f_i  = sqrtf((k * P_i) * S)
+ *       need = ((c * P_i) * sq) / gap - 1        ; the smallest real n' whose PUCT does not exceed puct_b
+ *       r_i  = ceilf(max(n_i - f_i, need)), clamped to [0, n_i]
+ *       if r_i < n_i and r_i <= 1: r_i = 0       ; a child reduced to a single playout is pruned outright
+ * Children with n_i == n_max or n_i == 0 keep their count.  The pruned counts r replace n in the weights that BOTH the
+ * move draw and the row are made from (a junk forced visit is not played at T = 1 either); under AZX_ROWS_VISITS the
+ * row is r_i / sum r.  At a ply drawn at temperature 0 the draw and the one-hot row cannot change (the maxima are
+ * untouched); only a visit-share row differs there.  Row metrics stay on the raw counts (width, mean child visits, the
+ * resign value); metric 2 is the log-probability under the distribution the move was drawn from, the pruned one.
+ *   Beside the other options: early stop stays sound (a forced select still adds at most one visit to one root child);
+ * resignation judges the raw root; a playout cap's fast plies neither force nor prune.
+ *   It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move launches,
+ * the pipelined half-pools, a registered external evaluator) and to nothing else: azx_search and the phase API select
+ * by PUCT whatever the option is, and azx_match_play / azx_tournament_play refuse an engine with the option set with
+ * AZX_EINVAL before touching any engine.
+ *   k must be finite and in [0, 64], prune 0 or 1; (0, 0) is off; k == 0 with prune == 1 is AZX_EINVAL (the prune
+ * gives back at most the forced quota).  A bad call is AZX_EINVAL and leaves the setting in place.  May be called
+ * between calls, for any evaluator.  The call zeroes the statistics of azx_forced_playouts_stats.  With the option
+ * never set, or cleared, every call launches the same kernels and returns the same bytes as without these entry
+ * points.  azx_kernel_info reports forced=off or forced=<k>/<prune|noprune>.  What was measured is given in DESIGN
+ * 7.13; the option's effect on playing strength and training efficiency is not measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_forced_playouts). */
+int azx_set_forced_playouts(azx_engine *e, float k, int prune);
+int azx_get_forced_playouts(azx_engine *e, float *k, int *prune);
+/* out4 = {full plies chosen under the option, selects whose forced set was non-empty, recorded rows with at least one
+ * reduced child, visits removed from recorded rows}, counted since the last azx_set_forced_playouts.  They live in an
+ * array of their own: azx_debug_counters keeps its 16 words. */
+int azx_forced_playouts_stats(azx_engine *e, int64_t out4[4]);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,

@@ -14,5 +14,6 @@ _lib.OPTIONAL.update(["azx_set_resign", "azx_clear_resign", "azx_resign_is_exemp
 _lib.OPTIONAL.update(["azx_set_early_stop", "azx_early_stop_stats"])
 _lib.OPTIONAL.update(["azx_set_train_targets", "azx_get_train_targets", "azx_train_targets_stats"])
 _lib.OPTIONAL.update(["azx_debug_tower_tiles"])
+_lib.OPTIONAL.update(["azx_set_forced_playouts", "azx_get_forced_playouts", "azx_forced_playouts_stats"])
 sys.argv = ["bench.py"] + sys.argv[2:]
 runpy.run_path(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), run_name="__main__")
