@@ -6,9 +6,11 @@ from the float32 1/k table, value 0 ("uniform") or the oracle's fnv1a hash of th
 rule off the restatement equals the unmodified oracle bit for bit on every position (tests/test_forced_playouts_api.py
 pins that).
 
-Setup: 5x5, 200 simulations, batch 10, c_puct 0.5, no noise.  Positions: the prefixes of 6 games from
-RandomState(20261020), each opening with two random plies and then following the UNFORCED search's first most-visited
-child, to at most 14 plies.
+Setup: a frozen Settings (tests/early_stop_reference.py: board, simulations, batch, c_puct, the oracle tree's capacity;
+the float32 1/k table follows from the board), by default 5x5, 200 simulations, batch 10, c_puct 0.5; no noise.
+Positions of the default setup: the prefixes of 6 games from RandomState(20261020), each opening with two random plies
+and then following the UNFORCED search's first most-visited child, to at most 14 plies.  Other boards' positions are
+tests/option_positions.py's, through position().
 
 Shared by tests/test_forced_playouts_api.py (CPU) and tests/test_gpu_forced_playouts.py; the references are computed once
 per process and never changed."""
@@ -22,30 +24,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from early_stop_reference import DEFAULT, Settings, game_at  # noqa: E402,F401
+from early_stop_reference import evaluator as oracle_evaluator  # noqa: E402,F401
+
 f32 = np.float32
-N, CELLS = 5, 25
-SIMS, BS, C_PUCT = 200, 10, 0.5
-NB = SIMS // BS + 1                     # select batches of a full search (mcts.py:268)
+N, CELLS = DEFAULT.n, DEFAULT.cells
+SIMS, BS, C_PUCT = DEFAULT.sims, DEFAULT.bs, DEFAULT.c_puct
+NB = DEFAULT.nb                         # select batches of a full search (mcts.py:268)
 K_FORCED = 2.0
 SEED, N_GAMES, MAX_PLIES = 20261020, 6, 14
-TABLE = (f32(1.0) / np.arange(0, CELLS + 1).clip(1).astype(f32)).astype(f32)   # float32 1/k
+TABLE = DEFAULT.table                   # float32 1/k
 KINDS = ("hash", "uniform")
-
-
-def oracle_evaluator(kind):
-    from oracle import oracle as orc
-    if kind == "hash":
-        return orc.UniformEval(hash_value=True, prior_by_k=TABLE)
-    assert kind == "uniform"
-    return orc.UniformEval()
-
-
-def game_at(prefix):
-    from oracle import oracle as orc
-    h = orc.Hex(N)
-    for m in prefix:
-        h.step(m)
-    return h
 
 
 def evaluate(h, kind):
@@ -65,8 +55,12 @@ class Search:
     level of every select.  Afterwards: n, w, p (the root children's visits, values and priors), forced (selects
     whose forced set was non-empty) and overrode (of those, the selects whose forced child was not the argmax)."""
 
-    def __init__(self, prefix, kind, k=0.0, sims=SIMS, bs=BS, c_puct=C_PUCT):
-        cap = 1 + CELLS + (sims // bs + 1) * bs * CELLS
+    def __init__(self, prefix, kind, k=0.0, sims=None, bs=None, c_puct=None, cfg=DEFAULT):
+        sims = cfg.sims if sims is None else sims
+        bs = cfg.bs if bs is None else bs
+        c_puct = cfg.c_puct if c_puct is None else c_puct
+        self.table = cfg.table
+        cap = 1 + cfg.cells + (sims // bs + 1) * bs * cfg.cells
         self.parent = np.full(cap, -1, np.int64)
         self.first = np.full(cap, -1, np.int64)
         self.nch = np.full(cap, -1, np.int64)
@@ -75,7 +69,8 @@ class Search:
         self.num_nodes = 1
         self.kind, self.k, self.c32 = kind, f32(k), f32(c_puct)
         self.forced = self.overrode = 0
-        self.games = {0: game_at(prefix)}                       # node -> position
+        self.forced_at = []                                     # the forced child's index, one per forced select
+        self.games = {0: game_at(prefix, cfg)}                  # node -> position
         self.moves = {}                                         # expanded node -> its legal moves
         root = self.games[0]
         assert root.result == 0
@@ -91,7 +86,7 @@ class Search:
         self.num_nodes += k
         self.first[node], self.nch[node] = first, k
         self.parent[first:first + k] = node
-        self.pp[first:first + k] = TABLE[k]
+        self.pp[first:first + k] = self.table[k]
         self.moves[node] = self.games[node].legal_moves()
 
     def pick(self, node):
@@ -107,6 +102,7 @@ class Search:
             forced = np.flatnonzero((nv > 0) & (nv * nv < (self.k * P) * S))
             if len(forced):
                 self.forced += 1
+                self.forced_at.append(int(forced[0]))
                 self.overrode += int(forced[0]) != best
                 best = int(forced[0])
         return best
@@ -155,10 +151,11 @@ class Search:
             node = int(self.parent[node])
 
 
-def prune(n, w, P, k=K_FORCED, c=C_PUCT):
+def prune(n, w, P, k=K_FORCED, c=C_PUCT, b=None):
     """The pruned counts r of include/azx.h, float32 op by op: children below the maximum give back the visits PUCT,
     measured against the first most-visited child, would not have spent on them; a child reduced to one visit loses
-    that too.  Maxima and unvisited children keep their count."""
+    that too.  Maxima and unvisited children keep their count.  (`b`: measure against this most-visited child instead
+    of the first -- NOT the rule; for the conditions on test inputs that must tell the two apart.)"""
     n, w, P = (np.asarray(a, f32) for a in (n, w, P))
     k, c = f32(k), f32(c)
     r = n.copy()
@@ -167,7 +164,9 @@ def prune(n, w, P, k=K_FORCED, c=C_PUCT):
     S = f32(n.sum(dtype=np.float64))
     sq = np.sqrt(S)
     n_max = n.max()
-    b = int(np.argmax(n))                                       # the first index with n_b == n_max
+    if b is None:
+        b = int(np.argmax(n))                                   # the first index with n_b == n_max
+    assert n[b] == n_max
     puct_b = (-w[b]) / n[b] + (c * P[b]) * (sq / (f32(1.0) + n[b]))
     sel = (n > 0) & (n < n_max)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -183,11 +182,11 @@ def prune(n, w, P, k=K_FORCED, c=C_PUCT):
     return r.astype(f32)
 
 
-def oracle_root(prefix, kind):
+def oracle_root(prefix, kind, cfg=DEFAULT):
     """(visits, values, priors) of the root's children after the UNMODIFIED oracle's search of `prefix`."""
     from oracle import oracle as orc
-    t = orc.Tree(1 << 16)
-    st = orc.search(t, game_at(prefix), oracle_evaluator(kind), SIMS, BS, C_PUCT)
+    t = orc.Tree(cfg.tree_cap)
+    st = orc.search(t, game_at(prefix, cfg), oracle_evaluator(kind, cfg), cfg.sims, cfg.bs, cfg.c_puct)
     assert st.status == 0
     nv, tv, pp, _, _ = t.root_stats()
     return np.asarray(nv, f32), np.asarray(tv, f32), np.asarray(pp, f32)
@@ -207,17 +206,21 @@ def prefixes(kind):
     return tuple(out)
 
 
+def position(prefix, kind, k=K_FORCED, cfg=DEFAULT):
+    """One position's dict: prefix; off_* = the restatement's root with the rule off; n, w, p = its root under
+    forcing with `k`; forced / overrode = its forced selects (forced_at: the forced child's index, select by select);
+    r = prune(n, w, p); removed = visits the prune takes."""
+    off, on = Search(prefix, kind, 0.0, cfg=cfg), Search(prefix, kind, k, cfg=cfg)
+    r = prune(on.n, on.w, on.p, k, cfg.c_puct)
+    return dict(prefix=list(prefix), off_n=off.n, off_w=off.w, off_p=off.p, n=on.n, w=on.w, p=on.p,
+                forced=on.forced, overrode=on.overrode, forced_at=tuple(on.forced_at), r=r,
+                removed=int((on.n - r).sum()))
+
+
 @functools.lru_cache(maxsize=None)
 def positions(kind, k=K_FORCED):
-    """One dict per position: prefix; off_* = the restatement's root with the rule off; n, w, p = its root under
-    forcing with `k`; forced / overrode = its forced selects; r = prune(n, w, p); removed = visits the prune takes."""
-    refs = []
-    for prefix in prefixes(kind):
-        off, on = Search(prefix, kind, 0.0), Search(prefix, kind, k)
-        r = prune(on.n, on.w, on.p, k)
-        refs.append(dict(prefix=list(prefix), off_n=off.n, off_w=off.w, off_p=off.p, n=on.n, w=on.w, p=on.p,
-                         forced=on.forced, overrode=on.overrode, r=r, removed=int((on.n - r).sum())))
-    return tuple(refs)
+    """position() of every prefix of prefixes(kind), on the default 5x5 setup."""
+    return tuple(position(prefix, kind, k) for prefix in prefixes(kind))
 
 
 def shares(counts):

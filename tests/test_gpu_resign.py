@@ -570,16 +570,26 @@ def test_player_resigns_and_counts():
     from azalea_amd import parallel_player
     from azalea_amd.azalea_agent import AzaleaAgent
     from azalea_amd.game.hex import HexGame
+    from azalea_amd import engine as eng
     agent = AzaleaAgent(partial(HexGame, board_size=N), policy=cuda_policy(), device="cuda:0")
-    player = parallel_player.Player(None, [agent], n_games=64, resign=RESIGN)
+    # AzaleaAgent() seeds its policy from the operating system (azalea_agent.py:41-44), and the Player draws the
+    # engine's seed from the policy: without this line every run plays other games with other exempt ones
+    agent.seed(1)
+    player = parallel_player.Player(None, [agent], n_games=G, resign=RESIGN)
     assert player.resign_stats() is None
-    frame, metrics = player.read(200)
-    assert len(frame) >= 200
+    # An exempt game plays to the end while its neighbours resign: a read of 200 rows returns after some twelve engine
+    # steps, most often before any exempt game is over.  A step hands over at most G rows and a 5x5 game is over after
+    # CELLS plies, so G * CELLS rows take at least CELLS steps: every slot's first game, the exempt ones included, is
+    # finished and counted by then.
+    frame, metrics = player.read(G * CELLS)
+    assert len(frame) >= G * CELLS
     assert "resign=0/2/0.25" in player._engine.kernel_info()
     rs = player.resign_stats()
+    exempt_first = sum(eng.resign_is_exempt(player._engine.cfg.seed, uid, RESIGN[2]) for uid in range(G))
+    assert exempt_first > 0                                     # a condition on the input: the seed above meets it
     # (the engine may have finished more games than this read handed out)
     assert rs["resigned"] + rs["played_out"] + rs["exempt"] >= metrics["games"] > 0
-    assert rs["resigned"] > 0 and rs["exempt"] > 0 and rs["sum_resign_ply"] >= 2 * rs["resigned"]
+    assert rs["resigned"] > 0 and rs["exempt"] >= exempt_first and rs["sum_resign_ply"] >= 2 * rs["resigned"]
     player.stop()
 
 
