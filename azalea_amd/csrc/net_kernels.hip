@@ -298,7 +298,9 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
     const int N = P.N, ncells = P.ncells;
     const int e = e0 + wb;
     const bool live = e < n_eval;
-    const int board_b = 128 * ROWB;
+    // board 1's image starts AZX_TOWER_BOARD_GAP rows behind board 0's 128, so that a cell's row has another residue
+    // mod 16 on either board (tower_tiles.h); the rows between are never read: a tap that would reach them is padding
+    const int board_b = (128 + AZX_TOWER_BOARD_GAP) * ROWB;
     // the shared zeros come first, two rows of them: a padding tap reads at (its own address mod 256), i.e. on the
     // bank slot it would have used, so the padded lanes of a read do not collide with the others' slots
     const int zero_off = 0;
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
         const int ry = r / N, rx = r - ry * N;
         // the stem's first neighbour of this cell in its board's staged (N + 2)^2 cells, -1 for a dead row
         cell0_[m] = r < ncells ? 2 * ROWB + (L >> 7) * board_b + 121 * ROWB + ry * (N + 2) + rx : -1;
-        rbase[m] = 2 * ROWB + L * ROWB + lchunk;         // 8 channels (16 B) per k-group
+        rbase[m] = 2 * ROWB + (L + AZX_TOWER_BOARD_GAP * (L >> 7)) * ROWB + lchunk;     // 8 channels (16 B) per k-group
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int yy = ry + tap / 3 - 1, xx = rx + tap % 3 - 1;
@@ -473,8 +475,9 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
     };
 #pragma unroll
     for (int i = 0; i < 4; ++i) load_w(0, i >> 1, i & 1);
-    auto conv_layer = [&](int layer, auto residual_tag) {
-        constexpr bool residual = decltype(residual_tag)::value;
+    // One k-loop for both kinds of layer (conv1, conv2 + residual): only the epilogue differs, a uniform choice by the
+    // layer's parity, so the loop's code exists once (32 KB of code instead of 46 KB).
+    for (int layer = 0; layer < 2 * P.blocks; ++layer) {
         asm volatile("" : "+v"(tapok_lo), "+v"(tapok_hi), "+v"(rbase[0]), "+v"(rbase[1]), "+v"(rbase[2]), "+v"(rbase[3]));
         f32x4 acc[MT][NT];
 #pragma unroll
@@ -521,7 +524,12 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
         // every row of the light tile LT (= MT - 1; `skip`, a scalar bit test) the wave branches over that tile's 6
         // MFMAs in both halves: each of those products would have added +-0 to an accumulator that started as +0,
         // which leaves every bit as it is (x + (-0) = x, +0 + (-0) = +0), and the order of the others is unchanged.
-        // The next step's fragments of tile MT - 2, which sit in the shadow of those MFMAs, are requested all the same.
+        // The next step's fragments of tile MT - 2, which sit in the shadow of those MFMAs, are requested all the same:
+        // under an `if` of their own on a second opaque read of the bit, not as the `else`.  The compiler turns a
+        // uniform if / else into a flag and two triangles anyway, and between the two it holds every value the first
+        // defines a second time; written out, the second triangle works on what the first left.  (Whole taps as two
+        // arms, each with its own loads, were built: every join then merges accumulators and all fragments, the
+        // allocator no longer finds 256 registers and keeps the residual in scratch -- DESIGN 3.2.)
         // The light tile's own two fragment loads stay where they are (for a skipped tap they read the zero rows): a
         // branch of their own around them cost more than they do (measured, as did issuing the light tile's twelve
         // MFMAs in one run under one branch: DESIGN 3.2).
@@ -549,9 +557,12 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
                 if (!tap_skipped(t >> 1)) {
 #pragma unroll
                     for (int q = 6 * LT; q < 24; ++q) step_q(q);
-                } else if (h == 1 && t + 1 < 18) {
-                    load_x(t + 1, MT - 2, 0);
-                    load_x(t + 1, MT - 2, 1);
+                }
+                if (h == 1 && t + 1 < 18) {
+                    if (tap_skipped(t >> 1)) {
+                        load_x(t + 1, MT - 2, 0);
+                        load_x(t + 1, MT - 2, 1);
+                    }
                 }
             }
         }
@@ -561,14 +572,18 @@ __global__ __launch_bounds__(F16X3_BPB * 128, 2) void k_tower_f16x3_s16(NetDev P
         NT_MARK(2)
         __syncthreads();   // both waves of the board finished reading it
         NT_MARK(3)
-        epilogue(acc, lb4, std::integral_constant<int, residual ? 1 : 0>{});
+        // two `if`s on opaque reads of the parity, for the reason given at the taps: as if / else the compiler
+        // hoisted the 64 sums acc + bias above the branch as the arms' common code and spilled them
+        auto second_conv = [&]() __attribute__((always_inline)) -> bool {
+            uint32_t s = (uint32_t)layer;
+            asm volatile("" : "+s"(s));
+            return s & 1u;
+        };
+        if (!second_conv()) epilogue(acc, lb4, std::integral_constant<int, 0>{});
+        if (second_conv()) epilogue(acc, lb4, std::integral_constant<int, 1>{});     // conv2 + residual
         NT_MARK(4)
         __syncthreads();   // the partner wave wrote the other rows of this board
         NT_MARK(5)
-    };
-    for (int blk = 0; blk < P.blocks; ++blk) {
-        conv_layer(2 * blk, std::false_type{});
-        conv_layer(2 * blk + 1, std::true_type{});
     }
 
     // heads' 1x1 convs + folded BN + ReLU (network.py:77, :83) as one more (tiny) MFMA layer: the last epilogue left
@@ -2195,6 +2210,7 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     const int bpb = net->tower_variant == 2 ? 1 : 2;
     net->lds_bytes = (size_t)bpb * 2 * (ncells + 1) * (chans + 4) * sizeof(float);
     if (net->tower_variant == 4) net->lds_bytes = (size_t)F16X3_BPB * 128 * 272 + 2 * 272;   // boards + the zero rows (two in k_tower_f16x3_s16)
+    if (x3) net->lds_bytes += (size_t)AZX_TOWER_BOARD_GAP * 272;     // ... and the rows between its two boards (tower_tiles.h)
     if (net->tower_variant == 5) net->lds_bytes = (size_t)(ncells + 2) * WIDE_ROWB;   // two zero rows + the chunk image
     net->d.sat_flag = nalloc<uint32_t>(net, 4);
     if (x3) {     // once per network: the kernel reads the table through NetDev
