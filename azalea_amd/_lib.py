@@ -174,6 +174,13 @@ SYMBOLS = {
     "azx_set_forced_playouts": (C.c_int, [_vp, C.c_float, C.c_int]),
     "azx_get_forced_playouts": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "azx_forced_playouts_stats": (C.c_int, [_vp, _i64p]),
+    # Gumbel root search with sequential halving (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_gumbel": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "azx_get_gumbel": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "azx_gumbel_stats": (C.c_int, [_vp, _i64p]),
+    "azx_gumbel_variate": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "azx_selftest_gumbel": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), _f32p]),
+    "azx_gumbel_state": (C.c_int, [_vp, _u64p, _u64p]),
 }
 
 class TrainConfig(C.Structure):

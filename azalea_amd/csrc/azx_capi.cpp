@@ -24,6 +24,7 @@
 #include "ext_kernels.h"
 #include "match_kernels.h"
 #include "playout_cap.h"
+#include "gumbel.h"
 #include "resign.h"
 #include "tower_tiles.h"
 
@@ -148,12 +149,15 @@ struct azx_engine {
     // forced playouts and policy target pruning (azx_set_forced_playouts): handed to the same launches, by the same scope
     float fp_k = 0.0f;
     int fp_prune = 0;
+    // Gumbel root search with sequential halving (azx_set_gumbel): handed to the same launches, by the same scope
+    int gm_m = 0, gm_rows = 0;
+    float gm_c_visit = 0.0f, gm_c_scale = 0.0f;
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
 // (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) and early stop
 // (azx_set_early_stop) travel the same way, and so do the training targets (azx_set_train_targets) and forced
-// playouts (azx_set_forced_playouts).
+// playouts (azx_set_forced_playouts) and the Gumbel root search (azx_set_gumbel).
 struct CapScope {
     DevEngine &d;
     explicit CapScope(azx_engine *e) : d(e->d) {
@@ -170,6 +174,7 @@ struct CapScope {
         if (e->estop_on) d.early_stop = 1;
         d.tt_rows = e->tt_rows; d.tt_mix = e->tt_mix;
         d.fp_k = e->fp_k; d.fp_prune = e->fp_prune;
+        d.gm_m = e->gm_m; d.gm_rows = e->gm_rows; d.gm_c_visit = e->gm_c_visit; d.gm_c_scale = e->gm_c_scale;
     }
     ~CapScope() {
         d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
@@ -177,6 +182,7 @@ struct CapScope {
         d.early_stop = 0;
         d.tt_rows = AZX_ROWS_REFERENCE; d.tt_mix = 0.0f;
         d.fp_k = 0.0f; d.fp_prune = 0;
+        d.gm_m = 0; d.gm_rows = 0; d.gm_c_visit = 0.0f; d.gm_c_scale = 0.0f;
     }
     CapScope(const CapScope &) = delete;
     CapScope &operator=(const CapScope &) = delete;
@@ -308,6 +314,9 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.estop_ctr, G * ES_COUNT);
     A(d.tt_ctr, G * TT_COUNT);
     A(d.fp_ctr, G * FP_COUNT);
+    A(d.gm_ctr, G * GM_COUNT);
+    A(d.gm_state, G * GM_STATE_WORDS);
+    A(d.gm_g, G * 2 * AZX_CELL_STRIDE);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
     A(e->g_cv, G * d.ncells); A(e->g_cw, G * d.ncells); A(e->g_cp, G * d.ncells);
     A(e->g_rv, G); A(e->g_rw, G); A(e->g_sv, G);
@@ -449,6 +458,9 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.estop_ctr += b * ES_COUNT;
     v.tt_ctr += b * TT_COUNT;
     v.fp_ctr += b * FP_COUNT;
+    v.gm_ctr += b * GM_COUNT;
+    v.gm_state += b * GM_STATE_WORDS;
+    v.gm_g += b * 2 * AZX_CELL_STRIDE;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
     if (v.row_prob) v.row_prob += b * nc * AZX_CELL_STRIDE;
     if (v.row_k) v.row_k += b * nc;
@@ -486,6 +498,14 @@ static std::string forced_text(const azx_engine *e) {
     if (!(e->fp_k > 0.0f)) return "off";
     char t[64];
     snprintf(t, sizeof t, "%.9g/%s", (double)e->fp_k, e->fp_prune ? "prune" : "noprune");
+    return t;
+}
+
+static std::string gumbel_text(const azx_engine *e) {
+    if (e->gm_m == 0) return "off";
+    char t[96];
+    snprintf(t, sizeof t, "%d/%.9g/%.9g/%s", e->gm_m, (double)e->gm_c_visit, (double)e->gm_c_scale,
+             e->gm_rows ? "rows" : "norows");
     return t;
 }
 
@@ -528,6 +548,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " estop=" + (e->estop_on ? "on" : "off") +
                        " targets=" + targets_text(e) +
                        " forced=" + forced_text(e) +
+                       " gumbel=" + gumbel_text(e) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -2104,6 +2125,9 @@ extern "C" int azx_resign_stats(azx_engine *e, int64_t out8[8]) {
 extern "C" int azx_set_early_stop(azx_engine *e, int on) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     if (on != 0 && on != 1) return fail(AZX_EINVAL, "early stop: on must be 0 or 1, got %d", on);
+    if (on != 0 && e->gm_m != 0)
+        return fail(AZX_EINVAL, "early stop: the engine has the Gumbel root search set, which does not play the PUCT visit "
+                                "leader (clear it with azx_set_gumbel(e, 0, 0, 1, 0))");
     ENGINE_GUARD(e);
     HIPCHECK(hipMemsetAsync(e->d.estop_ctr, 0, (size_t)e->d.G * ES_COUNT * sizeof(unsigned long long), e->stream));
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -2169,6 +2193,9 @@ extern "C" int azx_set_forced_playouts(azx_engine *e, float k, int prune) {
     if (prune != 0 && prune != 1) return fail(AZX_EINVAL, "forced playouts: prune must be 0 or 1, got %d", prune);
     if (k == 0.0f && prune == 1)
         return fail(AZX_EINVAL, "forced playouts: pruning needs forcing (k > 0): the prune gives back at most the forced quota");
+    if (k != 0.0f && e->gm_m != 0)
+        return fail(AZX_EINVAL, "forced playouts: the engine has the Gumbel root search set, whose root selects are not "
+                                "PUCT's (clear it with azx_set_gumbel(e, 0, 0, 1, 0))");
     ENGINE_GUARD(e);
     HIPCHECK(hipMemsetAsync(e->d.fp_ctr, 0, (size_t)e->d.G * FP_COUNT * sizeof(unsigned long long), e->stream));
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -2194,6 +2221,101 @@ extern "C" int azx_forced_playouts_stats(azx_engine *e, int64_t out4[4]) {
     for (int j = 0; j < 4; ++j) out4[j] = 0;
     for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
         for (int j = 0; j < FP_COUNT; ++j) out4[j] += (int64_t)hc[g * FP_COUNT + j];
+    return AZX_OK;
+}
+
+// ---- Gumbel root search with sequential halving (include/azx.h; NOT the reference's behaviour) ------
+extern "C" int azx_set_gumbel(azx_engine *e, int m, float c_visit, float c_scale, int improved_rows) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    if (m != 0 && (m < 2 || m > 64)) return fail(AZX_EINVAL, "gumbel: m must be 0 (off) or in [2, 64], got %d", m);
+    if (m != 0) {
+        if (!(c_visit >= 0.0f && c_visit <= 1.0e4f))     // NaN fails both comparisons
+            return fail(AZX_EINVAL, "gumbel: c_visit must be in [0, 1e4], got %g", (double)c_visit);
+        if (!(c_scale > 0.0f && c_scale <= 100.0f))
+            return fail(AZX_EINVAL, "gumbel: c_scale must be in (0, 100], got %g", (double)c_scale);
+        if (improved_rows != 0 && improved_rows != 1)
+            return fail(AZX_EINVAL, "gumbel: improved_rows must be 0 or 1, got %d", improved_rows);
+        if (e->fp_k > 0.0f)
+            return fail(AZX_EINVAL, "gumbel: the engine has forced playouts set, a rule about PUCT's root selects "
+                                    "(clear them with azx_set_forced_playouts(e, 0, 0))");
+        if (e->estop_on)
+            return fail(AZX_EINVAL, "gumbel: the engine has early stop set, a rule about the PUCT visit leader "
+                                    "(clear it with azx_set_early_stop(e, 0))");
+    }
+    ENGINE_GUARD(e);
+    HIPCHECK(hipMemsetAsync(e->d.gm_ctr, 0, (size_t)e->d.G * GM_COUNT * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipMemsetAsync(e->d.gm_state, 0, (size_t)e->d.G * GM_STATE_WORDS * sizeof(uint64_t), e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->gm_m = m;
+    e->gm_c_visit = m ? c_visit + 0.0f : 0.0f;
+    e->gm_c_scale = m ? c_scale : 0.0f;
+    e->gm_rows = m ? improved_rows : 0;
+    return AZX_OK;
+}
+
+extern "C" int azx_get_gumbel(azx_engine *e, int *m, float *c_visit, float *c_scale, int *improved_rows) {
+    if (!e || !m || !c_visit || !c_scale || !improved_rows) return fail(AZX_EINVAL, "null argument");
+    *m = e->gm_m;
+    *c_visit = e->gm_c_visit;
+    *c_scale = e->gm_c_scale;
+    *improved_rows = e->gm_rows;
+    return AZX_OK;
+}
+
+extern "C" int azx_gumbel_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * GM_COUNT);
+    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.gm_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < 4; ++j) out4[j] = 0;
+    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
+        for (int j = 0; j < GM_COUNT; ++j) out4[j] += (int64_t)hc[g * GM_COUNT + j];
+    return AZX_OK;
+}
+
+extern "C" int azx_gumbel_state(azx_engine *e, uint64_t *candidates, uint64_t *survivors) {
+    if (!e || !candidates || !survivors) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    const size_t G = e->d.G;
+    std::vector<uint64_t> hs(G * GM_STATE_WORDS);
+    HIPCHECK(hipMemcpyAsync(hs.data(), e->d.gm_state, hs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (size_t g = 0; g < G; ++g)
+        for (int s = 0; s < 3; ++s) {
+            candidates[g * 3 + s] = hs[g * GM_STATE_WORDS + GM_CAND + s];
+            survivors[g * 3 + s] = hs[g * GM_STATE_WORDS + GM_SURV + s];
+        }
+    return AZX_OK;
+}
+
+extern "C" int azx_gumbel_variate(uint64_t seed, int64_t uid, int ply, int child, double *g) {
+    if (!g) return fail(AZX_EINVAL, "null argument");
+    if (ply < 0) return fail(AZX_EINVAL, "ply %d is negative", ply);
+    if (child < 0 || child >= AZX_CELL_STRIDE) return fail(AZX_EINVAL, "child %d outside [0, %d)", child, AZX_CELL_STRIDE);
+    *g = azx_gumbel_of_word_host(azx_gumbel_word(seed, uid, ply, child));
+    return AZX_OK;
+}
+
+// ---- self-test hook (tests): the device's Gumbel variates of raw Philox words ----------------
+extern "C" int azx_selftest_gumbel(int device, int n, const uint32_t *words, float *g_out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AZX_ENODEV, "no HIP device visible");
+    if (n < 1 || !words || !g_out) return fail(AZX_EINVAL, "bad argument");
+    DevGuard guard(device);
+    uint32_t *dw = nullptr;
+    float *dg = nullptr;
+    hipError_t err = hipMalloc(&dw, (size_t)n * 4);
+    if (err == hipSuccess) err = hipMalloc(&dg, (size_t)n * 4);
+    if (err == hipSuccess) err = hipMemcpy(dw, words, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        azx_launch_gumbel_test(dw, dg, n, nullptr);
+        err = hipDeviceSynchronize();
+    }
+    if (err == hipSuccess) err = hipMemcpy(g_out, dg, (size_t)n * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(dw); (void)hipFree(dg);                       // (on every path)
+    if (err != hipSuccess) return fail(AZX_EHIP, "azx_selftest_gumbel: %s", hipGetErrorString(err));
     return AZX_OK;
 }
 
@@ -2535,6 +2657,9 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (a->fp_k > 0.0f || b->fp_k > 0.0f)
         return fail(AZX_EINVAL, "engine %s has forced playouts set: a match searches and draws every ply as the "
                                 "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", a->fp_k > 0.0f ? "a" : "b");
+    if (a->gm_m != 0 || b->gm_m != 0)
+        return fail(AZX_EINVAL, "engine %s has the Gumbel root search set: a match searches and draws every ply as the "
+                                "reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", a->gm_m != 0 ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2814,6 +2939,10 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->fp_k > 0.0f)
             return fail(AZX_EINVAL, "engine %d has forced playouts set: a tournament searches and draws every ply as the "
                                     "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->gm_m != 0)
+            return fail(AZX_EINVAL, "engine %d has the Gumbel root search set: a tournament searches and draws every ply as "
+                                    "the reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

@@ -170,7 +170,21 @@ struct DevEngine {
                                 // n > 0 and n * n < (k * P) * S, if there is one, instead of the PUCT argmax
     int32_t fp_prune;           // 1: the move draw and the row of a full ply are made from the pruned counts
     unsigned long long *fp_ctr;       // [G][FP_COUNT] per game (no atomics), azx_forced_playouts_stats' array; the host sums
+    // Gumbel root search with sequential halving (azx_set_gumbel; NOT the reference's behaviour), handed to the same
+    // launches only and "off" (gm_m == 0) in every other (include/azx.h has the definition)
+    int32_t gm_m;               // 0: off; else the number of root candidates sampled without replacement
+    int32_t gm_rows;            // 1: a recorded row is the policy improved by the completed Q-values
+    float gm_c_visit, gm_c_scale;
+    uint64_t *gm_state;         // [G][GM_STATE_WORDS] per game: the candidate mask of the slot's last searched ply (bit
+                                // c & 63 of word c >> 6, c the child index) and, from GM_SURV on, the survivors'
+    float *gm_g;                // [G][2][AZX_CELL_STRIDE] per game, by child index: g_j of the ply being searched (0 on a
+                                // greedy ply), written by the launch that begins the ply's search; the top of batch 0
+                                // makes it a_j = g_j + ln P_j and puts ln P_j in the second row
+    unsigned long long *gm_ctr;       // [G][GM_COUNT] per game (no atomics), azx_gumbel_stats' array; the host sums
 };
+// plies chosen under the option, halvings performed, root selects made under the option, rows recorded as the improved policy
+enum { GM_PLIES = 0, GM_HALVINGS, GM_SELECTS, GM_ROWS, GM_COUNT = 4 };
+enum { GM_CAND = 0, GM_SURV = 4, GM_STATE_WORDS = 8 };
 // full plies chosen under the option, selects whose forced set was non-empty, recorded rows with a reduced child,
 // visits removed from recorded rows
 enum { FP_PLIES = 0, FP_FORCED, FP_ROWS_PRUNED, FP_REMOVED, FP_COUNT = 4 };

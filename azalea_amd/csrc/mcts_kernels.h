@@ -32,6 +32,7 @@ void azx_launch_arith(const float *a, const float *b, float *sq, float *dv, floa
                       hipStream_t st);
 void azx_launch_divide_test(const float *num, const float *den, float *q, float *rt, int n, hipStream_t st);
 void azx_launch_noise_test(float alpha, const float *tab, int k, int n_rows, uint32_t seed, float *out, hipStream_t st);
+void azx_launch_gumbel_test(const uint32_t *words, float *g, int n, hipStream_t st);
 // inverse-CDF correction table of the device gamma sampler for one alpha: AZX_GAMMA_TAB_FLOATS floats
 #define AZX_GAMMA_TAB_FLOATS 802
 void azx_gamma_table(double alpha, float *tab);

@@ -21,6 +21,7 @@
 #include "azx_dev.h"
 #include "mcts_kernels.h"
 #include "playout_cap.h"
+#include "gumbel.h"
 #include "resign.h"
 
 __constant__ uint64_t c_geo[AZX_GEO_CELLS * 4];
@@ -92,16 +93,7 @@ struct Philox {
     uint32_t k0, k1;
     __device__ __forceinline__ void gen(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                         uint32_t out[4]) const {
-        uint32_t a = k0, b = k1;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ a, n1 = (uint32_t)p1;
-            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ b, n3 = (uint32_t)p0;
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-            a += 0x9E3779B9u; b += 0xBB67AE85u;
-        }
-        out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+        azx_philox4x32_10(k0, k1, c0, c1, c2, c3, out);      // (gumbel.h: one restatement, for host and device)
     }
 };
 __device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
@@ -414,14 +406,92 @@ __device__ __forceinline__ void compact_tree(const DevEngine &E, int g, TreeHdr 
 
 #ifdef AZX_WPE
 #define AZX_MCTS_ATTR __attribute__((amdgpu_waves_per_eu(AZX_WPE, AZX_WPE)))
+#define AZX_MCTS_WPE(S, F) AZX_MCTS_ATTR
 #define AZX_PLAY_ATTR(S) AZX_MCTS_ATTR
 #else
 #define AZX_MCTS_ATTR
+// k_mcts, stated at the occupancy each instantiation has had since forced playouts (profiles/gumbel_resources.txt): the
+// Gumbel root search's batch boundary, a rare branch of the select loop, sits close under the register bound of that
+// occupancy (k_mcts<3, FAST>: 128 of 128).  As the code stands nothing is spilled under these bounds; with the bound
+// stated, anything added to the boundary spills there instead of taking an occupancy step from every search.
+#define AZX_MCTS_WPE(S, F) __attribute__((amdgpu_waves_per_eu((F) ? ((S) == 2 ? 5 : 4) : ((S) == 2 ? 4 : 3))))
 #define AZX_PLAY_ATTR(S) __attribute__((amdgpu_waves_per_eu((S) == 2 ? 4 : 2)))     // k_play, see there
 #endif
 // The ply's move is drawn at temperature 0 (policy.py:142-149): choose_body's T and the early stop's gate
 __device__ __forceinline__ bool draw_is_greedy(const DevEngine &E, int ply) {
     return ply >= E.exploration_depth || !(E.temperature > 0.0f);
+}
+
+// ---- Gumbel root search with sequential halving (azx_set_gumbel; NOT the reference's behaviour) --------------------
+// include/azx.h has the definition.  The noise g_j is a function of (seed, uid, ply, j) alone, so the launch that begins
+// a ply's search writes it once, for every child index, into the game's gm_g row -- before the search's registers are
+// live: Philox and two accurate logarithms inside the select loop cost every tree kernel an occupancy step -- and the
+// batch boundaries and the move draw read it back.  0 on a greedy ply.
+__device__ __forceinline__ void gumbel_fill(const DevEngine &E, int g, int64_t uid, int ply, int lane) {
+    const bool greedy = draw_is_greedy(E, ply);
+    float *row = E.gm_g + (size_t)g * (2 * AZX_CELL_STRIDE);
+    for (int j = lane; j < E.ncells; j += 64)
+        row[j] = greedy ? 0.0f : azx_gumbel_of_word(azx_gumbel_word(E.seed, uid, ply, j));
+}
+// sigma of the root's children, one per lane-slot (ok[s]), from their visits n and values w and their stored priors P:
+// sigma = ((c_visit + n_max) * c_scale) * qh, qh the child's own 0.5 * ((-w) / n) + 0.5 where it is visited and the
+// prior-weighted mean vh of the visited children's qh otherwise (0.5 when none is).  float32, unfused, IEEE divide.
+template <int SLOTS>
+__device__ __forceinline__ void gumbel_sigma(float c_visit, float c_scale, const bool *ok, const float *n,
+                                             const float *w, const float *P, float *sig) {
+    float nmax = 0.0f, num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+        sig[s] = 0.0f;
+        if (ok[s] && n[s] > 0.0f) {
+            sig[s] = 0.5f * ((-w[s]) / n[s]) + 0.5f;
+            num += P[s] * sig[s];
+            den += P[s];
+            nmax = fmaxf(nmax, n[s]);
+        }
+        __builtin_amdgcn_sched_barrier(0);                    // one slot's divide at a time: registers, not speed
+    }
+    nmax = wave_max(nmax);
+    num = wave_sum(num);
+    den = wave_sum(den);
+    const float vh = den > 0.0f ? num / den : 0.5f;
+    const float scale = (c_visit + nmax) * c_scale;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) sig[s] = ok[s] ? scale * (n[s] > 0.0f ? sig[s] : vh) : 0.0f;
+}
+
+// The cnt lane-slots of `from` with the largest keys, ties to the lower index (slot-major, lane-minor), as wave-uniform
+// masks: cnt <= 64 rounds of one wave maximum each.  (key + 0.0f folds -0 into +0: equal floats, equal keys.)
+template <int SLOTS>
+__device__ __forceinline__ void gumbel_top(const float *key, const uint64_t *from, int cnt, uint64_t *out) {
+    uint64_t avail[SLOTS];
+    uint32_t kk[SLOTS];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+        avail[s] = from[s];
+        out[s] = 0ull;
+        kk[s] = f32_key(key[s] + 0.0f);
+    }
+    for (int t = 0; t < cnt; ++t) {
+        uint32_t lk = 0u;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint32_t x = lane_bit(avail[s]) ? kk[s] : 0u;
+            lk = x > lk ? x : lk;
+        }
+        const uint32_t wmax = wave_max_u32(lk);
+        bool done = false;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint64_t eq = __ballot(kk[s] == wmax) & avail[s];
+            if (eq && !done) {
+                const uint64_t bit = eq & (0ull - eq);
+                out[s] |= bit;
+                avail[s] &= ~bit;
+                done = true;
+            }
+        }
+    }
 }
 
 template <int SLOTS, bool FAST>
@@ -494,6 +564,19 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     // (k travels as its bit pattern in one scalar register, tested as an integer: the host hands +0.0f for "off")
     const int fp_kbits = __builtin_amdgcn_readfirstlane(cap_full ? __float_as_int(E.fp_k) : 0);
     uint32_t c_forced = 0;
+    // Gumbel root search (azx_set_gumbel; NOT the reference's behaviour, 0 unless the host hands a play-mode launch the
+    // option): the survivors of the sequential halving as wave-uniform masks by child index.  They are chosen at the top
+    // of batch 0 and halved at the top of later batches (gm_boundary below); a search that spans several launches finds
+    // them in gm_state again.  The root level of every select descends into the survivor with the fewest visits.
+    const int gm_m = __builtin_amdgcn_readfirstlane(E.gm_m);
+    uint64_t gsurv[SLOTS];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) gsurv[s] = 0ull;
+    if (gm_m != 0 && (mode & MODE_BEGIN)) gumbel_fill(E, g, gh->uid, ply, lane);
+    if (!FAST && gm_m != 0 && !(mode & MODE_BEGIN)) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) gsurv[s] = E.gm_state[(size_t)g * GM_STATE_WORDS + GM_SURV + s];
+    }
 
     if (mode & MODE_BEGIN) {
         batches_left = cap_full ? num_batches : E.cap_fast_batches;
@@ -1029,6 +1112,86 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         // child, is applied as soon as that child is known).
         int pk_rank = 0, pk_cell = 0, pk_link = 0;
         float pk_nv = 0.0f;
+        // Gumbel root search, the top of batch b = NBt - batches_left (the earlier batches are backed up, their virtual
+        // losses undone): at b == 0 the m0 = min(m, k) candidates with the largest g + ln P become the survivors; the
+        // survivors are halved -- the ceil(|S| / 2) largest g + ln P + sigma stay -- once for every r in 1..R-1 with
+        // floor(r * NBt / R) == b, R = max(1, ceil(log2 m0)).  Rare (R times per search) and all inside the option.
+        auto gm_boundary = [&]() __attribute__((always_inline)) {
+            const int NBt = cap_full ? num_batches : E.cap_fast_batches;
+            const int b = NBt - batches_left;
+            const int m0 = gm_m < k_root ? gm_m : k_root;
+            const int R = m0 <= 1 ? 1 : 32 - __clz(m0 - 1);
+            int nh = 0;
+            for (int r = 1; r < R; ++r) nh += (r * NBt >= b * R && r * NBt < (b + 1) * R) ? 1 : 0;
+            if (b != 0 && nh == 0) return;
+            // Room for what follows, inside this branch: the node cache is written back and the last batch's per-leaf
+            // words, dead here but live to the compiler (each batch rewrites them lane by lane), are cleared.
+            cache_flush();
+            m_node = -1; m_len = 0; m_link = 0; m_tm = 0; m_cells = 0; m_uidx = 0; m_k = 0; m_slot1 = -1;
+            m_val = 0.0f;
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) m_mask[s] = 0ull;
+            // gm_g row of the game: g_j from gumbel_fill; batch 0 adds ln P_j in place (a_j) and keeps ln P_j behind it
+            // (the row's address is formed HERE: hoisted to the launch's entry as a per-lane pointer it was spilled there,
+            // a scratch store in every launch, option or not)
+            float *gbase = E.gm_g;
+            asm volatile("" : "+s"(gbase));
+            float *grow = gbase + (size_t)g * (2 * AZX_CELL_STRIDE);
+            bool ok[SLOTS];
+            float key[SLOTS], gn[SLOTS], gw[SLOTS], gp[SLOTS], sig[SLOTS];
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                ok[s] = lane_bit(rootrm[s]);
+                key[s] = ok[s] ? grow[s * 64 + lane] : 0.0f;
+                if (b == 0 && ok[s]) {
+                    const float lp = logf(rst[s].z);
+                    key[s] = key[s] + lp;
+                    grow[s * 64 + lane] = key[s];
+                    grow[AZX_CELL_STRIDE + s * 64 + lane] = lp;
+                }
+                __builtin_amdgcn_sched_barrier(0);                // one slot's logarithm at a time
+            }
+            uint64_t *st = E.gm_state + (size_t)g * GM_STATE_WORDS;
+            uint64_t ns[SLOTS];                                   // the new survivors
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) ns[s] = gsurv[s];
+            if (b == 0) {
+                gumbel_top<SLOTS>(key, rootrm, m0, ns);
+                if (lane == 0) {
+#pragma unroll
+                    for (int s = 0; s < SLOTS; ++s) st[GM_CAND + s] = ns[s];
+                }
+            }
+            if (nh != 0) {
+#pragma unroll
+                for (int s = 0; s < SLOTS; ++s) { gn[s] = rst[s].x; gw[s] = rst[s].y; gp[s] = rst[s].z; }
+                gumbel_sigma<SLOTS>(E.gm_c_visit, E.gm_c_scale, ok, gn, gw, gp, sig);
+#pragma unroll
+                for (int s = 0; s < SLOTS; ++s) key[s] = key[s] + sig[s];
+                for (int h = 0; h < nh; ++h) {
+                    int cnt = 0;
+                    uint64_t from[SLOTS];
+#pragma unroll
+                    for (int s = 0; s < SLOTS; ++s) { from[s] = ns[s]; cnt += popc64(ns[s]); }
+                    gumbel_top<SLOTS>(key, from, (cnt + 1) >> 1, ns);
+                }
+                if (lane == 0) E.gm_ctr[(size_t)g * GM_COUNT + GM_HALVINGS] += (unsigned long long)nh;
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int s = 0; s < SLOTS; ++s) st[GM_SURV + s] = ns[s];
+            }
+            // the select loop takes them from gm_state again, as a launch that continues a search does: handed over in
+            // registers, the boundary's scalar code and the root level's were allocated as one and cost the tree kernels
+            // an occupancy step
+            wave_mem_sync();
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const uint64_t v = *(volatile uint64_t *)(st + GM_SURV + s);
+                gsurv[s] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                           (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+            }
+        };
         auto root_pick = [&](int sel, auto rs_tag) __attribute__((always_inline)) {
             constexpr int RS = decltype(rs_tag)::value;
             // sqrt(sum of the children's visits), mcts.py:132: the sum is the integer root_sumn.  A scalar
@@ -1037,46 +1200,65 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             // flight that this function is meant to overlap)
             const int sumn = root_sumn;
             const float sq_tab = c_sqrt[sumn < AZX_SQRT_TAB ? sumn : AZX_SQRT_TAB - 1];
-            float nz[SLOTS] = {};
-            const bool noisy = E.noise_scale != 0.0 && cap_full;
-            float Pn[SLOTS];
+            int best_idx = 0x7fffffff;
+            if (gm_m != 0) {
+                // the survivor with the fewest visits as this select sees them (virtual losses of the batch in flight
+                // included), ties to the lower index; no Dirichlet noise, no scores
+                uint32_t lk = 0u;
 #pragma unroll
-            for (int s = 0; s < RS; ++s) Pn[s] = rst[s].z;
-            if (noisy) {
-                if (FAST || E.device_noise) {
-                    // one stream word per (game, move, select): a Weyl sequence from the per-move
-                    // base through one mixer (splitmix construction)
-                    const uint32_t noise_stream = mix32(noise_base + (uint32_t)sel * 0x9E3779B9u);
-                    dirichlet_noise<RS>(rootrm, lane, noise_stream, gconst, (float)E.noise_scale, nz);
-                    // (1 - eps) * P, mcts.py:130: the same float32 product every select, so it
-                    // is formed once per launch (rkp) and only the noise is added here
-#pragma unroll
-                    for (int s = 0; s < RS; ++s) Pn[s] = rkp[s] + nz[s];
-                } else {
-                    const double *row = E.noise + ((size_t)g * E.n_select + sel) * E.noise_stride;
-#pragma unroll
-                    for (int s = 0; s < RS; ++s)
-                        if (lane_bit(rootrm[s]))
-                            Pn[s] = (float)((double)(keep32 * Pn[s]) + E.noise_scale * row[64 * s + lane]);
+                for (int s = 0; s < RS; ++s) {
+                    const uint32_t x = lane_bit(gsurv[s]) ? ~(uint32_t)(int)rst[s].x : 0u;
+                    lk = x > lk ? x : lk;
                 }
-            }
-            const float sq = sqrt_of(sq_tab, sumn);
-            // the forced set, over the priors this select scores with and the counts it sees (virtual losses of the
-            // batch in flight included): its lowest-index member is taken in place of the argmax.  Found BEFORE the
-            // scores, into one scalar, so that its two temporaries are dead where the scoring's registers peak.
-            int forced_idx = -1;
-            if (fp_kbits != 0) {
-                const float S = (float)sumn, fp_k = __int_as_float(fp_kbits);
+                const uint32_t wmax = wave_max_u32(lk);
 #pragma unroll
                 for (int s = RS - 1; s >= 0; --s) {
-                    const float n = rst[s].x;
-                    const uint64_t fm = __ballot(n > 0.0f && n * n < (fp_k * Pn[s]) * S) & rootrm[s];
-                    if (fm) forced_idx = s * 64 + (int)__ffsll((long long)fm) - 1;
+                    const uint64_t eq = __ballot(~(uint32_t)(int)rst[s].x == wmax) & gsurv[s];
+                    if (eq) best_idx = s * 64 + (int)__ffsll((long long)eq) - 1;
                 }
-                if (forced_idx >= 0) c_forced += 1;
+                if (best_idx == 0x7fffffff) best_idx = 0;     // (no survivor: cannot happen once batch 0 has begun)
+            } else {
+                float nz[SLOTS] = {};
+                const bool noisy = E.noise_scale != 0.0 && cap_full;
+                float Pn[SLOTS];
+#pragma unroll
+                for (int s = 0; s < RS; ++s) Pn[s] = rst[s].z;
+                if (noisy) {
+                    if (FAST || E.device_noise) {
+                        // one stream word per (game, move, select): a Weyl sequence from the per-move
+                        // base through one mixer (splitmix construction)
+                        const uint32_t noise_stream = mix32(noise_base + (uint32_t)sel * 0x9E3779B9u);
+                        dirichlet_noise<RS>(rootrm, lane, noise_stream, gconst, (float)E.noise_scale, nz);
+                        // (1 - eps) * P, mcts.py:130: the same float32 product every select, so it
+                        // is formed once per launch (rkp) and only the noise is added here
+#pragma unroll
+                        for (int s = 0; s < RS; ++s) Pn[s] = rkp[s] + nz[s];
+                    } else {
+                        const double *row = E.noise + ((size_t)g * E.n_select + sel) * E.noise_stride;
+#pragma unroll
+                        for (int s = 0; s < RS; ++s)
+                            if (lane_bit(rootrm[s]))
+                                Pn[s] = (float)((double)(keep32 * Pn[s]) + E.noise_scale * row[64 * s + lane]);
+                    }
+                }
+                const float sq = sqrt_of(sq_tab, sumn);
+                // the forced set, over the priors this select scores with and the counts it sees (virtual losses of the
+                // batch in flight included): its lowest-index member is taken in place of the argmax.  Found BEFORE the
+                // scores, into one scalar, so that its two temporaries are dead where the scoring's registers peak.
+                int forced_idx = -1;
+                if (fp_kbits != 0) {
+                    const float S = (float)sumn, fp_k = __int_as_float(fp_kbits);
+#pragma unroll
+                    for (int s = RS - 1; s >= 0; --s) {
+                        const float n = rst[s].x;
+                        const uint64_t fm = __ballot(n > 0.0f && n * n < (fp_k * Pn[s]) * S) & rootrm[s];
+                        if (fm) forced_idx = s * 64 + (int)__ffsll((long long)fm) - 1;
+                    }
+                    if (forced_idx >= 0) c_forced += 1;
+                }
+                const int argmax_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq);
+                best_idx = forced_idx >= 0 ? forced_idx : argmax_idx;
             }
-            const int argmax_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq);
-            const int best_idx = forced_idx >= 0 ? forced_idx : argmax_idx;
             const int bl = best_idx & 63, bsl = best_idx >> 6;
 #pragma unroll
             for (int s = 0; s < RS; ++s) {
@@ -1096,6 +1278,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             else root_pick(sel, std::integral_constant<int, 1>{});
         };
 
+        if (__builtin_expect(gm_m != 0, 0)) gm_boundary();
         root_pick_any(select_count);
         memo_ok = true;
         for (int i = 0; i < bs; ++i) {
@@ -1471,6 +1654,8 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             es[ES_SKIPPED] += (unsigned long long)(-1 - es_r1);
         }
         if (c_forced) E.fp_ctr[(size_t)g * FP_COUNT + FP_FORCED] += c_forced;
+        // azx_gumbel_stats: every select of a search under the option makes its root level under it
+        if (gm_m != 0 && c_selects) E.gm_ctr[(size_t)g * GM_COUNT + GM_SELECTS] += c_selects;
     }
     // the six per-game tallies, one lane each (as six scalar read-modify-writes the compiler waited
     // for each load in turn: six memory round trips at the end of every launch)
@@ -1484,7 +1669,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
 }
 
 template <int SLOTS, bool FAST>
-__global__ __launch_bounds__(64) AZX_MCTS_ATTR void k_mcts(DevEngine E, int mode_arg, int num_batches) {
+__global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, FAST) void k_mcts(DevEngine E, int mode_arg, int num_batches) {
     mcts_body<SLOTS, FAST>(E, mode_arg, num_batches);
 }
 
@@ -2035,6 +2220,77 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
             }
         }
     }
+    // Gumbel root search (azx_set_gumbel; NOT the reference's behaviour; include/azx.h has the definition): the move is
+    // the survivor with the largest g + ln P + sigma, ties to the lower index, whatever was drawn above; pi, the policy
+    // improved by the completed Q-values, is softmax(ln P + sigma) over all children; metric 2 is ln pi of the move.
+    // A playout cap's fast plies are chosen this way too.
+    float gm_pi[SLOTS], gm_logp = 0.0f;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) gm_pi[s] = 0.0f;
+    if (E.gm_m != 0) {
+        bool ok[SLOTS];
+        float cn[SLOTS], cw[SLOTS], cp[SLOTS], lp[SLOTS], ga[SLOTS], sig[SLOTS];
+        uint64_t from[SLOTS], top[SLOTS];
+        bool any = false;
+        const float *grow = E.gm_g + (size_t)g * (2 * AZX_CELL_STRIDE);   // a_j and ln P_j, by child index
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            ok[s] = lane_bit(mk.m[s]);
+            ga[s] = 0.0f;
+            lp[s] = 0.0f;
+            cn[s] = 0.0f;
+            cw[s] = 0.0f;
+            cp[s] = 0.0f;
+            if (ok[s]) {
+                const Node c = arena[rootn.link + rk[s]];
+                cn[s] = c.nv;
+                cw[s] = c.tv;
+                cp[s] = c.pp;
+                ga[s] = grow[rk[s]];
+                lp[s] = grow[AZX_CELL_STRIDE + rk[s]];
+            }
+        }
+        gumbel_sigma<SLOTS>(E.gm_c_visit, E.gm_c_scale, ok, cn, cw, cp, sig);
+        const uint64_t *st = E.gm_state + (size_t)g * GM_STATE_WORDS + GM_SURV;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint64_t word = ok[s] ? st[rk[s] >> 6] : 0ull;
+            from[s] = __ballot(((word >> (rk[s] & 63)) & 1ull) != 0ull);
+            any = any || from[s] != 0ull;
+        }
+        if (!any) {                                          // (no survivor recorded: every child stands)
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) from[s] = mk.m[s];
+        }
+        float xm = -3.0e38f;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            lp[s] = lp[s] + sig[s];                          // the softmax's argument
+            ga[s] = ga[s] + sig[s];                          // the key
+            if (ok[s]) xm = fmaxf(xm, lp[s]);
+        }
+        gumbel_top<SLOTS>(ga, from, 1, top);
+        xm = wave_max(xm);
+        float es = 0.0f;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            gm_pi[s] = ok[s] ? expf(lp[s] - xm) : 0.0f;
+            es += gm_pi[s];
+        }
+        es = wave_sum(es);
+        bool have = false;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            gm_pi[s] = gm_pi[s] / es;
+            if (top[s] && !have) {
+                const int l = (int)__ffsll((long long)top[s]) - 1;
+                chosen = __builtin_amdgcn_readlane(rk[s], l);
+                gm_logp = (readlane_f(lp[s], l) - xm) - logf(es);
+                have = true;
+            }
+        }
+        if (lane == 0) E.gm_ctr[(size_t)g * GM_COUNT + GM_PLIES] += 1ull;
+    }
     // early stop (azx_set_early_stop): the T = 0 plies searched under the option, fast plies included
     if (E.early_stop != 0 && lane == 0 && draw_is_greedy(E, ply)) E.estop_ctr[(size_t)g * ES_COUNT + ES_T0_PLIES] += 1ull;
     // forced playouts (azx_set_forced_playouts): the full plies chosen under the option
@@ -2062,7 +2318,8 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
     for (int s = 0; s < SLOTS; ++s) {
         const int cell = s * 64 + lane;
         if (cell < AZX_CELL_STRIDE) E.row_board[rb + cell] = (unsigned char)(h.c[s] & 3u);
-        if (lane_bit(mk.m[s])) E.row_prob[rb + rk[s]] = (tt_vis ? nv[s] : w[s]) / row_den;
+        if (lane_bit(mk.m[s]))
+            E.row_prob[rb + rk[s]] = (E.gm_m != 0 && E.gm_rows != 0) ? gm_pi[s] : (tt_vis ? nv[s] : w[s]) / row_den;
     }
     for (int o = mk.k + lane; o < AZX_CELL_STRIDE; o += 64) E.row_prob[rb + o] = 0.0f;
     if (lane == 0) {
@@ -2070,7 +2327,7 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
         gh->n_rows = row + 1;
         float rs_v;
         gh->move_id = resign_judge(E, g, gh, th, ply, chosen, &rs_v);
-        const float logp = __logf(chosen_w / tot);
+        const float logp = E.gm_m != 0 ? gm_logp : __logf(chosen_w / tot);
         // mcts.py:291 (as azx_get_root reports it); under early stop the mean is over the selects the ply made
         // (0 where a stopped ply made none: the carried subtree's leader was already out of reach)
         const int sval_n = E.early_stop != 0 ? th->select_count : E.selects_per_search;
@@ -2092,6 +2349,8 @@ __device__ __forceinline__ void choose_body(const DevEngine &E) {
                 if (width > 1) tc[TT_GREEDY_WIDE] += 1ull;
             }
         }
+        // azx_gumbel_stats: rows recorded as the improved policy
+        if (E.gm_m != 0 && E.gm_rows != 0) E.gm_ctr[(size_t)g * GM_COUNT + GM_ROWS] += 1ull;
         // azx_forced_playouts_stats: recorded rows with at least one reduced child, visits removed from them
         if (fp_removed > 0.0f) {
             unsigned long long *fc = E.fp_ctr + (size_t)g * FP_COUNT;
@@ -2214,6 +2473,16 @@ __global__ void k_divide_test(const float *num, const float *den, float *q, floa
         const int v = (int)den[j];
         rt[j] = (v >= 0 && v < AZX_SQRT_TAB) ? c_sqrt[v] : 0.0f;
     }
+}
+
+// ---- device Gumbel variates of raw Philox words (azx_selftest_gumbel), by the function the tree kernels use ----
+__global__ void k_gumbel_test(const uint32_t *words, float *g, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) g[i] = azx_gumbel_of_word(words[i]);
+}
+
+void azx_launch_gumbel_test(const uint32_t *words, float *g, int n, hipStream_t st) {
+    hipLaunchKernelGGL(k_gumbel_test, dim3((n + 255) / 256), dim3(256), 0, st, words, g, n);
 }
 
 // ---- device Dirichlet self-test: rows of k-cell noise exactly as k_mcts draws it ---------------

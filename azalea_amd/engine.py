@@ -702,6 +702,65 @@ class Engine:
         check(self.L.azx_forced_playouts_stats(self.h, _p(out, C.c_int64)))
         return {k: int(out[i]) for i, k in enumerate(self.FORCED_PLAYOUTS_STATS)}
 
+    # ---- Gumbel root search with sequential halving (azx_set_gumbel; NOT the reference's behaviour) ----
+    def set_gumbel(self, m=16, c_visit=50.0, c_scale=1.0, improved_rows=True):
+        """azx_set_gumbel: in the following play / play_device / replay_fill / play_steps calls every search is a Gumbel
+        root search (include/azx.h has the definition, DESIGN 7.14 its two deviations from Danihelka et al. 2022):
+        min(m, k) root candidates are sampled without replacement by g + ln P, the search's select batches are divided
+        among them by sequential halving on g + ln P + sigma(completed Q), no Dirichlet noise is mixed in, the final
+        survivor is played, and with improved_rows=True the recorded row is softmax(ln P + sigma) over all children.
+        improved_rows=False keeps the row the engine records otherwise (a diagnostic and test mode).  A playout cap's
+        fast plies search under the option too.  m = 0 is off; otherwise 2 <= m <= 64, c_visit in [0, 1e4], c_scale in
+        (0, 100].  The defaults c_visit = 50 and c_scale = 1.0 are the author's recollection of the paper's board-game
+        values and are not checked here.  NOT the reference's behaviour; off by default.  search(), the phase API and
+        matches are untouched; Match / Tournament refuse an engine with the option set, and it cannot be set beside
+        forced playouts or early stop (rules about PUCT visit leaders).  set_gumbel(0) clears it: the same kernels, the
+        same bytes as before.  Zeroes gumbel_stats().  Its effect on playing strength and training efficiency is NOT
+        measured."""
+        m = int(m)
+        if m != 0 and not 2 <= m <= 64:
+            raise ValueError("gumbel: m must be 0 (off) or in [2, 64], got %r" % (m,))
+        c_visit, c_scale = float(c_visit), float(c_scale)
+        if m != 0:
+            if not 0.0 <= c_visit <= 1.0e4:             # NaN fails both comparisons
+                raise ValueError("gumbel: c_visit must be in [0, 1e4], got %r" % (c_visit,))
+            if not 0.0 < c_scale <= 100.0:
+                raise ValueError("gumbel: c_scale must be in (0, 100], got %r" % (c_scale,))
+            if improved_rows not in (True, False, 0, 1):
+                raise ValueError("gumbel: improved_rows must be True or False, got %r" % (improved_rows,))
+        check(self.L.azx_set_gumbel(self.h, m, c_visit, c_scale, 1 if (m != 0 and improved_rows) else 0))
+
+    def clear_gumbel(self):
+        """set_gumbel(0): PUCT root selects, Dirichlet noise and the move draw from the counts again."""
+        check(self.L.azx_set_gumbel(self.h, 0, 0.0, 1.0, 0))
+
+    def gumbel(self):
+        """azx_get_gumbel: (m, c_visit, c_scale, improved_rows) in force, (0, 0.0, 0.0, False) when off."""
+        if getattr(self.L, "azx_get_gumbel", None) is None:     # an older build (tools/lib_bench.py): never set
+            return 0, 0.0, 0.0, False
+        m, cv, cs, rows = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_int(0)
+        check(self.L.azx_get_gumbel(self.h, C.byref(m), C.byref(cv), C.byref(cs), C.byref(rows)))
+        return int(m.value), float(cv.value), float(cs.value), bool(rows.value)
+
+    GUMBEL_STATS = ("plies", "halvings", "root_selects", "improved_rows")
+
+    def gumbel_stats(self):
+        """azx_gumbel_stats since the last set_gumbel: dict(plies, halvings, root_selects, improved_rows) -- the plies
+        chosen under the option, the halvings performed, the root selects made under the option and the rows recorded
+        as the improved policy."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_gumbel_stats(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(self.GUMBEL_STATS)}
+
+    def gumbel_state(self):
+        """azx_gumbel_state: (candidates, survivors), two uint64[n_games, 3] arrays of bit masks by child index (bit
+        c & 63 of word c >> 6) -- the m0 candidates chosen at the top of each slot's last searched ply and the survivors
+        left at its end.  Blocking; meant for tests."""
+        cand = np.zeros((self.G, 3), np.uint64)
+        surv = np.zeros((self.G, 3), np.uint64)
+        check(self.L.azx_gumbel_state(self.h, _p(cand, C.c_uint64), _p(surv, C.c_uint64)))
+        return cand, surv
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""
@@ -992,6 +1051,26 @@ def playout_cap_is_full(seed, uid, ply, full_prob):
     if rc < 0:
         raise ValueError(L.azx_last_error().decode(errors="replace"))
     return bool(rc)
+
+
+def gumbel_variate(seed, uid, ply, child):
+    """azx_gumbel_variate: g = -ln(-ln u) of root child `child` at ply `ply` (from the empty board) of game `uid` of an
+    engine created with `seed`, in double precision -- the definition of the Gumbel root search's noise (include/azx.h),
+    on the host (no GPU is needed).  ValueError for a negative ply or a child outside [0, 192)."""
+    L = _lib.lib()
+    g = C.c_double(0.0)
+    rc = L.azx_gumbel_variate(int(seed) & 0xFFFFFFFFFFFFFFFF, int(uid), int(ply), int(child), C.byref(g))
+    if rc < 0:
+        raise ValueError(L.azx_last_error().decode(errors="replace"))
+    return float(g.value)
+
+
+def selftest_gumbel(words, device=0):
+    """azx_selftest_gumbel: the device's float32 g of raw Philox words, by the function the tree kernels use."""
+    words = np.ascontiguousarray(words, np.uint32)
+    out = np.zeros(words.shape, np.float32)
+    check(_lib.lib().azx_selftest_gumbel(device, words.size, _p(words, C.c_uint32), _p(out, C.c_float)))
+    return out
 
 
 def resign_is_exempt(seed, uid, keep_prob):

@@ -218,7 +218,7 @@ def _throughput_policy(agent, external_batch=False):
 
 def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                         games=None, external_batch: bool = False, pooled: bool = False,
-                        collect=None, info=None, openings=None) -> Dict[Pair, OutcomeCounts]:
+                        collect=None, info=None, openings=None, gumbel=None) -> Dict[Pair, OutcomeCounts]:
     """Round robin of `evaluate` -- pairs in `gen_pairs` order, `num_rounds` games per pair -- with each
     pair's games played by the two agents' engines against each other on the device (azx_match_play):
     returns {(i, j): [wins of i, 0, wins of j]}.  One engine per agent, `n_slots` games resident at a time
@@ -251,8 +251,15 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     one way round only and the following pairs' openings fall out of step with their colours.  Pooled or not, the
     games are the same; `games[pair]` gains "opening", the opening index of each game.  NOT the reference's
     behaviour, whose evaluation games all start from the empty board; off by default.  A ValueError with the
-    library's message, before any engine is made, for a book the rules refuse (engine.openings_check)."""
+    library's message, before any engine is made, for a book the rules refuse (engine.openings_check).
+    `gumbel`: refused.  The Gumbel root search (Engine.set_gumbel, Player(gumbel=...)) is a self-play option; device
+    matches and tournaments search and draw every ply as the reference does.  Anything but None / False / 0 is a
+    ValueError, before any engine is made."""
     import torch
+    from .parallel_player import normalize_gumbel
+    if normalize_gumbel(gumbel) is not None:
+        raise ValueError("evaluate_throughput: gumbel is a self-play option: device matches and tournaments search and "
+                         "draw every ply as the reference does (engine.Match refuses an engine with it set)")
     from . import engine as _eng
     from .policy import SearchTreeFull, external_evaluator, tower_flags
 

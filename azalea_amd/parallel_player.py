@@ -77,7 +77,7 @@ class Player:
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
                  openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None,
-                 forced_playouts=None):
+                 forced_playouts=None, gumbel=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -143,7 +143,18 @@ class Player:
         whenever the engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True
         (a match searches and draws as the reference does), when the games would run through the host loop, or for
         anything normalize_forced_playouts refuses.  Its effect on playing strength and training efficiency is not
-        measured."""
+        measured.
+        `gumbel` (NOT the reference's behaviour, which draws and records from PUCT visit counts under Dirichlet noise;
+        off by default): True (= m 16), an int m, an (m, c_visit, c_scale) triple or a dict with those keys plus
+        "improved_rows" sets Engine.set_gumbel (include/azx.h has the definition) on the self-play engine this Player
+        builds, device self-play or external_batch: a Gumbel root search with sequential halving at every ply, the
+        final survivor played, the recorded row the policy improved by the completed Q-values -- a search whose move
+        and row are sound at 32-100 simulations.  The defaults c_visit = 50 and c_scale = 1.0 are the author's
+        recollection of the paper's board-game values and are not checked here.  It is applied again whenever the
+        engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True (a match
+        searches and draws as the reference does), when the games would run through the host loop, together with
+        forced_playouts or early_stop (rules about PUCT visit leaders), or for anything normalize_gumbel refuses.  Its
+        effect on playing strength and training efficiency is NOT measured."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -173,6 +184,7 @@ class Player:
         self.early_stop = self._check_early_stop(early_stop)
         self.train_targets = self._check_train_targets(train_targets)
         self.forced_playouts = self._check_forced_playouts(forced_playouts)
+        self.gumbel = self._check_gumbel(gumbel)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -384,6 +396,32 @@ class Player:
                              "which selects by PUCT alone and records every visit")
         return forced_playouts
 
+    def _check_gumbel(self, gumbel):
+        """`gumbel` as an (m, c_visit, c_scale, improved_rows) tuple, or None for off; a ValueError naming what does not
+        hold."""
+        gumbel = normalize_gumbel(gumbel)
+        if gumbel is None:
+            return None
+        if self.device_match:
+            raise ValueError("gumbel is a self-play option: a device match searches and draws every ply as the "
+                             "reference does (engine.Match refuses an engine with the Gumbel root search set)")
+        if self.forced_playouts is not None or self.early_stop:
+            raise ValueError("gumbel cannot be set together with %s: that option is a rule about PUCT visit leaders, "
+                             "which a Gumbel root search does not play"
+                             % ("forced_playouts" if self.forced_playouts is not None else "early_stop"))
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("gumbel needs the games to run in a device engine (a single agent whose Policy holds a "
+                             "HexNetwork, or external_batch=True): these agents play through the host loop, which "
+                             "selects by PUCT and draws from the visit counts")
+        return gumbel
+
+    def gumbel_stats(self):
+        """Engine.gumbel_stats() of the self-play engine, or None while there is none or gumbel is not set."""
+        if self.gumbel is None or self._engine is None:
+            return None
+        return self._engine.gumbel_stats()
+
     def forced_playouts_stats(self):
         """Engine.forced_playouts_stats() of the self-play engine, or None while there is none or forced_playouts is
         not set."""
@@ -549,6 +587,8 @@ class Player:
                 self._engine.set_train_targets(*self.train_targets)
             if self.forced_playouts is not None:
                 self._engine.set_forced_playouts(*self.forced_playouts)
+            if self.gumbel is not None:
+                self._engine.set_gumbel(*self.gumbel)
             self._engine_key = key
         return self._engine
 
@@ -759,6 +799,54 @@ def normalize_forced_playouts(forced_playouts):
             raise ValueError("forced_playouts: pruning needs forcing (k > 0), got k = 0 with prune = True")
         return None
     return k, bool(prune)
+
+
+GUMBEL_DEFAULT = (16, 50.0, 1.0, True)
+
+
+def normalize_gumbel(gumbel):
+    """(m, c_visit, c_scale, improved_rows) of True (= (16, 50.0, 1.0, True)), an int m, an (m, c_visit, c_scale)
+    triple or a mapping with the keys "m", "c_visit", "c_scale", "improved_rows" (any subset: the rest default), or None
+    for off (None, False, m = 0); a ValueError unless m is an int in [2, 64], c_visit a number in [0, 1e4], c_scale a
+    number in (0, 100] and improved_rows a bool.  The defaults 50 and 1.0 are the author's recollection of the paper's
+    board-game values and are not checked here."""
+    if gumbel is None or gumbel is False:
+        return None
+    m, c_visit, c_scale, rows = GUMBEL_DEFAULT
+    if gumbel is True:
+        pass
+    elif isinstance(gumbel, dict):
+        extra = set(gumbel) - {"m", "c_visit", "c_scale", "improved_rows"}
+        if extra:
+            raise ValueError("gumbel as a dict takes the keys 'm', 'c_visit', 'c_scale' and 'improved_rows', got %r"
+                             % (sorted(map(str, gumbel)),))
+        m, c_visit = gumbel.get("m", m), gumbel.get("c_visit", c_visit)
+        c_scale, rows = gumbel.get("c_scale", c_scale), gumbel.get("improved_rows", rows)
+    elif isinstance(gumbel, (tuple, list)) and len(gumbel) == 3:
+        m, c_visit, c_scale = gumbel
+    elif isinstance(gumbel, (int, np.integer)):
+        m = gumbel
+    else:
+        raise ValueError("gumbel must be True, an int m, an (m, c_visit, c_scale) triple or a dict with those keys, "
+                         "got %r" % (gumbel,))
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)):
+        raise ValueError("gumbel: m must be an int in [2, 64] (0 is off), got %r" % (m,))
+    m = int(m)
+    if m == 0:
+        return None
+    if not 2 <= m <= 64:
+        raise ValueError("gumbel: m must be in [2, 64] (0 is off), got %r" % (m,))
+    for name, v in (("c_visit", c_visit), ("c_scale", c_scale)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("gumbel: %s must be a number, got %r" % (name, v))
+    c_visit, c_scale = float(c_visit), float(c_scale)
+    if not 0.0 <= c_visit <= 1.0e4:                  # NaN fails both comparisons
+        raise ValueError("gumbel: c_visit must be in [0, 1e4], got %r" % (c_visit,))
+    if not 0.0 < c_scale <= 100.0:
+        raise ValueError("gumbel: c_scale must be in (0, 100], got %r" % (c_scale,))
+    if not isinstance(rows, (bool, np.bool_)):
+        raise ValueError("gumbel: improved_rows must be True or False, got %r" % (rows,))
+    return m, c_visit, c_scale, bool(rows)
 
 
 def normalize_early_stop(early_stop):

@@ -376,8 +376,23 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     ranks and the actors play under it too; the random-mover player that fills the first buffer does NOT get it.  One
     log line says whether it is on.  A ValueError, before anything is built, for anything normalize_forced_playouts
     refuses; Player refuses it where the games would run through the host loop.  Its effect on playing strength and
-    on training efficiency is not measured."""
-    from .parallel_player import normalize_early_stop, normalize_train_targets, normalize_forced_playouts
+    on training efficiency is not measured.
+
+    config["gumbel"] = true, an int m, (m, c_visit, c_scale) or {"m": 16, "c_visit": 50.0, "c_scale": 1.0,
+    "improved_rows": true} (default absent; NOT the reference's behaviour, and outside every parity claim): every
+    self-play search is a Gumbel root search with sequential halving, the final survivor is played and the recorded row
+    is the policy improved by the completed Q-values (Engine.set_gumbel, include/azx.h has the definition) -- a search
+    whose move and row are sound at 32-100 simulations.  The defaults 50 and 1.0 are the author's recollection of the
+    paper's board-game values and are not checked here.  It goes to the one self-play Player built here
+    (Player(gumbel=...)); the random-mover player that fills the first buffer does NOT get it.  One log line says
+    whether it is on.  A ValueError, before anything is built, for anything normalize_gumbel refuses and together with
+    config["forced_playouts"] or config["early_stop"]; Player refuses it where the games would run through the host
+    loop.  Its effect on playing strength and on training efficiency is NOT measured."""
+    from .parallel_player import normalize_early_stop, normalize_train_targets, normalize_forced_playouts, normalize_gumbel
+    try:
+        gumbel = normalize_gumbel(config.get("gumbel"))
+    except ValueError as exc:
+        raise ValueError("config['gumbel']: %s" % exc) from None
     try:
         forced_playouts = normalize_forced_playouts(config.get("forced_playouts"))
     except ValueError as exc:
@@ -390,6 +405,10 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
         early_stop = normalize_early_stop(config.get("early_stop"))
     except ValueError as exc:
         raise ValueError("config['early_stop']: %s" % exc) from None
+    if gumbel is not None and (forced_playouts is not None or early_stop):
+        raise ValueError("config['gumbel']: gumbel cannot be set together with config['%s']: that option is a rule about "
+                         "PUCT visit leaders, which a Gumbel root search does not play"
+                         % ("forced_playouts" if forced_playouts is not None else "early_stop"))
     resign = None
     if config.get("resign") is not None:
         from .parallel_player import normalize_resign
@@ -439,7 +458,12 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
                     external_batch=bool(config.get("selfplay_external_batch", False)),
                     random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
                     resign=resign, early_stop=early_stop, train_targets=train_targets,
-                    forced_playouts=forced_playouts)
+                    forced_playouts=forced_playouts, gumbel=gumbel)
+    if leader:
+        logging.info("Gumbel root search (config['gumbel']): %s",
+                     "off" if gumbel is None else
+                     "on -- NOT the reference's behaviour: m = %d, c_visit = %g, c_scale = %g, rows = %s"
+                     % (gumbel[0], gumbel[1], gumbel[2], "the improved policy" if gumbel[3] else "from the visit counts"))
     if leader:
         logging.info("forced playouts (config['forced_playouts']): %s",
                      "off" if forced_playouts is None else

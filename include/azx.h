@@ -655,6 +655,77 @@ int azx_get_forced_playouts(azx_engine *e, float *k, int *prune);
  * array of their own: azx_debug_counters keeps its 16 words. */
 int azx_forced_playouts_stats(azx_engine *e, int64_t out4[4]);
 
+/* Gumbel root search with sequential halving, for throughput self-play (Danihelka et al. 2022, "Policy improvement by
+ * planning with Gumbel"; the paper was not at hand: THIS text is the definition, and it names its two deviations).
+ * NOT the reference's behaviour (off by default, outside every parity claim): the reference draws and records from PUCT
+ * visit counts under per-select Dirichlet noise, which carry a policy improvement only at a few hundred simulations per
+ * move.  Under the option m root candidates are sampled without replacement with Gumbel noise, the simulations are
+ * divided among them by sequential halving, the final survivor is played and the recorded row is the policy improved
+ * by the completed Q-values: a move and a row that are sound at 32-100 simulations.
+ *   All float32 arithmetic is unfused, with IEEE divide; counts are integers held in float32.  j = a root child by
+ * index; n_j, w_j, P_j = its num_visits, total_value and stored, un-noised prior; k = the number of root children;
+ * NBt = the select batches of this ply's search (simulations / search_batch_size + 1 on a full ply, the playout cap's
+ * fast batch count on a fast ply); bs = search_batch_size.
+ *   1. Noise.  r = Philox4x32-10(key of the game's uid).gen(0x47554D42, ply, j >> 2, 0x4E4F4953),
+ * u = ((r[j & 3] >> 8) + 1/2) / 2^24, g_j = -ln(-ln u).  azx_gumbel_variate is this function in double precision; the
+ * device computes a float32 with accurate logarithms (not the fast intrinsics; for the upper half of the 24-bit values,
+ * where u is no float32, -ln u is -log1pf(-(1 - u)) of the exact complement), once per ply and child, not per select.
+ * On a greedy ply (ply >= exploration_depth, or temperature == 0) g_j = 0 for all j.  Temperatures other than 0 and 1
+ * are ignored under the option.
+ *   2. No Dirichlet noise is mixed into any select of a search made under the option, whatever noise_scale is.
+ *   3. Candidates, chosen at the top of batch 0 (the root is expanded, nothing is pending): m0 = min(m, k); the m0
+ * children with the largest a_j = g_j + ln P_j, ties to the lower index.  R = max(1, ceil(log2 m0)) phases.
+ *   4. Halving, at the top of batch b = 0 .. NBt-1, before its first select (the earlier batches backed up, their
+ * virtual losses undone): the survivor set S is halved once for every r in 1..R-1 with floor(r * NBt / R) == b
+ * (several times at one b, b = 0 included, when NBt < R).  A halving keeps the ceil(|S| / 2) survivors with the largest
+ * key_j = a_j + sigma_j, ties to the lower index, where
+ *       sigma_j = ((c_visit + n_max) * c_scale) * qh_j,          n_max = max of n_j over ALL root children,
+ *       qh_j    = 0.5 * ((-w_j) / n_j) + 0.5 where n_j > 0, else vh,
+ *       vh      = (sum over n_j > 0 of P_j * qh_j) / (sum over n_j > 0 of P_j), 0.5 when no child is visited.
+ * DEVIATION 1: vh is the paper's v_mix without the root's own network value, which the reference's tree discards
+ * (mcts.py:18-27).
+ *   5. The root level of every select of that search descends into the survivor with the smallest n_j as that select
+ * sees it (virtual losses of the batch in flight included), ties to the lower index.  Below the root PUCT stays as it
+ * is, and so do virtual loss, dedup, expand and backup.  DEVIATION 2: this is root-only Gumbel; the paper's
+ * deterministic interior rule is not built.
+ *   6. The move: at the end of the search the survivor with the largest key_j, ties to the lower index.  Resignation
+ * judges the raw root as before.
+ *   7. The row of a recorded ply: with improved_rows = 1, pi_j = softmax_j(ln P_j + sigma_j) over ALL children (the
+ * maximum subtracted first); with improved_rows = 0 what the engine records otherwise from the visit counts (the
+ * reference's row, or AZX_ROWS_VISITS) -- a diagnostic and test mode, the row's maximum need not be the played move.
+ * value_mix works as always.  Row metric 2 is ln pi_chosen under the option, in either rows mode; metrics 0, 1 and
+ * 3..7 are unchanged.
+ *   8. Beside the playout cap: fast plies search under the option over their own NBt and record nothing.
+ *   9. It applies to azx_play, azx_play_device, azx_replay_fill and azx_play_steps (persistent k_play, per-move
+ * launches, the generic instantiation, the pipelined half-pools, a registered external evaluator) and to nothing else:
+ * azx_search and the phase API read "off", and azx_match_play / azx_tournament_play refuse an engine with the option
+ * set with AZX_EINVAL before touching any engine.
+ *   m == 0 is off; otherwise 2 <= m <= 64, c_visit finite in [0, 1e4], c_scale finite in (0, 100], improved_rows 0 or
+ * 1.  A bad call is AZX_EINVAL and leaves the setting in place.  It is AZX_EINVAL while forced playouts or early stop
+ * is set on the engine, and azx_set_forced_playouts / azx_set_early_stop refuse values other than off while this
+ * option is on: both are rules about PUCT visit leaders.  May be called between calls, for any evaluator; the call
+ * zeroes the statistics of azx_gumbel_stats.  With the option never set, or cleared, every call launches the same
+ * kernels and returns the same bytes as without these entry points.  azx_kernel_info reports gumbel=off or
+ * gumbel=<m>/<c_visit>/<c_scale>/<rows|norows>.  DESIGN 7.14 has what was measured; the option's effect on playing
+ * strength and training efficiency is NOT measured.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_gumbel). */
+int azx_set_gumbel(azx_engine *e, int m, float c_visit, float c_scale, int improved_rows);
+int azx_get_gumbel(azx_engine *e, int *m, float *c_visit, float *c_scale, int *improved_rows);
+/* out4 = {plies chosen under the option, halvings performed, root selects made under the option, rows recorded as the
+ * improved policy}, counted since the last azx_set_gumbel.  They live in an array of their own: azx_debug_counters keeps
+ * its 16 words. */
+int azx_gumbel_stats(azx_engine *e, int64_t out4[4]);
+/* g_j of rule 1 for (the engine's seed, the game's uid, the ply from the empty board, the child index), in double
+ * precision: the definition of the noise, as azx_playout_cap_is_full is of the cap's draw.  A host function.
+ * AZX_EINVAL for a negative ply or a child outside [0, AZX_CELL_STRIDE). */
+int azx_gumbel_variate(uint64_t seed, int64_t uid, int ply, int child, double *g);
+/* self-test (tests): the device's float32 g of n raw Philox words, by the function the tree kernels use. */
+int azx_selftest_gumbel(int device, int n, const uint32_t *words, float *g_out);
+/* candidates, survivors: [n_games][3] words each, bit c & 63 of word c >> 6 for child index c -- the m0 candidates
+ * chosen at the top of each slot's last searched ply and the survivors left at its end.  Blocking; meant for tests. */
+int azx_gumbel_state(azx_engine *e, uint64_t *candidates, uint64_t *survivors);
+
 /* float32 arithmetic self-test (tests): the tree kernels need IEEE-rounded sqrt and divide and
  * no FMA contraction (mcts.py:132-135).  sq=sqrtf(a), dv=a/(1+b), mul=(0.75f*a)*b+a. */
 int azx_selftest_arith(int device, int n, const float *a, const float *b, float *sq, float *dv,
