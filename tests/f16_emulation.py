@@ -7,6 +7,7 @@ fp32); the folded stem, conv and head-filter weights enter as f16(w); the activa
 enters the next conv and the head filters as f16(a); sums, bias and the residual (the unrounded block input) are not
 rounded -- float64 here, fp32 in the kernel; the one-hot stem input is exact; the heads behind the six planes are
 unchanged.  rounded=False leaves every f16 rounding out: the network itself."""
+import numpy as np
 import torch
 from torch.nn import functional as F
 
@@ -17,9 +18,31 @@ def _fold(state, pre):
     return scale, (b - m * scale).float().double()
 
 
-def forward(state, blocks, board, legal_moves, rounded=True):
-    """(value [B], moves_logprob [B, K]) as float64 numpy arrays; `state`: the HexNetwork state dict (numpy or torch)."""
-    r16 = (lambda t: t.float().half().double()) if rounded else (lambda t: t)
+def _lo_half(rem, bits):
+    """f16(rem) kept to `bits` explicit mantissa bits, rounded to nearest on the f16 pattern (half away from zero, a carry
+    into the exponent included) as lo_round_bits / split2_f16 do it in a build with AZX_LO_BITS = bits; 10 keeps all."""
+    assert 0 <= bits <= 10
+    pat = rem.float().half().contiguous().view(torch.int16).numpy().view(np.uint16).astype(np.uint32)
+    if bits < 10:
+        pat = (pat + (1 << (9 - bits))) & ((0xFFFF << (10 - bits)) & 0xFFFF)
+    return torch.from_numpy(pat.astype(np.uint16).view(np.int16)).view(torch.float16).double()
+
+
+def forward(state, blocks, board, legal_moves, rounded=True, lo_bits=None):
+    """(value [B], moves_logprob [B, K]) as float64 numpy arrays; `state`: the HexNetwork state dict (numpy or torch).
+
+    lo_bits = b (default None: the plain-f16 tower above) makes every rounded operand hi + lo_b instead of hi, with
+    hi = f16(x) and lo_b = f16(x - hi) kept to b mantissa bits: the definition of the default tower's hi + lo split
+    (k_tower_f16x3_s16; b = 10 is the shipped one, fewer bits are the AZX_LO_BITS diagnostic builds) in float64.  The
+    lo * lo product the kernel drops, 2^-22 of the result, stays in."""
+    if not rounded:
+        r16 = lambda t: t                                       # noqa: E731
+    elif lo_bits is None:
+        r16 = lambda t: t.float().half().double()               # noqa: E731
+    else:
+        def r16(t):
+            hi = t.float().half().double()
+            return hi + _lo_half(t - hi, lo_bits)
     g = lambda name: torch.as_tensor(state[name]).double()   # noqa: E731
     board, legal_moves = torch.as_tensor(board).long(), torch.as_tensor(legal_moves).long()
 

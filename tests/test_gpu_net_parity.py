@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from forward_accuracy_cases import expected_kernels
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -132,6 +134,7 @@ def test_wide_tower_forward(eng, orc, n, blocks, chans, count, use_oracle):
     boards, lm = _random_positions(orc, n, count, rng)
     E = eng.Engine(board_size=n, n_games=4, simulations=10, search_batch_size=10,
                    evaluator=eng.EVAL_RESNET, num_blocks=blocks, base_chans=chans)
+    assert expected_kernels(n, blocks, chans, os.environ) in E.kernel_info(), E.kernel_info()   # which tower this point hit
     E.set_weights(state)
     value, logprob = E.forward(boards, lm)
     legal = lm > 0
@@ -148,10 +151,12 @@ def test_wide_tower_forward(eng, orc, n, blocks, chans, count, use_oracle):
 @pytest.mark.parametrize("n,blocks,chans", [(n, 1 + n % 2, (16, 64, 128, 24, 32, 256, 48, 8, 96)[(n + k) % 9])
                                             for n in range(2, 14) for k in (0, 4)])
 def test_forward_every_board_size(eng, orc, n, blocks, chans):
-    """Every board size the engine accepts, with channel counts that land on each tower (the fused split-f16 one: 16 /
-    32 / 64; the wide per-layer one: 128 / 256; the exact-fp32 one: 8 / 24 / 48 / 96), nine positions (an odd count),
-    against the torch module.  (A sweep of all 200 combinations of 2..13 x {8 .. 256} x {1, 2} blocks ran clean; this is
-    a diagonal of it.)"""
+    """Every board size the engine accepts, with channel counts that land on each tower as azx_net_create dispatches
+    them (forward_accuracy_cases.expected_kernels, asserted per point): 64 channels on the fused split-f16 tower up to
+    11x11 and on the exact-fp32 MFMA tiling <64,6,1,2,2> on 12x12 / 13x13; 32 channels on the exact-fp32 MFMA tiling
+    <32,6,2,2,1>; 128 / 256 on the wide per-layer split-f16 pair; 8 / 16 / 24 / 48 / 96 on the exact-fp32 VALU pair.
+    Nine positions (an odd count), against the torch module.  (A sweep of all 200 combinations of 2..13 x {8 .. 256} x
+    {1, 2} blocks ran clean; this is a diagonal of it.)"""
     test_wide_tower_forward(eng, orc, n, blocks, chans, 9, False)
 
 

@@ -162,6 +162,45 @@ def test_mover_view_collate_is_the_search_side_flip():
         E.close()
 
 
+@pytest.mark.parametrize("mode", ["overflow", "wrap"])
+def test_record_put_wraps_and_overflows_like_the_row_put(mode):
+    """k_records_put's wrap ((write_idx + i) % cap) and overflow (skip = n - cap) paths, which no ring larger than its
+    rows reaches: the same harvested 7x7 rows enter engine A's ring as records (replay_put_records) and engine B's as
+    host rows (replay_put, whose wrap and overflow golden G7 pins) -- once as a single put into a ring five rows too
+    small, once as two puts of which the second wraps -- and the two rings hold the same state and collate the same
+    batches at every index."""
+    from azalea_amd import distributed as azd
+    A, B = make_engine(n=7, games=16, sims=20), make_engine(n=7, games=16, sims=20)
+    rows, _ = A.play_device(40)
+    assert rows >= 40
+    rec = torch.empty((rows, A.record_bytes), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    A.rows_pack(0, rows, rec.data_ptr())
+    turned = rec.flip(0).contiguous()                           # the second put: the same rows, last first
+    torch.cuda.synchronize()
+    puts = [rec] if mode == "overflow" else [rec, turned]
+    cap = rows - 5 if mode == "overflow" else rows + rows // 2
+    from azalea_amd.device_replay import DeviceReplayBuffer
+    bufs = [DeviceReplayBuffer(E, cap) for E in (A, B)]
+    for part in puts:
+        h = azd.unpack_rows(part.cpu().numpy(), 7)
+        A.replay_put_records(rows, part.data_ptr())
+        B.replay_put(h["board"], h["color"], h["nlegal"], h["moves_prob"], h["reward"])
+        assert A.replay_state() == B.replay_state()
+    want = dict(capacity=cap, size=cap, write_idx=(len(puts) * rows) % cap)
+    assert A.replay_state() == want and want["write_idx"] != 0
+    a, b = (host(buf.sample(np.arange(cap))) for buf in bufs)
+    for k in KEYS:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    # and the ring is what a sequential put leaves: slot (first + i) % cap holds row i of the last cap rows put
+    h = azd.unpack_rows(torch.cat(puts).cpu().numpy(), 7)
+    total = len(puts) * rows
+    slot = np.arange(total - cap, total) % cap
+    assert np.array_equal(a["board"].reshape(cap, 49)[slot], h["board"].reshape(total, 49)[total - cap:])
+    assert np.array_equal(a["reward"][slot], h["reward"][total - cap:])
+    A.close(); B.close()
+
+
 @pytest.mark.parametrize("n", [2, 3, 8, 12, 13])
 def test_record_exchange_round_trip_on_other_board_sizes(n):
     """The multi-GPU exchange unit (AZX_RECORD_BYTES, k_rows_pack -> k_records_put) on the smallest and largest boards:
