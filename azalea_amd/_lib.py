@@ -152,6 +152,12 @@ SYMBOLS = {
     "azx_openings_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p, _i32p, _i32p]),
     "azx_match_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
     "azx_tournament_set_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p]),
+    # weighted opening book of device self-play (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_selfplay_openings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p, C.POINTER(C.c_double)]),
+    "azx_selfplay_opening_word": (C.c_int, [C.c_uint64, C.c_int64, C.POINTER(C.c_uint32)]),
+    "azx_selfplay_openings_bounds": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "azx_selfplay_openings_slots": (C.c_int, [_vp, _i32p]),
+    "azx_selfplay_openings_stats": (C.c_int, [_vp, C.c_int64, _i64p]),
     # playout cap randomisation of throughput self-play (additions within revision 7; NOT the reference's behaviour)
     "azx_set_playout_cap": (C.c_int, [_vp, C.c_double, C.c_int]),
     "azx_playout_cap_is_full": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_double]),

@@ -26,6 +26,7 @@
 #include "playout_cap.h"
 #include "gumbel.h"
 #include "resign.h"
+#include "selfplay_openings.h"
 #include "tower_tiles.h"
 
 #ifndef AZX_SRC_SHA
@@ -152,6 +153,9 @@ struct azx_engine {
     // Gumbel root search with sequential halving (azx_set_gumbel): handed to the same launches, by the same scope
     int gm_m = 0, gm_rows = 0;
     float gm_c_visit = 0.0f, gm_c_scale = 0.0f;
+    // self-play opening book (azx_set_selfplay_openings): the device tables e->d.bk_* point at (the engine owns them;
+    // replaced as a whole, freed by azx_destroy).  Not scoped: e->d carries the book in every launch (azx_dev.h)
+    void *book_allocs[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
@@ -363,6 +367,7 @@ extern "C" void azx_destroy(azx_engine *e) {
     for (void *p : e->allocs) (void)hipFree(p);
     for (void *p : e->q_allocs) (void)hipFree(p);
     for (void *p : e->ring_allocs) (void)hipFree(p);
+    for (void *p : e->book_allocs) if (p) (void)hipFree(p);
     if (e->export_board) (void)hipFree(e->export_board);
     if (e->export_prob) (void)hipFree(e->export_prob);
     if (e->ext_info_host) (void)hipHostFree(e->ext_info_host);
@@ -549,6 +554,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " targets=" + targets_text(e) +
                        " forced=" + forced_text(e) +
                        " gumbel=" + gumbel_text(e) +
+                       " book=" + (d.bk_n > 0 ? std::to_string(d.bk_n) : std::string("off")) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -2454,6 +2460,95 @@ static int book_set(MatchBook *book, int board_size, int n_openings, int stride,
     return AZX_OK;
 }
 
+// ---- self-play opening book (include/azx.h; NOT the reference's behaviour) ------------------------------------
+extern "C" int azx_selfplay_opening_word(uint64_t seed, int64_t uid, uint32_t *word) {
+    if (!word) return fail(AZX_EINVAL, "null argument");
+    *word = azx_book_word(seed, uid);
+    return AZX_OK;
+}
+
+extern "C" int azx_selfplay_openings_bounds(int n_openings, const double *weights, uint64_t *ub) {
+    if (!ub) return fail(AZX_EINVAL, "null argument");
+    if (n_openings < 1 || n_openings > (1 << 20))
+        return fail(AZX_EINVAL, "selfplay openings: n_openings %d outside [1, %d]", n_openings, 1 << 20);
+    int bad = -1;
+    if (const char *why = azx_book_bounds(n_openings, weights, ub, &bad)) {
+        if (bad >= 0) return fail(AZX_EINVAL, "selfplay openings: weight %d (%g) %s", bad, weights[bad], why);
+        return fail(AZX_EINVAL, "selfplay openings: the weights' %s", why[0] == 'a' ? "values are all zero" : why);
+    }
+    return AZX_OK;
+}
+
+extern "C" int azx_set_selfplay_openings(azx_engine *e, int n_openings, int stride, const int16_t *moves,
+                                         const int32_t *lengths, const double *weights) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    TRY(openings_args(n_openings, stride, moves, lengths));
+    TRY(azx_openings_check(e->d.N, n_openings, stride, moves, lengths, nullptr, nullptr));
+    std::vector<uint64_t> ub((size_t)n_openings);
+    if (n_openings > 0) TRY(azx_selfplay_openings_bounds(n_openings, weights, ub.data()));
+    ENGINE_GUARD(e);
+    // no play call of the engine is running (they block): the old tables are free to go once the new ones stand
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    if (e->stream_b) HIPCHECK(hipStreamSynchronize(e->stream_b));
+    void *na[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (n_openings > 0) {
+        const size_t n = (size_t)n_openings;
+        const size_t bytes[4] = {std::max<size_t>(sizeof(int16_t) * n * (size_t)stride, 16), sizeof(int32_t) * n,
+                                 sizeof(uint64_t) * n, sizeof(unsigned long long) * n * BK_COUNT};
+        const void *src[4] = {moves, lengths, ub.data(), nullptr};
+        hipError_t err = hipSuccess;
+        for (int i = 0; i < 4 && err == hipSuccess; ++i) {
+            err = hipMalloc(&na[i], bytes[i]);
+            if (err != hipSuccess) break;
+            if (i == 0 && stride == 0) err = hipMemset(na[i], 0, bytes[i]);
+            else if (src[i]) err = hipMemcpy(na[i], src[i], i == 0 ? sizeof(int16_t) * n * (size_t)stride : bytes[i], hipMemcpyHostToDevice);
+            else err = hipMemset(na[i], 0, bytes[i]);
+        }
+        if (err != hipSuccess) {
+            for (void *p : na) if (p) (void)hipFree(p);
+            return fail(AZX_ENOMEM, "copying a book of %d openings to the device failed: %s", n_openings, hipGetErrorString(err));
+        }
+    }
+    for (int i = 0; i < 4; ++i) {
+        if (e->book_allocs[i]) (void)hipFree(e->book_allocs[i]);
+        e->book_allocs[i] = na[i];
+    }
+    DevEngine &d = e->d;
+    d.bk_n = n_openings;
+    d.bk_stride = n_openings > 0 ? stride : 0;
+    d.bk_moves = (const int16_t *)na[0];
+    d.bk_len = (const int32_t *)na[1];
+    d.bk_ub = (const uint64_t *)na[2];
+    d.bk_ctr = (unsigned long long *)na[3];
+    // the games that have not begun follow the new book (or, cleared, the empty board) from where they stand
+    azx_launch_book_seat(d, e->stream);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
+}
+
+extern "C" int azx_selfplay_openings_slots(azx_engine *e, int32_t *opening) {
+    if (!e || !opening) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    std::vector<GameHdr> hdr((size_t)e->d.G);
+    HIPCHECK(hipMemcpyAsync(hdr.data(), e->d.ghdr, hdr.size() * sizeof(GameHdr), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (size_t g = 0; g < hdr.size(); ++g) opening[g] = e->d.bk_n > 0 ? hdr[g].book : -1;
+    return AZX_OK;
+}
+
+extern "C" int azx_selfplay_openings_stats(azx_engine *e, int64_t cap, int64_t *out) {
+    if (!e || (cap > 0 && !out)) return fail(AZX_EINVAL, "null argument");
+    const int64_t n = e->d.bk_n;
+    if (cap < n) return fail(AZX_EINVAL, "selfplay openings: room for %lld openings, the book has %lld", (long long)cap, (long long)n);
+    if (n == 0) return 0;
+    ENGINE_GUARD(e);
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "tally width");
+    HIPCHECK(hipMemcpyAsync(out, e->d.bk_ctr, (size_t)n * BK_COUNT * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return (int)n;
+}
+
 // ---- matches between two engines on the device (match_kernels.hip) -------------------------------------------
 // evaluation.worker + play_game (evaluation.py:60-80, play_game.py:27-52) for a whole pool of games: slot g of
 // engine a and slot g of engine b hold the two agents' trees of one game.  Per ply the host enqueues
@@ -2660,6 +2755,10 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (a->gm_m != 0 || b->gm_m != 0)
         return fail(AZX_EINVAL, "engine %s has the Gumbel root search set: a match searches and draws every ply as the "
                                 "reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", a->gm_m != 0 ? "a" : "b");
+    if (a->d.bk_n > 0 || b->d.bk_n > 0)
+        return fail(AZX_EINVAL, "engine %s has a self-play opening book set: a match starts its games from its own book "
+                                "(azx_match_set_openings; clear the engine's with azx_set_selfplay_openings(e, 0, ...))",
+                    a->d.bk_n > 0 ? "a" : "b");
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -2943,6 +3042,11 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
         if (t->eng[k]->gm_m != 0)
             return fail(AZX_EINVAL, "engine %d has the Gumbel root search set: a tournament searches and draws every ply as "
                                     "the reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", k);
+    for (int k = 0; k < K; ++k)
+        if (t->eng[k]->d.bk_n > 0)
+            return fail(AZX_EINVAL, "engine %d has a self-play opening book set: a tournament starts its games from its own "
+                                    "book (azx_tournament_set_openings; clear the engine's with "
+                                    "azx_set_selfplay_openings(e, 0, ...))", k);
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

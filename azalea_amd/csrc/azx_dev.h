@@ -67,7 +67,10 @@ struct alignas(64) GameHdr {
                        // held (0: none yet); AZX_RS_SKIP: the game was in progress when azx_set_resign was called and
                        // counts in no resign statistic; AZX_RS_DONE: the game ended by resignation (a parked slot's
                        // harvest needs it)
-    int32_t pad[4];
+    int32_t book;      // self-play opening book (azx_set_selfplay_openings): the index of the opening this game was seated
+                       // on, in the book installed now; -1: the game did not come from it (no book, azx_reset with a
+                       // move table, a match's game, or a game that was in progress when the book was last set)
+    int32_t pad[3];
 };
 #define AZX_RS_CROSS 0xFFFF
 #define AZX_RS_SKIP 0x10000
@@ -181,7 +184,17 @@ struct DevEngine {
                                 // greedy ply), written by the launch that begins the ply's search; the top of batch 0
                                 // makes it a_j = g_j + ln P_j and puts ln P_j in the second row
     unsigned long long *gm_ctr;       // [G][GM_COUNT] per game (no atomics), azx_gumbel_stats' array; the host sums
+    // self-play opening book (azx_set_selfplay_openings; NOT the reference's behaviour).  Unlike the options above it is
+    // in every launch: it acts wherever the engine itself starts a game (k_reset without a move table, advance_body's
+    // restart, k_book_seat) and nowhere else; bk_n == 0 is "off" (selfplay_openings.h has the draw)
+    int32_t bk_n, bk_stride;
+    const int16_t *bk_moves;    // [bk_n][bk_stride] tile + 1 in play order, colour 1 at the even plies
+    const int32_t *bk_len;      // [bk_n]
+    const uint64_t *bk_ub;      // [bk_n] game uid starts from the least o with azx_book_word(seed, uid) < bk_ub[o]
+    unsigned long long *bk_ctr; // [bk_n][BK_COUNT] per OPENING (several slots share one: atomics), azx_selfplay_openings_stats' array
 };
+// games started, games finished, finished games won by colour 1, plies of finished games counted from the empty board
+enum { BK_STARTED = 0, BK_FINISHED, BK_WON1, BK_PLIES, BK_COUNT = 4 };
 // plies chosen under the option, halvings performed, root selects made under the option, rows recorded as the improved policy
 enum { GM_PLIES = 0, GM_HALVINGS, GM_SELECTS, GM_ROWS, GM_COUNT = 4 };
 enum { GM_CAND = 0, GM_SURV = 4, GM_STATE_WORDS = 8 };

@@ -77,6 +77,7 @@ __device__ __forceinline__ void match_restart(const DevEngine &E, int g, int64_t
         gh->ply0 = ply;
         gh->parked = 0;
         gh->rs_state = 0;
+        gh->book = -1;             // (a match's book is the match's own: azx_match_set_openings)
         if (uid >= 0) gh->uid = uid;
         if (opened) E.thdr[g].arena = 0;
     }

@@ -19,6 +19,8 @@ bool azx_launch_play(const DevEngine &E, int num_batches, int steps, hipStream_t
 void azx_launch_reset(const DevEngine &E, const int32_t *slots, int n_slots, const int32_t *moves,
                       const int32_t *n_moves, int stride, int assign_uid, hipStream_t st);
 void azx_launch_advance(const DevEngine &E, const int32_t *move_ids, int play_mode, hipStream_t st);
+// azx_set_selfplay_openings: seat every slot whose game has not begun under the book now in E (k_book_seat)
+void azx_launch_book_seat(const DevEngine &E, hipStream_t st);
 // resignation (azx_set_resign): the statistic of every slot's current root; mark the games in progress as uncounted
 void azx_launch_resign_value(const DevEngine &E, float *out, hipStream_t st);
 void azx_launch_resign_mark(const DevEngine &E, hipStream_t st);

@@ -23,6 +23,7 @@
 #include "playout_cap.h"
 #include "gumbel.h"
 #include "resign.h"
+#include "selfplay_openings.h"
 
 __constant__ uint64_t c_geo[AZX_GEO_CELLS * 4];
 __constant__ float c_sqrt[AZX_SQRT_TAB];
@@ -1700,6 +1701,49 @@ __device__ __forceinline__ void tree_reset(const DevEngine &E, int g, TreeHdr *t
     }
 }
 
+// The board and the ply of a game the engine itself starts (k_reset without a move table, advance_body's restart,
+// k_book_seat), in the state k_reset leaves for the move prefix: the empty board, or under a self-play opening book
+// (azx_set_selfplay_openings; NOT the reference's behaviour) the position after the opening game `uid` draws
+// (selfplay_openings.h).  Stores the cells and the header's colour, winner, ply, ply0 and book index, counts the game
+// as started, and returns the legal moves of the position: the caller resets the tree over them.  Everything is
+// wave-uniform: the draw's binary search is scalar loads (at most 20, dependent), the moves are scalar loads, and the
+// host has checked the book (azx_openings_check: every move legal, no opening decides the game).
+// Kept out of line: in k_play the restart sits at the end of a loop whose registers are all spoken for (k_play<2> is on
+// its 128-VGPR bound), and a second HexWave with its game steps inlined there is live-range pressure the loop pays for.
+// The engine as game_seat wants it, for a kernel whose FIRST argument is its DevEngine: a pointer into the
+// kernel-argument segment.  (The address of the by-value argument itself makes the compiler copy the whole struct to
+// the frame first: 560 bytes of scratch stores at the entry of every launch.)
+__device__ __forceinline__ const DevEngine *kernarg_engine() {
+    return (const DevEngine *)(const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+template <int SLOTS>
+__device__ __noinline__ int game_seat(const DevEngine *Ep, int g, int64_t uid, int lane) {
+    const DevEngine &E = *Ep;
+    HexWave<SLOTS> z;
+    z.clear();
+    int ply = 0, o = -1;
+    const int n = E.bk_n;
+    if (n > 0) {
+        o = __builtin_amdgcn_readfirstlane(azx_book_index(azx_book_word(E.seed, uid), E.bk_ub, n));
+        const int16_t *mv = E.bk_moves + (size_t)o * E.bk_stride;
+        ply = __builtin_amdgcn_readfirstlane(E.bk_len[o]);
+        z.geom(E.N, lane);
+        for (int p = 0; p < ply; ++p) z.step(__builtin_amdgcn_readfirstlane(mv[p] - 1), E.N, lane);
+        if (lane == 0) atomicAdd(E.bk_ctr + (size_t)o * BK_COUNT + BK_STARTED, 1ull);
+    }
+    z.store(E.cells + (size_t)g * SLOTS * 64, lane);
+    GameHdr *gh = E.ghdr + g;
+    if (lane == 0) {
+        gh->color = z.color;
+        gh->winner = z.winner;
+        gh->ply = ply;
+        gh->ply0 = ply;
+        gh->book = o;
+    }
+    return E.ncells - ply;      // an opening's moves fill one empty cell each and none decides the game
+}
+
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots, int n_slots,
                                               const int32_t *moves, const int32_t *n_moves,
@@ -1708,6 +1752,26 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
     const int idx = blockIdx.x;
     if (idx >= n_slots) return;
     const int g = slots ? slots[idx] : idx;
+    GameHdr *gh = E.ghdr + g;
+    TreeHdr *th = E.thdr + g;
+    if (!moves && assign_uid && E.bk_n > 0) {
+        // a game the engine starts itself follows the self-play opening book (azx_set_selfplay_openings)
+        const int64_t uid = game_uid(E, g, gh->gen);
+        const int k = game_seat<SLOTS>(kernarg_engine(), g, uid, lane);
+        if (lane == 0) {
+            gh->active = 1;
+            gh->move_id = -1;
+            gh->n_rows = 0;
+            gh->parked = 0;
+            gh->rs_state = 0;
+            gh->uid = uid;
+            gh->gen += 1;
+            th->arena = 0;
+        }
+        __builtin_amdgcn_s_waitcnt(0);
+        tree_reset<SLOTS>(E, g, th, k, lane);
+        return;
+    }
     HexWave<SLOTS> h;
     h.clear();
     h.geom(E.N, lane);
@@ -1722,8 +1786,6 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
     }
     h.store(E.cells + (size_t)g * SLOTS * 64, lane);
     const Masks<SLOTS> mk = make_masks<SLOTS>(h, lane, E.ncells);
-    GameHdr *gh = E.ghdr + g;
-    TreeHdr *th = E.thdr + g;
     if (lane == 0) {
         gh->color = h.color;
         gh->winner = h.winner;
@@ -1734,11 +1796,36 @@ __global__ __launch_bounds__(64) void k_reset(DevEngine E, const int32_t *slots,
         gh->parked = 0;
         gh->ply0 = ply;
         gh->rs_state = 0;
+        gh->book = -1;
         if (assign_uid) { gh->uid = game_uid(E, g, gh->gen); gh->gen += 1; }
         th->arena = 0;
     }
     __builtin_amdgcn_s_waitcnt(0);
     tree_reset<SLOTS>(E, g, th, mk.k, lane);
+}
+
+// azx_set_selfplay_openings: every slot whose game has not begun -- no ply played, no row recorded, a bare unevaluated
+// root with no search under way, not parked -- is seated again in place under the book now installed (or on the empty
+// board when the book was cleared), with the uid it has.  A game in progress finishes as it is and leaves the book's
+// tallies: its index belonged to the table that was replaced.
+template <int SLOTS>
+__global__ __launch_bounds__(64) void k_book_seat(DevEngine E) {
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x;
+    GameHdr *gh = E.ghdr + g;
+    TreeHdr *th = E.thdr + g;
+    const Node *arena = E.arena[th->arena] + (size_t)g * E.cap;
+    const bool fresh = gh->ply == gh->ply0 && gh->n_rows == 0 && gh->parked == 0 && gh->winner == 0 &&
+                       th->status == 0 && th->num_nodes == 1 && th->root_id == 0 && th->pending == 0 &&
+                       th->batches_left == 0 && arena[0].link == AZX_LINK_UNEVAL;
+    if (!fresh) {
+        if (lane == 0) gh->book = -1;
+        return;
+    }
+    const int k = game_seat<SLOTS>(kernarg_engine(), g, gh->uid, lane);
+    if (lane == 0) { gh->move_id = -1; gh->rs_state = 0; }
+    __builtin_amdgcn_s_waitcnt(0);
+    tree_reset<SLOTS>(E, g, th, k, lane);
 }
 
 // ============================================================================================
@@ -1950,31 +2037,36 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
                     E.counters[(size_t)g * CTR_COUNT + CTR_CAP_EMPTY] += 1ull;   // no ply of the game was a full search
                 }
                 E.stat_sums[(size_t)g * 8 + 4] += (double)ply;        // game length from the empty board
+                // self-play opening book: the opening's tallies (several slots share an opening: atomics)
+                const int bo = gh->book;
+                if (bo >= 0 && bo < E.bk_n) {
+                    unsigned long long *bc = E.bk_ctr + (size_t)bo * BK_COUNT;
+                    atomicAdd(bc + BK_FINISHED, 1ull);
+                    if (h.winner == 1) atomicAdd(bc + BK_WON1, 1ull);
+                    atomicAdd(bc + BK_PLIES, (unsigned long long)ply);
+                }
             }
         }
     } else {
         if (lane == 0) E.counters[(size_t)g * CTR_COUNT + CTR_ERRORS] += 1ull;   // parallel_player.py:73-76
     }
     if (restart) {
-        HexWave<SLOTS> z;
-        z.clear();
-        z.store(E.cells + (size_t)g * SLOTS * 64, lane);
+        // (the header still holds the finished game: its winner, its length, its resign marks)
+        if (lane == 0 && finished && E.resign_mode != AZX_RESIGN_OFF) resign_count(E, g, gh);
+        // the next game of the slot: the empty board, or its opening under a self-play book (game_seat stores the
+        // cells and the header's colour, winner, ply, ply0 and book index)
+        const int64_t uid = game_uid(E, g, gh->gen);
+        const int k = game_seat<SLOTS>(&E, g, uid, lane);
         if (lane == 0) {
-            // (the header still holds the finished game: its winner, its length, its resign marks)
-            if (finished && E.resign_mode != AZX_RESIGN_OFF) resign_count(E, g, gh);
-            gh->color = 1;
-            gh->winner = 0;
-            gh->ply = 0;
             gh->move_id = -1;
             gh->n_rows = 0;
-            gh->ply0 = 0;
             gh->rs_state = 0;
             if (parked) { gh->parked = 0; gh->active = 1; }
-            gh->uid = game_uid(E, g, gh->gen);
+            gh->uid = uid;
             gh->gen += 1;
         }
         __builtin_amdgcn_s_waitcnt(0);
-        tree_reset<SLOTS>(E, g, th, E.ncells, lane);
+        tree_reset<SLOTS>(E, g, th, k, lane);
     }
 }
 
@@ -1983,7 +2075,8 @@ __device__ __forceinline__ void advance_body(const DevEngine &E, int g, const in
 // ============================================================================================
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_advance(DevEngine E, const int32_t *move_ids, int play_mode) {
-    advance_body<SLOTS>(E, blockIdx.x, move_ids, play_mode);
+    (void)E;    // read in place, so that the restart's game_seat is handed a pointer and not a copy in the frame
+    advance_body<SLOTS>(*kernarg_engine(), blockIdx.x, move_ids, play_mode);
 }
 
 template <int SLOTS>
@@ -2622,6 +2715,12 @@ bool azx_launch_play(const DevEngine &E, int num_batches, int steps, hipStream_t
 void azx_launch_reset(const DevEngine &E, const int32_t *slots, int n_slots, const int32_t *moves,
                       const int32_t *n_moves, int stride, int assign_uid, hipStream_t st) {
 #define CALL(S) hipLaunchKernelGGL((k_reset<S>), dim3(n_slots), dim3(64), 0, st, E, slots, n_slots, moves, n_moves, stride, assign_uid)
+    DISPATCH_SLOTS(E.slots, CALL);
+#undef CALL
+}
+
+void azx_launch_book_seat(const DevEngine &E, hipStream_t st) {
+#define CALL(S) hipLaunchKernelGGL((k_book_seat<S>), dim3(E.G), dim3(64), 0, st, E)
     DISPATCH_SLOTS(E.slots, CALL);
 #undef CALL
 }

@@ -560,6 +560,50 @@ class Engine:
         check(self.L.azx_playout_cap_stats(self.h, _p(out, C.c_int64)))
         return dict(full_plies=int(out[0]), fast_plies=int(out[1]), empty_games=int(out[2]))
 
+    # ---- weighted opening book of self-play (azx_set_selfplay_openings; NOT the reference's behaviour) ------------
+    def set_selfplay_openings(self, openings, weights=None):
+        """azx_set_selfplay_openings: every game this engine starts from now on -- a slot's restart inside play /
+        play_device / replay_fill / play_steps, reset() without moves -- begins from the opening of `openings` (a list
+        of move lists, tile + 1 in play order, colour 1 first; [] is the empty board) that its uid draws under
+        `weights` (None: uniform): selfplay_opening_index(seed, uid, selfplay_openings_bounds(weights)).  Slots whose
+        game has not begun are seated again at once, keeping their uid; games in progress finish as they are.
+        reset(moves=...) seats what it is given for that one game.  An empty list clears the book.  ValueError, with the
+        library's message, for a book openings_check refuses or weights that are negative, non-finite or all zero; the
+        book before stays then.  Match / Tournament refuse an engine with a self-play book."""
+        n, stride, mv, ln = _book_arrays(openings)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+            if w.size != n:
+                raise ValueError("selfplay openings: %d weights for %d openings" % (w.size, n))
+        _book_error(self.L.azx_set_selfplay_openings(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32),
+                                                     _p(w, C.c_double) if n else None))
+        self._selfplay_book = n
+
+    def clear_selfplay_openings(self):
+        """Self-play as before set_selfplay_openings: the same kernels, the same bytes."""
+        check(self.L.azx_set_selfplay_openings(self.h, 0, 0, None, None, None))
+        self._selfplay_book = 0
+
+    def selfplay_openings_slots(self):
+        """azx_selfplay_openings_slots: int32[n_games], the book index of each slot's game in progress, -1 where it did
+        not come from the installed book."""
+        out = np.zeros(self.G, np.int32)
+        check(self.L.azx_selfplay_openings_slots(self.h, _p(out, C.c_int32)))
+        return out
+
+    def selfplay_openings_stats(self):
+        """azx_selfplay_openings_stats since the book was last set: dict(started, finished, wins_color1, plies) of
+        int64[n_openings] arrays -- plies are those of the finished games, counted from the empty board."""
+        n = int(getattr(self, "_selfplay_book", 0))
+        out = np.zeros((max(n, 1), 4), np.int64)
+        rc = self.L.azx_selfplay_openings_stats(self.h, n, _p(out, C.c_int64))
+        if rc < 0:
+            check(rc)
+        out = out[:n]
+        return dict(started=out[:, 0].copy(), finished=out[:, 1].copy(), wins_color1=out[:, 2].copy(),
+                    plies=out[:, 3].copy())
+
     # ---- resignation with no-resign calibration games (azx_set_resign; NOT the reference's behaviour) ------------
     def set_resign(self, threshold, min_ply=0, keep_prob=0.1):
         """azx_set_resign: in the following play / play_device / replay_fill / play_steps calls the mover of a game
@@ -1051,6 +1095,38 @@ def playout_cap_is_full(seed, uid, ply, full_prob):
     if rc < 0:
         raise ValueError(L.azx_last_error().decode(errors="replace"))
     return bool(rc)
+
+
+def selfplay_opening_word(seed, uid):
+    """azx_selfplay_opening_word: the 32-bit word game `uid` of an engine created with `seed` draws its opening with
+    -- the function the kernels use, on the host (no device call)."""
+    out = C.c_uint32(0)
+    check(_lib.lib().azx_selfplay_opening_word(int(seed) & 0xFFFFFFFFFFFFFFFF, int(uid), C.byref(out)))
+    return int(out.value)
+
+
+def selfplay_openings_bounds(weights_or_n):
+    """azx_selfplay_openings_bounds: uint64[n], the upper bounds of the openings' shares of the 2^32 words -- of `n`
+    equally weighted openings (an int) or of the given weights.  ValueError, with the library's message, for weights
+    that are negative, non-finite or all zero.  Host only."""
+    if isinstance(weights_or_n, (int, np.integer)):
+        n, w = int(weights_or_n), None
+    else:
+        w = np.ascontiguousarray(weights_or_n, np.float64).reshape(-1)
+        n = int(w.size)
+    ub = np.zeros(max(n, 1), np.uint64)
+    _book_error(_lib.lib().azx_selfplay_openings_bounds(n, _p(w, C.c_double), _p(ub, C.c_uint64)))
+    return ub[:n]
+
+
+def selfplay_opening_index(seed, uids, bounds):
+    """The opening of each game in `uids` (an int or an array) under `bounds` (selfplay_openings_bounds): the least o
+    with selfplay_opening_word(seed, uid) < bounds[o].  Host only."""
+    ub = np.asarray(bounds, np.uint64)
+    flat = np.atleast_1d(np.asarray(uids, np.int64))
+    words = np.array([selfplay_opening_word(seed, int(u)) for u in flat.ravel()], np.uint64)
+    idx = np.searchsorted(ub, words, side="right").astype(np.int64).reshape(flat.shape)
+    return int(idx[0]) if np.ndim(uids) == 0 else idx
 
 
 def gumbel_variate(seed, uid, ply, child):

@@ -77,7 +77,7 @@ class Player:
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
                  openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None,
-                 forced_playouts=None, gumbel=None):
+                 forced_playouts=None, gumbel=None, selfplay_openings=None, selfplay_opening_weights=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -154,7 +154,17 @@ class Player:
         engine is made again.  A ValueError -- here, before any engine is made -- with device_match=True (a match
         searches and draws as the reference does), when the games would run through the host loop, together with
         forced_playouts or early_stop (rules about PUCT visit leaders), or for anything normalize_gumbel refuses.  Its
-        effect on playing strength and training efficiency is NOT measured."""
+        effect on playing strength and training efficiency is NOT measured.
+        `selfplay_openings` (NOT the reference's behaviour, whose games all start from the empty board; off by default):
+        a weighted opening book for SELF-PLAY -- a list of move lists, or any form normalize_selfplay_openings takes,
+        with `selfplay_opening_weights` (None: uniform) -- sets Engine.set_selfplay_openings (include/azx.h has the
+        definition) on the self-play engine this Player builds, device self-play or external_batch, right after the
+        engine is created and before any play: every game the engine starts begins from the opening its uid draws, on
+        the device.  It is applied again whenever the engine is made again.  (`openings` keeps its meaning: the book of
+        a device match.)  A ValueError -- here, before any engine is made -- with device_match=True (a match has its
+        own book: use openings=), with two agents, when the games would run through the host loop, or for anything
+        normalize_selfplay_openings or the rules refuse.  opening_stats() has the per-opening tallies.  Its effect on
+        playing strength and training efficiency is NOT measured."""
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -185,6 +195,7 @@ class Player:
         self.train_targets = self._check_train_targets(train_targets)
         self.forced_playouts = self._check_forced_playouts(forced_playouts)
         self.gumbel = self._check_gumbel(gumbel)
+        self.selfplay_openings = self._check_selfplay_openings(selfplay_openings, selfplay_opening_weights)
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -416,6 +427,40 @@ class Player:
                              "selects by PUCT and draws from the visit counts")
         return gumbel
 
+    def _check_selfplay_openings(self, openings, weights):
+        """`selfplay_openings` as a (book, weights or None) pair, or None for off; a ValueError naming what does not
+        hold."""
+        if openings is None:
+            if weights is not None:
+                raise ValueError("selfplay_opening_weights given without selfplay_openings")
+            return None
+        if self.device_match:
+            raise ValueError("selfplay_openings is a self-play option: a device match starts its games from its own "
+                             "book (use openings=; engine.Match refuses an engine with a self-play book)")
+        if len(self.agents) != 1:
+            raise ValueError("selfplay_openings is a self-play option: it needs a single agent, got %d (two agents play "
+                             "through the host loop or, with device_match=True, a device match)" % len(self.agents))
+        pol = self._external_policy() if self.external_batch else self._device_policy()
+        if pol is None:
+            raise ValueError("selfplay_openings needs the games to run in a device engine (a single agent whose Policy "
+                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
+                             "which starts every game from the empty board")
+        n = self.agents[0].game.board_size
+        book, w = normalize_selfplay_openings(openings, n)
+        if weights is not None:
+            if w is not None:
+                raise ValueError("selfplay_openings: weights given twice (in the book's dict and as selfplay_opening_weights)")
+            book, w = normalize_selfplay_openings({"book": book, "weights": weights}, n)
+        _eng.openings_check(n, book)
+        return book, w
+
+    def opening_stats(self):
+        """Engine.selfplay_openings_stats() of the self-play engine, or None while there is none or selfplay_openings
+        is not set."""
+        if self.selfplay_openings is None or self._engine is None:
+            return None
+        return self._engine.selfplay_openings_stats()
+
     def gumbel_stats(self):
         """Engine.gumbel_stats() of the self-play engine, or None while there is none or gumbel is not set."""
         if self.gumbel is None or self._engine is None:
@@ -577,6 +622,8 @@ class Player:
                 num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                 flags=self._engine_flags | tower_flags(pol),
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
+            if self.selfplay_openings is not None:      # before any play: generation 0 follows the book too
+                self._engine.set_selfplay_openings(*self.selfplay_openings)
             if self.playout_cap is not None:
                 self._engine.set_playout_cap(*self.playout_cap)
             if self.resign is not None:
@@ -735,6 +782,76 @@ def normalize_playout_cap(cap):
     if fast < 1:
         raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
     return full_prob, fast
+
+
+def normalize_selfplay_openings(spec, board_size=None):
+    """(book, weights) of a self-play opening book -- book a list of move lists (tile + 1 in play order), weights a list
+    of floats or None for uniform -- or None for None.  Accepted: a list of move lists; {"book": [...]} with an optional
+    "weights": [...]; {"all": 1 | 2} for engine.all_openings(board_size, plies) (needs `board_size`); and in a dict an
+    optional "empty_share": s in [0, 1], which puts the empty opening first with weight s and gives the others 1 - s in
+    equal parts (not together with "weights").  A ValueError for anything else: unknown keys, both or neither of "book"
+    and "all", an empty book, moves that are not whole numbers, weights of another length, or negative, non-finite or
+    all zero.  The rules themselves (moves on the board, no tile twice, undecided) are engine.openings_check's."""
+    if spec is None:
+        return None
+    what = "selfplay_openings"
+    weights, share = None, None
+    if isinstance(spec, dict):
+        extra = set(spec) - {"book", "weights", "all", "empty_share"}
+        if extra:
+            raise ValueError("%s as a dict takes the keys 'book', 'weights', 'all' and 'empty_share', got %r"
+                             % (what, sorted(map(str, spec))))
+        if ("book" in spec) == ("all" in spec):
+            raise ValueError("%s as a dict needs exactly one of 'book' and 'all'" % what)
+        if "all" in spec:
+            plies = spec["all"]
+            if isinstance(plies, bool) or plies not in (1, 2):
+                raise ValueError("%s: 'all' must be 1 or 2 (plies), got %r" % (what, plies))
+            if board_size is None:
+                raise ValueError("%s: 'all' needs the board size" % what)
+            book = _eng.all_openings(int(board_size), int(plies))
+        else:
+            book = spec["book"]
+        weights, share = spec.get("weights"), spec.get("empty_share")
+    else:
+        book = spec
+    try:
+        if isinstance(book, (str, bytes, dict)):
+            raise TypeError
+        book = [list(o) for o in book]
+        for o in book:
+            for m in o:
+                if isinstance(m, bool) or int(m) != m:
+                    raise ValueError
+        book = [[int(m) for m in o] for o in book]
+    except (TypeError, ValueError):
+        raise ValueError("%s: the book must be a list of move lists (whole numbers, tile + 1 in play order), got %r"
+                         % (what, spec)) from None
+    if not book:
+        raise ValueError("%s: the book is empty (leave the option out to play from the empty board)" % what)
+    if share is not None:
+        if weights is not None:
+            raise ValueError("%s: 'empty_share' and 'weights' cannot be given together" % what)
+        if isinstance(share, bool) or not isinstance(share, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(share) <= 1.0:
+            raise ValueError("%s: empty_share must be a number in [0, 1], got %r" % (what, share))
+        share = float(share)
+        weights = [share] + [(1.0 - share) / len(book)] * len(book)
+        book = [[]] + book
+    if weights is not None:
+        try:
+            if isinstance(weights, (str, bytes, dict)):
+                raise TypeError
+            weights = [float(w) for w in weights]
+        except (TypeError, ValueError):
+            raise ValueError("%s: weights must be a list of numbers, got %r" % (what, weights)) from None
+        if len(weights) != len(book):
+            raise ValueError("%s: %d weights for %d openings" % (what, len(weights), len(book)))
+        if any(not np.isfinite(w) or w < 0.0 for w in weights):
+            raise ValueError("%s: weights must be finite and >= 0, got %r" % (what, weights))
+        if not sum(weights) > 0.0:
+            raise ValueError("%s: the weights are all zero" % what)
+    return book, weights
 
 
 def normalize_train_targets(train_targets):

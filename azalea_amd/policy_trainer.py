@@ -387,8 +387,23 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     (Player(gumbel=...)); the random-mover player that fills the first buffer does NOT get it.  One log line says
     whether it is on.  A ValueError, before anything is built, for anything normalize_gumbel refuses and together with
     config["forced_playouts"] or config["early_stop"]; Player refuses it where the games would run through the host
-    loop.  Its effect on playing strength and on training efficiency is NOT measured."""
-    from .parallel_player import normalize_early_stop, normalize_train_targets, normalize_forced_playouts, normalize_gumbel
+    loop.  Its effect on playing strength and on training efficiency is NOT measured.
+
+    config["selfplay_openings"] = a list of move lists, {"book": [...], "weights": [...]}, or {"all": 1 | 2} for every
+    opening of that many plies, each optionally with "empty_share": s (default absent; NOT the reference's behaviour,
+    and outside every parity claim): every self-play game starts from the opening its uid draws from this weighted
+    book, on the device (Engine.set_selfplay_openings, include/azx.h has the definition).  It goes to the one self-play
+    Player built here (Player(selfplay_openings=...)), so the lock-step ranks and the actors pass it to their own
+    engines: the draw is keyed on the global uid, so N ranks play the one-rank set of games.  The random-mover player
+    that fills the first buffer does NOT get it.  One log line says whether it is on.  A ValueError, before anything is
+    built, for anything normalize_selfplay_openings or the rules refuse; Player refuses it where the games would run
+    through the host loop.  Its effect on playing strength and on training efficiency is NOT measured."""
+    from .parallel_player import (normalize_early_stop, normalize_train_targets, normalize_forced_playouts, normalize_gumbel,
+                                  normalize_selfplay_openings)
+    try:
+        selfplay_openings = normalize_selfplay_openings(config.get("selfplay_openings"), config.get("board_size"))
+    except ValueError as exc:
+        raise ValueError("config['selfplay_openings']: %s" % exc) from None
     try:
         gumbel = normalize_gumbel(config.get("gumbel"))
     except ValueError as exc:
@@ -458,7 +473,15 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
                     external_batch=bool(config.get("selfplay_external_batch", False)),
                     random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
                     resign=resign, early_stop=early_stop, train_targets=train_targets,
-                    forced_playouts=forced_playouts, gumbel=gumbel)
+                    forced_playouts=forced_playouts, gumbel=gumbel,
+                    selfplay_openings=None if selfplay_openings is None else selfplay_openings[0],
+                    selfplay_opening_weights=None if selfplay_openings is None else selfplay_openings[1])
+    if leader:
+        logging.info("self-play opening book (config['selfplay_openings']): %s",
+                     "off" if selfplay_openings is None else
+                     "on -- NOT the reference's behaviour: every game starts from one of %d openings, %s, drawn on the "
+                     "device from its uid" % (len(selfplay_openings[0]),
+                                              "uniform" if selfplay_openings[1] is None else "weighted"))
     if leader:
         logging.info("Gumbel root search (config['gumbel']): %s",
                      "off" if gumbel is None else

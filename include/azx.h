@@ -969,6 +969,65 @@ int azx_match_set_openings(azx_match *m, int n_openings, int stride, const int16
 int azx_tournament_set_openings(azx_tournament *t, int n_openings, int stride, const int16_t *moves,
                                 const int32_t *lengths);
 
+/* ---- a weighted opening book for device self-play --------------------------------------------------------------
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_selfplay_openings).  NOT the reference's behaviour (its games start from game.reset()):
+ * opt-in, off by default, outside every parity claim.  This block is the normative text.
+ *
+ * Every game the engine itself starts begins from an opening drawn from the book ON THE DEVICE, a pure function of
+ * (cfg.seed, the game's uid):
+ *   the word    azx_selfplay_opening_word(seed, uid): 32 bits from the game's key (the two key words of seed + uid, as
+ *               the other per-game draws have them) on a stream of its own -- both key words are salted with constants
+ *               used nowhere else, so the word shares no intermediate with the Dirichlet, reflection, move-draw, cap,
+ *               resign-exemption or Gumbel words.  Nothing else enters: not the slot, n_games, the half-pool, the
+ *               launch or the ply.
+ *   the bounds  for a book of n openings with weights W[o] >= 0 (NULL: all equal), cum the float64 running sum taken
+ *               left to right: ub[o] = (uint64) floor(ldexp(cum[o] / cum[n-1], 32)), and ub[n-1] is forced to 2^32.
+ *               The host computes the table once (azx_selfplay_openings_bounds is that function).
+ *   the draw    game u starts from the least o with word < ub[o].  A zero-weight opening is never drawn, one in first
+ *               place included.  All weights zero, a negative or a non-finite weight: AZX_EINVAL.
+ * azx_set_selfplay_openings(e, n_openings, stride, moves, lengths, weights)
+ *     The book format and its checks are azx_openings_check's for the engine's board size, with the same messages;
+ *     then the weights.  Book, bounds and tallies are copied to device memory the engine owns until they are replaced
+ *     or the engine destroyed.  n_openings == 0 clears the book.  A failing call leaves the previous book in place and
+ *     playing.  A successful one zeroes the statistics below.  May be called between calls, for any evaluator.
+ * Which games follow the book: the restart of a slot whose game finished or was dropped (in azx_play, azx_play_device,
+ * azx_replay_fill and azx_play_steps: persistent k_play, per-move launches, the pipelined half-pools, a registered
+ * external evaluator, and a parked slot that rejoins), and azx_reset called WITHOUT a move table.  At the moment the
+ * book is set (or cleared) every slot whose game has not begun -- no ply played, no row recorded, a bare unevaluated
+ * root with no search under way, not parked -- is seated again in place, KEEPING its uid: generation 0 follows the book
+ * too, and a fixed seed plays the same set of games whatever n_games and the sharding (game_index_stride / _offset)
+ * are.  Games in progress finish as they are; they count in no tally.  azx_reset WITH a move table seats what it is
+ * given (book index -1) for that one game: between azx_reset with a table and azx_set_selfplay_openings THE LAST CALL
+ * WINS for a slot whose game has not begun; either way the slot's next game follows the book.
+ * A game seated on an opening of length L is in the state azx_reset leaves for that prefix: stones placed,
+ * ply = ply0 = L, colour and winner as the moves leave them, the tree fresh over cells - L moves, no resign mark.
+ * Everything keyed on the ply counts from the empty board: the temperature gate, the playout-cap word, resign's min_ply,
+ * the Gumbel variates, the reflection bits, the rows' colour and reward sign.  Rows cover the searched plies only
+ * (length - L of a game played in full); azx_play_stats.sum_game_length and the per-opening plies count from the empty
+ * board; azx_play_stats.plies counts the engine's moves only.
+ * azx_selfplay_openings_slots(e, opening[n_games])
+ *     per slot the book index of the game in progress, or -1 if it did not come from the installed book (no book,
+ *     azx_reset with a table, or in progress when the book was last set).  The index is kept with the game when it is
+ *     seated, not recomputed.
+ * azx_selfplay_openings_stats(e, cap, out[cap][4])
+ *     per opening {games started, games finished, finished games won by colour 1, plies of finished games counted from
+ *     the empty board}, counted on the device at seating and at harvest since the book was last set.  A game dropped
+ *     for SearchTreeFull counts as started only; a resigned game counts with the winner the resignation leaves.
+ *     Returns the number of openings written (0 with no book), or AZX_EINVAL when cap is smaller than the book.
+ * azx_selfplay_opening_word / azx_selfplay_openings_bounds are host only (no device call); bounds takes n in
+ * [1, 1 << 20] and weights or NULL.
+ * With the book never set, or cleared, every call enqueues the same kernels and returns the same bytes as before these
+ * entry points existed.  azx_kernel_info reports book=off or book=<n>.  azx_match_play and azx_tournament_play refuse an
+ * engine with a self-play book (AZX_EINVAL, before touching any engine): they have books of their own.  The effect on
+ * playing strength and training efficiency is not measured. */
+int azx_set_selfplay_openings(azx_engine *e, int n_openings, int stride, const int16_t *moves, const int32_t *lengths,
+                              const double *weights /* NULL = uniform */);
+int azx_selfplay_opening_word(uint64_t seed, int64_t uid, uint32_t *word);
+int azx_selfplay_openings_bounds(int n_openings, const double *weights /* NULL = uniform */, uint64_t *ub);
+int azx_selfplay_openings_slots(azx_engine *e, int32_t *opening);
+int azx_selfplay_openings_stats(azx_engine *e, int64_t cap, int64_t *out /* [n][4] */);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

@@ -15,6 +15,8 @@ _lib.OPTIONAL.update(["azx_set_early_stop", "azx_early_stop_stats"])
 _lib.OPTIONAL.update(["azx_set_train_targets", "azx_get_train_targets", "azx_train_targets_stats"])
 _lib.OPTIONAL.update(["azx_debug_tower_tiles"])
 _lib.OPTIONAL.update(["azx_set_forced_playouts", "azx_get_forced_playouts", "azx_forced_playouts_stats"])
+_lib.OPTIONAL.update(["azx_set_selfplay_openings", "azx_selfplay_opening_word", "azx_selfplay_openings_bounds",
+                      "azx_selfplay_openings_slots", "azx_selfplay_openings_stats"])
 _lib.OPTIONAL.update(["azx_set_gumbel", "azx_get_gumbel", "azx_gumbel_stats", "azx_gumbel_variate", "azx_selftest_gumbel",
                       "azx_gumbel_state"])
 sys.argv = ["bench.py"] + sys.argv[2:]
