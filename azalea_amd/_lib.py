@@ -187,6 +187,12 @@ SYMBOLS = {
     "azx_gumbel_variate": (C.c_int, [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "azx_selftest_gumbel": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), _f32p]),
     "azx_gumbel_state": (C.c_int, [_vp, _u64p, _u64p]),
+    # rollout evaluator: a network-free MCTS opponent (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_rollout_evaluator": (C.c_int, [_vp, C.c_int, C.c_uint64]),
+    "azx_rollout_value": (C.c_int, [C.c_uint64, C.c_int, _i32p, C.c_int, _i32p, _f32p]),
+    "azx_selftest_rollout": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_uint64, _i32p, _f32p, _f32p,
+                                       C.POINTER(C.c_uint8)]),
+    "azx_rollout_stats": (C.c_int, [_vp, _i64p]),
 }
 
 class TrainConfig(C.Structure):

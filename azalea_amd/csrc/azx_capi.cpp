@@ -26,6 +26,7 @@
 #include "playout_cap.h"
 #include "gumbel.h"
 #include "resign.h"
+#include "rollout_kernels.h"
 #include "selfplay_openings.h"
 #include "tower_tiles.h"
 
@@ -86,6 +87,11 @@ struct azx_engine {
     int32_t *ext_info_host = nullptr;           // pinned landing place of ext.info (a copy into it never blocks the host)
     std::vector<char> ext_dirty;
     bool ext_failed = false;
+    // rollout evaluator (azx_set_rollout_evaluator): takes ext_fn's place at the evaluation points while ro_R > 0
+    int ro_R = 0;
+    uint64_t ro_seed = 0;
+    int64_t ro_handovers = 0, ro_rows = 0;
+    unsigned long long *ro_won = nullptr;       // device: rollouts won by the mover (one add per row)
     // play mode
     bool play_ready = false;
     int64_t q_alloc = 0;
@@ -555,6 +561,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " forced=" + forced_text(e) +
                        " gumbel=" + gumbel_text(e) +
                        " book=" + (d.bk_n > 0 ? std::to_string(d.bk_n) : std::string("off")) +
+                       (e->ro_R > 0 ? " eval=rollout(" + std::to_string(e->ro_R) + ")" : std::string()) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
@@ -779,7 +786,9 @@ static int upload_noise(azx_engine *e, const double *noise, int n_select, int no
 }
 
 // ---- registered external evaluator (azx_set_external_evaluator) ------------------------------------------------
-static bool ext_registered(const azx_engine *e) { return e->d.evaluator == AZX_EVAL_EXTERNAL && e->ext_fn; }
+static bool ext_registered(const azx_engine *e) {
+    return e->d.evaluator == AZX_EVAL_EXTERNAL && (e->ext_fn || e->ro_R > 0);
+}
 
 static int ext_refuse(const azx_engine *e) {
     if (!e->ext_failed) return AZX_OK;
@@ -855,9 +864,17 @@ static int ext_point_finish(azx_engine *e, bool timed) {
     if (n > 0) {
         azx_launch_ext_export(d, e->ext, n, e->stream);
         HIPCHECK(hipGetLastError());
-        const int rc = e->ext_fn(e->ext_user, n, kmax, e->ext.board, e->ext.legal, e->ext.value, e->ext.prior,
-                                 (void *)e->stream);
-        if (rc) return ext_fail(e, "external evaluator returned %d on a batch of %d rows", rc, n);
+        if (e->ro_R > 0) {      // the rollout evaluator: a kernel on the same stream where the callback would run
+            azx_launch_rollout_ex(e->ext.board, n, d.N, e->ro_R, e->ro_seed, e->ext.value, e->ext.prior, nullptr, nullptr,
+                                  e->ro_won, e->stream);
+            HIPCHECK(hipGetLastError());
+            e->ro_handovers += 1;
+            e->ro_rows += n;
+        } else {
+            const int rc = e->ext_fn(e->ext_user, n, kmax, e->ext.board, e->ext.legal, e->ext.value, e->ext.prior,
+                                     (void *)e->stream);
+            if (rc) return ext_fail(e, "external evaluator returned %d on a batch of %d rows", rc, n);
+        }
         azx_launch_ext_import(d, e->ext, n, e->stream);
         HIPCHECK(hipGetLastError());
     }
@@ -904,13 +921,9 @@ static int ext_search_resume(azx_engine *e, ExtCursor *c) {
     return AZX_OK;
 }
 
-extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *user) {
-    if (!e) return fail(AZX_EINVAL, "null engine");
-    ENGINE_GUARD(e);
-    if (e->d.evaluator != AZX_EVAL_EXTERNAL)
-        return fail(AZX_EINVAL, "an external evaluator needs an AZX_EVAL_EXTERNAL engine (this one has evaluator %d)",
-                    e->d.evaluator);
-    if (fn && !e->ext.info) {
+// the hand-over buffers of a registered evaluator, made at the first registration and kept
+static int ext_alloc(azx_engine *e) {
+    if (!e->ext.info) {
         const size_t E = (size_t)e->d.G * e->d.bs, nc = (size_t)e->d.ncells;
         ExtBufs x = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         int rc = AZX_OK;
@@ -931,8 +944,119 @@ extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *u
         e->ext = x;
         e->ext_dirty.assign((size_t)e->d.G, 0);
     }
+    return AZX_OK;
+}
+
+extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *user) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    ENGINE_GUARD(e);
+    if (e->d.evaluator != AZX_EVAL_EXTERNAL)
+        return fail(AZX_EINVAL, "an external evaluator needs an AZX_EVAL_EXTERNAL engine (this one has evaluator %d)",
+                    e->d.evaluator);
+    if (fn) TRY(ext_alloc(e));
     e->ext_fn = fn;
     e->ext_user = fn ? user : nullptr;
+    if (fn) e->ro_R = 0;                 // it and azx_set_rollout_evaluator replace each other: the last call wins
+    return AZX_OK;
+}
+
+// ---- rollout evaluator (azx_set_rollout_evaluator; NOT the reference's behaviour) --------------------------------
+extern "C" int azx_set_rollout_evaluator(azx_engine *e, int rollouts, uint64_t seed) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    ENGINE_GUARD(e);
+    if (e->d.evaluator != AZX_EVAL_EXTERNAL)
+        return fail(AZX_EINVAL, "a rollout evaluator needs an AZX_EVAL_EXTERNAL engine (this one has evaluator %d)",
+                    e->d.evaluator);
+    if (rollouts < 0 || rollouts > AZX_ROLLOUT_MAX)
+        return fail(AZX_EINVAL, "rollouts must be 0 (unregister) or in [1, %d], got %d", AZX_ROLLOUT_MAX, rollouts);
+    if (rollouts > 0 && (e->d.flags & AZX_FLAG_RANDOM_REFLECT))
+        return fail(AZX_EINVAL, "a rollout evaluator is a function of the position as it stands: the engine was created "
+                                "with AZX_FLAG_RANDOM_REFLECT");
+    if (rollouts == 0) {
+        e->ro_R = 0;
+        return AZX_OK;
+    }
+    TRY(ext_alloc(e));
+    if (!e->ro_won) TRY(dev_alloc(e, &e->ro_won, 1));
+    HIPCHECK(hipMemsetAsync(e->ro_won, 0, sizeof *e->ro_won, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->ro_R = rollouts;
+    e->ro_seed = seed;
+    e->ro_handovers = e->ro_rows = 0;
+    e->ext_fn = nullptr;
+    e->ext_user = nullptr;
+    return AZX_OK;
+}
+
+extern "C" int azx_rollout_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    unsigned long long won = 0;
+    if (e->ro_won) {
+        HIPCHECK(hipMemcpyAsync(&won, e->ro_won, sizeof won, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    }
+    out4[0] = e->ro_handovers;
+    out4[1] = e->ro_rows;
+    out4[2] = e->ro_rows * (int64_t)e->ro_R;
+    out4[3] = (int64_t)won;
+    return AZX_OK;
+}
+
+static int rollout_args(int board_size, int n, const int32_t *boards, int rollouts) {
+    if (board_size < 2 || board_size > AZX_MAX_BOARD)
+        return fail(AZX_EINVAL, "rollout: board size %d outside [2, %d]", board_size, AZX_MAX_BOARD);
+    if (rollouts < 1 || rollouts > AZX_ROLLOUT_MAX)
+        return fail(AZX_EINVAL, "rollout: rollouts %d outside [1, %d]", rollouts, AZX_ROLLOUT_MAX);
+    if (n < 1) return fail(AZX_EINVAL, "rollout: %d rows", n);
+    if (!boards) return fail(AZX_EINVAL, "null argument");
+    const size_t total = (size_t)n * board_size * board_size;
+    for (size_t i = 0; i < total; ++i)
+        if (boards[i] < 0 || boards[i] > 2)
+            return fail(AZX_EINVAL, "rollout: cell %zu holds %d, not 0, 1 or 2", i, boards[i]);
+    return AZX_OK;
+}
+
+extern "C" int azx_rollout_value(uint64_t seed, int board_size, const int32_t *board, int rollouts, int32_t *wins,
+                                 float *value) {
+    if (!wins || !value) return fail(AZX_EINVAL, "null argument");
+    TRY(rollout_args(board_size, 1, board, rollouts));
+    const int w = azx_rollout_host(seed, board_size, board, rollouts);
+    *wins = w;
+    *value = (float)(2 * w - rollouts) / (float)rollouts;
+    return AZX_OK;
+}
+
+// ---- self-test hook (tests): the rollout kernel alone on host boards -------------------------------------------
+extern "C" int azx_selftest_rollout(int device, int board_size, int n, const int32_t *boards, int rollouts, uint64_t seed,
+                                    int32_t *wins, float *value, float *prior, uint8_t *fills) {
+    if (!wins || !value || !prior) return fail(AZX_EINVAL, "null argument");
+    TRY(rollout_args(board_size, n, boards, rollouts));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AZX_ENODEV, "no HIP device visible");
+    DevGuard guard(device);
+    const size_t cells = (size_t)board_size * board_size, rows = (size_t)n;
+    const size_t nf = (size_t)(rollouts < AZX_ROLLOUT_FILLS ? rollouts : AZX_ROLLOUT_FILLS);
+    int32_t *db = nullptr, *dw = nullptr;
+    float *dv = nullptr, *dp = nullptr;
+    uint8_t *df = nullptr;
+    hipError_t err = hipMalloc(&db, rows * cells * 4);
+    if (err == hipSuccess) err = hipMalloc(&dw, rows * 4);
+    if (err == hipSuccess) err = hipMalloc(&dv, rows * 4);
+    if (err == hipSuccess) err = hipMalloc(&dp, rows * cells * 4);
+    if (err == hipSuccess && fills) err = hipMalloc(&df, rows * nf * cells);
+    if (err == hipSuccess) err = hipMemcpy(db, boards, rows * cells * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        azx_launch_rollout_ex(db, n, board_size, rollouts, seed, dv, dp, dw, df, nullptr, nullptr);
+        err = hipGetLastError();
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+    }
+    if (err == hipSuccess) err = hipMemcpy(wins, dw, rows * 4, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(value, dv, rows * 4, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(prior, dp, rows * cells * 4, hipMemcpyDeviceToHost);
+    if (err == hipSuccess && fills) err = hipMemcpy(fills, df, rows * nf * cells, hipMemcpyDeviceToHost);
+    (void)hipFree(db); (void)hipFree(dw); (void)hipFree(dv); (void)hipFree(dp); (void)hipFree(df);    // (on every path)
+    if (err != hipSuccess) return fail(AZX_EHIP, "azx_selftest_rollout: %s", hipGetErrorString(err));
     return AZX_OK;
 }
 
@@ -2574,7 +2698,7 @@ struct azx_match {
 };
 
 static const char *match_engine_problem(const azx_engine *e) {
-    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !e->ext_fn)
+    if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
         return "is an AZX_EVAL_EXTERNAL engine with no evaluator registered (azx_set_external_evaluator)";
     if (e->d.evaluator == AZX_EVAL_RESNET && !azx_net_ready(e->net)) return "has no weights (azx_set_weights)";
     return nullptr;

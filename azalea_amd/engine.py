@@ -114,6 +114,27 @@ class Engine:
         check(self.L.azx_set_external_evaluator(self.h, C.cast(cb, C.c_void_p), None))
         self._ext_cb = cb
 
+    # ---- rollout evaluator (azx_set_rollout_evaluator; NOT the reference's behaviour) ----
+    def set_rollout_evaluator(self, rollouts, seed=0):
+        """azx_set_rollout_evaluator (EVAL_EXTERNAL engines): every pending position's value is the share of `rollouts`
+        (1..4096) uniformly random playouts its mover wins, by the definition in include/azx.h; the priors are uniform.
+        The rollout kernel runs where a registered external evaluator would be called -- search / play / play_device /
+        replay_fill / play_steps, Match and Tournament -- with no torch tensor and no Python callback in the loop.  It
+        replaces a registered external evaluator and is replaced by one; 0 unregisters.  Zeroes rollout_stats().
+        Refused on an engine with FLAG_RANDOM_REFLECT."""
+        rollouts = int(rollouts)
+        if rollouts < 0 or rollouts > 4096:
+            raise ValueError("rollouts must be 0 (unregister) or in [1, 4096], got %r" % (rollouts,))
+        check(self.L.azx_set_rollout_evaluator(self.h, rollouts, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        if rollouts:
+            self._ext_cb = None
+
+    def rollout_stats(self):
+        """azx_rollout_stats since the evaluator was last registered: dict(handovers, rows, rollouts, rollouts_won)."""
+        out = np.zeros(4, np.int64)
+        check(self.L.azx_rollout_stats(self.h, _p(out, C.c_int64)))
+        return dict(handovers=int(out[0]), rows=int(out[1]), rollouts=int(out[2]), rollouts_won=int(out[3]))
+
     def set_prior_table(self, table):
         t = np.ascontiguousarray(table, np.float32)
         check(self.L.azx_set_prior_table(self.h, _p(t, C.c_float), t.size))
@@ -1147,6 +1168,40 @@ def selftest_gumbel(words, device=0):
     out = np.zeros(words.shape, np.float32)
     check(_lib.lib().azx_selftest_gumbel(device, words.size, _p(words, C.c_uint32), _p(out, C.c_float)))
     return out
+
+
+def rollout_value(seed, board, rollouts):
+    """azx_rollout_value: the rollout evaluator's definition (include/azx.h) on the host, no GPU.  board: an N x N (or
+    flat N*N) array in {0, 1, 2} in the first player's view, the mover being colour 1.  Returns (wins, value)."""
+    b = np.ascontiguousarray(board, np.int32).ravel()
+    n = int(round(b.size ** 0.5))
+    if n * n != b.size:
+        raise ValueError("board of %d cells is not square" % b.size)
+    wins, value = C.c_int32(0), C.c_float(0.0)
+    check(_lib.lib().azx_rollout_value(int(seed) & 0xFFFFFFFFFFFFFFFF, n, _p(b, C.c_int32), int(rollouts),
+                                       C.byref(wins), C.byref(value)))
+    return wins.value, np.float32(value.value)
+
+
+def selftest_rollout(boards, rollouts, seed=0, fills=False, device=0):
+    """azx_selftest_rollout: the rollout kernel alone on host boards [n, N, N] (or [n, N*N]).  Returns (wins int32 [n],
+    value float32 [n], prior float32 [n, cells]) and, with fills=True, the filled boards uint8 [n, min(rollouts, 64),
+    cells] of the first rollouts as a fourth entry."""
+    b = np.ascontiguousarray(boards, np.int32)
+    n = b.shape[0]
+    b = b.reshape(n, -1)
+    cells = b.shape[1]
+    N = int(round(cells ** 0.5))
+    if N * N != cells:
+        raise ValueError("boards of %d cells are not square" % cells)
+    wins = np.zeros(n, np.int32)
+    value = np.zeros(n, np.float32)
+    prior = np.zeros((n, cells), np.float32)
+    f = np.zeros((n, min(max(int(rollouts), 1), 64), cells), np.uint8) if fills else None
+    check(_lib.lib().azx_selftest_rollout(device, N, n, _p(b, C.c_int32), int(rollouts), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          _p(wins, C.c_int32), _p(value, C.c_float), _p(prior, C.c_float),
+                                          _p(f, C.c_uint8)))
+    return (wins, value, prior, f) if fills else (wins, value, prior)
 
 
 def resign_is_exempt(seed, uid, keep_prob):

@@ -206,6 +206,9 @@ def _throughput_policy(agent, external_batch=False):
         raise TypeError("evaluate_throughput needs agents whose policy is an azalea_amd Policy")
     if pol._uses_device_net():
         return pol
+    from .rollout import is_rollout_net
+    if is_rollout_net(pol.net):         # the rollout kernel is its evaluator: no torch in the loop, nothing to place
+        return pol
     if not external_batch:
         raise TypeError("evaluate_throughput needs agents whose Policy holds a HexNetwork "
                         "(external_batch=True takes other networks)")
@@ -232,6 +235,8 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     through an EVAL_EXTERNAL engine with policy.external_evaluator(net) registered: its net gets the leaf batches
     of all the slots in which it is the mover, on the device, at every evaluation point (ValueError when the
     network is not on such a device).  Agents with a HexNetwork keep the device tower, so fields may be mixed.
+    An agent whose Policy holds a rollout.RolloutNet needs no `external_batch`: its engine gets the rollout kernel
+    (Engine.set_rollout_evaluator; NOT the reference's behaviour) and `info` names it as eval=rollout(R).
     `pooled`: play all pairs in ONE ply loop (engine.Tournament, azx_tournament_play) instead of one match per pair
     after the other: the same games, tallies and `games` records, bit for bit.  `n_slots` stays "slots per engine"
     (default min((K - 1) * num_rounds, AZX_GAMES or 4096), rounded up to even): every engine's pool is shared out
@@ -261,7 +266,8 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
         raise ValueError("evaluate_throughput: gumbel is a self-play option: device matches and tournaments search and "
                          "draw every ply as the reference does (engine.Match refuses an engine with it set)")
     from . import engine as _eng
-    from .policy import SearchTreeFull, external_evaluator, tower_flags
+    from .policy import SearchTreeFull, tower_flags
+    from .rollout import register_evaluator
 
     pols = [_throughput_policy(a, external_batch) for a in agents]
     flags = [tower_flags(pol) for pol in pols]           # a ValueError before any engine is made
@@ -308,16 +314,14 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                               nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),   # 0: the engine's default
                               flags=flags[a], seed=((int(seed) << 8) + a) << 32)
             engines.append(eng)
-            if info is not None:
-                info[a] = eng.kernel_info()
             if hasattr(pol.net, "eval"):
                 pol.net.eval()
             if external:
-                eng.set_external_evaluator(external_evaluator(pol.net))
-                # the forward passes run on the engine's stream: after whatever torch queued last on the net's device
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+                # (a net's forward passes run on the engine's stream: after whatever torch queued last on its device)
+                register_evaluator(eng, pol.net)
+            if info is not None:
+                info[a] = eng.kernel_info()
+            if external:
                 continue
             sd = {k: v for k, v in pol.net.state_dict().items() if v.dtype == torch.float32}
             if dev.type == "cuda":

@@ -31,7 +31,8 @@ from . import distributed as azdist
 from . import engine as _eng
 from .game.hex import HexGameState
 from .play_game import play_game
-from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags
+from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags  # noqa: F401
+from .rollout import is_rollout_net, register_evaluator
 from .replay_buffer import ReplayDataFrame
 
 Metrics = Dict[str, float]
@@ -504,7 +505,7 @@ class Player:
             raise ValueError("external_batch is for networks other than HexNetwork: a HexNetwork takes the "
                              "native device path without it")
         dev = _net_device(pol.net)
-        if dev.type != "cuda":
+        if dev.type != "cuda" and not is_rollout_net(pol.net):      # (a RolloutNet's evaluator is a kernel of the engine)
             raise ValueError("external_batch needs the network on a CUDA (ROCm) device, it is on %s" % dev)
         if self.gather and azdist.is_distributed():
             raise ValueError("external_batch does not share reads across ranks: pass gather=False under "
@@ -525,7 +526,7 @@ class Player:
             pols.append(pol)
         for i, pol in enumerate(pols):
             dev = _net_device(pol.net)
-            if dev.type != "cuda":
+            if dev.type != "cuda" and not is_rollout_net(pol.net):
                 raise ValueError("device_match needs every network on a CUDA (ROCm) device, agent %d's is on %s" % (i, dev))
         if self.gather and azdist.is_distributed():
             raise ValueError("device_match does not share reads across ranks: pass gather=False under "
@@ -651,12 +652,9 @@ class Player:
         net = pol.net
         if hasattr(net, "eval"):
             net.eval()                          # parallel_player.py:64-69
-        eng.set_external_evaluator(external_evaluator(net))
-        # the forward passes run on the engine's stream: after whatever torch queued last (the trainer's step)
-        dev = _net_device(net)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+        # a net's forward passes run on the engine's stream: after whatever torch queued last (the trainer's step);
+        # a RolloutNet gets the rollout kernel instead
+        register_evaluator(eng, net)
         rows, st = eng.play(max(1, int(want)))
         self._harvest(eng, rows, st)
 
@@ -687,7 +685,7 @@ class Player:
                            evaluator=_eng.EVAL_EXTERNAL if external else _eng.EVAL_RESNET,
                            num_blocks=getattr(pol, "num_blocks", 0) if external else pol.num_blocks,
                            base_chans=getattr(pol, "base_chans", 0) if external else pol.base_chans,
-                           device=dev.index or 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
+                           device=(dev.index or 0) if dev.type == "cuda" else 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
                            flags=self._engine_flags | tower_flags(pol),
                            seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
 
@@ -711,11 +709,7 @@ class Player:
             if pol._uses_device_net():
                 self._push_weights(eng, pol)
             else:
-                eng.set_external_evaluator(external_evaluator(net))
-                dev = _net_device(net)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                torch.cuda.ExternalStream(eng.stream, device=dev).wait_event(ev)
+                register_evaluator(eng, net)
         if match is None:                                     # (a match wants its engines ready: weights / evaluator)
             match = _eng.Match(a, b)
             if self.openings:

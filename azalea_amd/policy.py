@@ -194,13 +194,18 @@ class Policy:
         from .network import HexNetwork
         return isinstance(self._net, HexNetwork)
 
+    def _uses_rollouts(self):
+        from .rollout import is_rollout_net
+        return is_rollout_net(self._net)
+
     def _get_engine(self, board_size):
         device = 0
-        if self._uses_device_net() and self._net.device.type == "cuda":
+        if (self._uses_device_net() or self._uses_rollouts()) and self._net.device.type == "cuda":
             device = self._net.device.index or 0
         key = (board_size, self.simulations, self.search_batch_size, float(self.exploration_coef),
                self._uses_device_net(), getattr(self, "num_blocks", 0), getattr(self, "base_chans", 0),
-               self.keep_reference_arena, device)          # a net moved to another GPU gets a new engine there
+               self.keep_reference_arena, device,          # a net moved to another GPU gets a new engine there
+               (self._net.rollouts, self._net.seed) if self._uses_rollouts() else None)
         if self._engine is None or key != self._engine_key:
             if self._engine is not None:
                 self._engine.close()
@@ -217,6 +222,8 @@ class Policy:
                 base_chans=getattr(self, "base_chans", 0) or 1,
                 nodes_per_game=min(cap, 1 << 23),
                 flags=_eng.FLAG_NO_COMPACT if self.keep_reference_arena else 0, device=device)
+            if self._uses_rollouts():       # the rollout kernel evaluates on the device: choose_action runs search()
+                self._engine.set_rollout_evaluator(self._net.rollouts, self._net.seed)
             self._engine_key = key
             self._engine_moves = None
             self._weights_version = None
@@ -289,6 +296,8 @@ class Policy:
                     self._net.eval()
             except Exception:
                 pass
+            eng.search(noise=noise, noise_scale=noise_scale)
+        elif self._uses_rollouts():
             eng.search(noise=noise, noise_scale=noise_scale)
         else:
             eng.search_external(self._host_evaluator(), noise=noise, noise_scale=noise_scale)

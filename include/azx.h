@@ -1028,6 +1028,58 @@ int azx_selfplay_openings_bounds(int n_openings, const double *weights /* NULL =
 int azx_selfplay_openings_slots(azx_engine *e, int32_t *opening);
 int azx_selfplay_openings_stats(azx_engine *e, int64_t cap, int64_t *out /* [n][4] */);
 
+/* ---- Rollout evaluator: a network-free MCTS opponent on the device -----------------------------------------------
+ * NOT the reference's behaviour (its only network-free agent is RandomPolicy); additive, off unless asked for, and
+ * outside every parity claim.  A registered rollout evaluator takes the place of an azx_eval_fn on an AZX_EVAL_EXTERNAL
+ * engine: every pending position's value is the share of uniformly random playouts the mover wins, its priors are
+ * uniform.  A filled Hex board has exactly one winner and further stones never undo a win, so a uniformly random
+ * playout to the end is a uniformly random fill of the empty cells plus one connectivity test.
+ *
+ * THE DEFINITION (the kernel, azx_rollout_value and the tests' restatement are held to it bit for bit).  All
+ * arithmetic is unsigned and wraps at the stated width.  The two mixers:
+ *   sm(x):  x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31)            (64 bit)
+ *   lb(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (32 bit)
+ * Input: seed, a u64; N, the board size, 2..13; board[N*N], int32 in {0, 1, 2} in the first player's view as the
+ *   hand-over exports it (azx_eval_fn's board_dev; mcts.py:174-181), so the side to move is colour 1.  Colour 1 wins by
+ *   connecting row 0 to row N-1, colour 2 by connecting column 0 to column N-1.  The neighbours of (i, j) are (i-1, j),
+ *   (i-1, j+1), (i, j-1), (i, j+1), (i+1, j-1), (i+1, j) where on the board (hex.py:192-197).  R, the number of
+ *   rollouts, 1..4096.
+ * Position key: H = sm(seed) ^ XOR over cells c with board[c] != 0 of sm(seed + 4*c + board[c]).
+ * Rollout r (0 <= r < R): k_r = lb((u32)H ^ lb((u32)(H >> 32) + r)).  With e the number of empty cells, need =
+ *   (e + 1) >> 1 (the mover places first) and rem = e, visit the empty cells in ascending index c:
+ *     w = lb(k_r + c * 0x9E3779B9); the cell becomes colour 1 iff ((u64)w * rem) >> 32 < need, and then need -= 1;
+ *     otherwise it becomes colour 2; then rem -= 1.
+ *   This is selection sampling: exactly (e + 1) >> 1 cells become colour 1.  The rollout is a win iff colour 1 connects
+ *   row 0 to row N-1 on the filled board.
+ * Result: wins = the number of winning rollouts; value = (float)(2*wins - R) / (float)R, one correctly rounded f32
+ *   division, in the mover's view; prior[j] = 1.0f / (float)e for each of the e legal moves.  e = 0 (a full board) is
+ *   legal for the self-test and the host function -- all rollouts are then the same board; the engine never asks for a
+ *   terminal position.
+ * The value is a pure function of (seed, board): it does not depend on slot, call order, or how the GPU scheduled
+ * anything.  So the same position gets the same estimate in every game of a match; games differ through the move draw.
+ *
+ * azx_set_rollout_evaluator: AZX_EVAL_EXTERNAL engines only (anything else is AZX_EINVAL); rollouts in 1..4096, 0
+ *   unregisters; AZX_EINVAL on an engine created with AZX_FLAG_RANDOM_REFLECT.  It allocates the hand-over buffers as
+ *   azx_set_external_evaluator does; at every evaluation point the pending rows are exported, the rollout kernel runs
+ *   on them and its results are imported, all on the engine's stream, with no callback.  From then on the engine counts
+ *   as "evaluator registered" everywhere that is asked (azx_search, azx_play*, azx_replay_fill, azx_match_create,
+ *   azx_tournament_create).  It and azx_set_external_evaluator replace each other: the last call wins.  Registering
+ *   zeroes azx_rollout_stats.  azx_kernel_info reports eval=rollout(R) while one is registered.
+ * azx_rollout_value: the definition on the host in plain C++, no GPU.  AZX_EINVAL for a board size outside 2..13,
+ *   rollouts outside 1..4096, a cell outside {0, 1, 2} or a null pointer.
+ * azx_selftest_rollout: the kernel alone on n host boards [n][cells]: wins[n], value[n], prior[n][cells] (entry j =
+ *   1/e for j < e, 0 after) and, unless NULL, fills[n][min(rollouts, 64)][cells], the filled boards (cells in {1, 2}) of
+ *   the first rollouts.  Argument errors as azx_rollout_value, before any device work.
+ * azx_rollout_stats: {hand-overs, rows, rollouts, rollouts won by the mover} since the evaluator was last registered.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_rollout_evaluator). */
+int azx_set_rollout_evaluator(azx_engine *e, int rollouts, uint64_t seed);
+int azx_rollout_value(uint64_t seed, int board_size, const int32_t *board, int rollouts, int32_t *wins, float *value);
+int azx_selftest_rollout(int device, int board_size, int n, const int32_t *boards, int rollouts, uint64_t seed,
+                         int32_t *wins, float *value, float *prior, uint8_t *fills /* NULL or [n][min(rollouts,64)][cells] */);
+int azx_rollout_stats(azx_engine *e, int64_t out4[4]);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

@@ -24,6 +24,11 @@ settings, temperature-1 sampling for the first `exploration_depth` plies and no 
                             11x11 6x64: its tensors are the golden fixture tests/golden/g8_checkpoint.npz), same search
                             settings on both sides -- an absolute yardstick
 
+    ... --anchor rollout[:R]
+                            also: the trained network against a rollout agent (azalea_amd.rollout.RolloutNet(R), default
+                            R = 64: MCTS on random playouts, no checkpoint, never changes -- NOT the reference's behaviour)
+                            at equal simulations, through evaluate_throughput: an absolute yardstick on any board
+
 Prints one JSON line: training seconds / steps / steps per second, rows of self-play consumed, and the tally."""
 import argparse
 import copy
@@ -63,6 +68,44 @@ def tournament(policies, n, rounds):
         agents.append(AzaleaAgent(lambda n=n: HexGame(n), policy=p, device="cuda:0"))
     out = evaluation.evaluate_batched(agents, rounds)
     return {"%d-%d" % k: [int(x) for x in v] for k, v in out.items()}
+
+
+def parse_anchor(text):
+    """--anchor: None, or the rollouts R of "rollout" / "rollout:R"."""
+    if not text or text == "off":
+        return None
+    name, _, r = text.partition(":")
+    if name != "rollout":
+        raise SystemExit("--anchor takes rollout or rollout:R, got %r" % text)
+    rollouts = int(r) if r else 64
+    if not 1 <= rollouts <= 4096:
+        raise SystemExit("--anchor rollout:R needs R in [1, 4096], got %d" % rollouts)
+    return rollouts
+
+
+def anchor_match(policy, args, rollouts):
+    """The trained network (agent 1) against a rollout agent (agent 0), same search settings, `rounds` games."""
+    from azalea_amd import evaluation
+    from azalea_amd.azalea_agent import AzaleaAgent
+    from azalea_amd.game.hex import HexGame
+    from azalea_amd.policy import Policy
+    from azalea_amd.rollout import RolloutNet
+    anchor = Policy()
+    anchor.initialize(dict(device="cpu", network="azalea_amd.rollout.RolloutNet", board_size=args.board, num_blocks=0,
+                           base_chans=0, simulations=args.sims, search_batch_size=10, exploration_coef=args.c,
+                           exploration_depth=args.depth, exploration_noise_alpha=args.alpha,
+                           exploration_noise_scale=0.25, exploration_temperature=1.0, seed=args.seed))
+    anchor.net = RolloutNet(rollouts, seed=args.seed)
+    agents = []
+    for p in (anchor, policy):
+        p.settings["move_sampling"] = True
+        p.settings["move_exploration"] = False
+        agents.append(AzaleaAgent(lambda n=args.board: HexGame(n), policy=p, device="cuda:0"))
+    info = {}
+    out = evaluation.evaluate_throughput(agents, args.rounds, seed=args.seed, info=info)
+    w_anchor, draws, w_net = (int(x) for x in out[(0, 1)])
+    return {"anchor": "rollout(%d)" % rollouts, "sims": args.sims, "tally_anchor_draw_trained": [w_anchor, draws, w_net],
+            "trained_win_rate_vs_anchor": w_net / max(1, w_anchor + draws + w_net), "anchor_engine": info[0]}
 
 
 def parse_train_targets(text):
@@ -157,6 +200,13 @@ def run(args):
             shipped["elo_start_minus_shipped"] = float(e3[2] - e3[0])
         except ranking.RankingError:
             pass
+    anchor = None
+    rollouts = parse_anchor(getattr(args, "anchor", None))
+    if rollouts is not None:
+        anchor = anchor_match(policy, args, rollouts)
+        print("trained network vs rollout(%d) at %d simulations: anchor %d, trained %d" %
+              (rollouts, args.sims, anchor["tally_anchor_draw_trained"][0], anchor["tally_anchor_draw_trained"][2]),
+              file=sys.stderr)
     curve = None
     if args.checkpoints:
         from azalea_amd.policy import Policy
@@ -177,7 +227,7 @@ def run(args):
             "steps_per_sec_incl_selfplay_and_fill": steps / secs, "selfplay_rows_consumed": steps * 128 / args.oversampling,
             "loss_by_step": losses.rows[1:],          # [step, mean loss over the interval, steps/s incl. self-play]
             "tally_untrained_draw_trained": [w_old, draws, w_new], "trained_win_rate": w_new / max(1, games),
-            "trained_elo_over_start": elo, "elo_curve": curve, "vs_shipped_model": shipped,
+            "trained_elo_over_start": elo, "elo_curve": curve, "vs_shipped_model": shipped, "vs_anchor": anchor,
             "world": args.world, "selfplay_mode": history.get("selfplay_mode"), "learner": history.get("learner"),
             "play_ahead": history.get("play_ahead")}
 
@@ -202,6 +252,7 @@ def main():
     ap.add_argument("--checkpoints", type=int, default=0, help="save this many evenly spaced checkpoints and rank them")
     ap.add_argument("--curve-rounds", type=int, default=40, help="games per pair of the ranking round robin")
     ap.add_argument("--vs-shipped", action="store_true")
+    ap.add_argument("--anchor", default=None, help="rollout or rollout:R: also play the trained network against a rollout agent")
     ap.add_argument("--lr-decay", type=float, default=0.1)
     ap.add_argument("--lr-decay-epochs", type=int, default=0, help="StepLR period in epochs (default: only the last epoch decays)")
     ap.add_argument("--mover-view", action="store_true", help="config['train_mover_view']: not the reference's batches")
@@ -212,6 +263,7 @@ def main():
     ap.add_argument("--selfplay-mode", default="actor_learner")
     ap.add_argument("--weight-sync-steps", type=int, default=50)
     args = ap.parse_args()
+    parse_anchor(args.anchor)                  # a bad value ends the run before it trains
     if args.world == 1:
         print(json.dumps(run(args)))
         return
