@@ -125,6 +125,7 @@ SYMBOLS = {
     "azx_debug_choose": (C.c_int, [_vp, _i32p, _f32p]),
     "azx_debug_counters": (C.c_int, [_vp, _u64p]),
     "azx_debug_counters_raw": (C.c_int, [_vp, _u64p, C.c_int64]),
+    "azx_debug_slow_div": (C.c_int, [_vp, _i32p]),
     "azx_kernel_info": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "azx_debug_set_queue_cap": (C.c_int, [_vp, C.c_int64]),
     "azx_debug_stagger": (C.c_int, [_vp, _i32p]),

@@ -1304,6 +1304,16 @@ extern "C" int azx_get_status(azx_engine *e, int32_t *status) {
     return AZX_OK;
 }
 
+extern "C" int azx_debug_slow_div(azx_engine *e, int32_t *out) {
+    if (!e || !out) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    std::vector<TreeHdr> th(e->d.G);
+    HIPCHECK(hipMemcpyAsync(th.data(), e->d.thdr, sizeof(TreeHdr) * th.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    for (int g = 0; g < e->d.G; ++g) out[g] = th[g].slow_div != 0;
+    return AZX_OK;
+}
+
 extern "C" int azx_get_tree_nodes(azx_engine *e, int32_t *nodes) {
     if (!e || !nodes) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);

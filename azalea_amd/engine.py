@@ -552,6 +552,13 @@ class Engine:
         check(self.L.azx_debug_counters_raw(self.h, _p(out, C.c_uint64), self.G))
         return out
 
+    def debug_slow_div(self):
+        """azx_debug_slow_div: int32 [G], 1 where a slot's scores go through the IEEE divide (a value outside the unscaled
+        divide's range has reached its tree since its last reset)."""
+        out = np.zeros(self.G, np.int32)
+        check(self.L.azx_debug_slow_div(self.h, _p(out, C.c_int32)))
+        return out
+
     def play_steps(self, plies):
         st = PlayStats()
         self._check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))

@@ -755,6 +755,14 @@ int azx_debug_choose(azx_engine *e, int32_t *move_id, float *moves_prob);
 int azx_debug_counters(azx_engine *e, uint64_t *out16);
 /* the same counters per game slot, not summed: out[n_games][16] (diagnostics: load balance) */
 int azx_debug_counters_raw(azx_engine *e, uint64_t *out, int64_t n_games);
+/* tests, read-only: out[n_games] = 1 for every slot whose scores are computed with the IEEE divide, 0 while the slot is on
+ * the unscaled divide.  A slot switches when a value reaches its tree that is neither 0 nor 2^-60 <= |v| <= 1e30 (an
+ * evaluation applied to it, its root's own included) and stays switched through moves, subtree reuse and arena
+ * compaction; only azx_reset of that slot switches it back.  Both divides give the same bits, so this changes no
+ * result: it tells a test which copy of the score arithmetic ran.  Always 0 with the inline evaluators
+ * (AZX_EVAL_UNIFORM, AZX_EVAL_UNIFORM_HASH), whose values are 0, -1 or multiples of 2^-15.  Blocking.
+ * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_slow_div). */
+int azx_debug_slow_div(azx_engine *e, int32_t *out);
 
 /* Which kernels this engine launches, as one line of text ("tree=... play=... tower=... heads=..."): the
  * diagnostic switches AZX_MCTS_GENERIC / AZX_NO_PERSISTENT / AZX_TOWER /

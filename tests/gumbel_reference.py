@@ -83,6 +83,12 @@ CASES = tuple((s.name, kind) for s in SETUPS for kind in s.kinds)
 # evaluators every child of a node has one prior, so ln P cancels in the improved row; here it does not.
 POW2 = Setup("m8_pow2", DEFAULT, 8, kinds=("pow2",))
 SETUP[POW2.name] = POW2
+# The same with exact zeros among the priors ("pow2z": w = 0 where (i - j) mod 4 == 3): ln P = -inf for those children, in
+# the candidates' keys, in sigma's prior-weighted mean and in the improved row.  m = 8 on the 5x5 positions, and m = 16 on
+# the positions with fewer than min(16, k) children of nonzero prior, where zero-prior children must become candidates.
+POW2Z = (Setup("m8_pow2z", DEFAULT, 8, kinds=("pow2z",)), Setup("m16_pow2z", DEFAULT, 16, family="few", kinds=("pow2z",)))
+SETUP.update({s.name: s for s in POW2Z})
+POW2Z_MAX_PLIES = 10                    # prefixes this short keep a legal cell of nonzero weight at every expanded node
 
 
 def philox_block(k0, k1, counter):
@@ -145,6 +151,8 @@ def safe_cut(keys, kept, dropped, ident):
     """Whether every (kept, dropped) pair is MARGIN apart in key, or identical in (g, P, n, w)."""
     for i in kept:
         for j in dropped:
+            if keys[i] == keys[j] == -np.inf:                   # two zero priors: ln 0 is -inf in any precision, an exact
+                continue                                        # tie on both sides, which the index breaks
             if abs(keys[i] - keys[j]) <= MARGIN and ident[i] != ident[j]:
                 return False
     return True
@@ -158,12 +166,43 @@ def pow2_prior(tiles, n):
     return (w / w.sum()).astype(f32)
 
 
+def pow2z_prior(tiles, n):
+    """pow2_prior with w = 0 where (i - j) mod 4 == 3: exact zeros among the priors.  Defined only while some legal cell
+    has a nonzero weight."""
+    t = np.asarray(tiles, np.int64) - 1
+    d = (t // n - t % n) % 4
+    w = np.where(d == 3, 0.0, np.ldexp(np.float64(1.0), -(1 + d)))
+    assert w.sum() > 0, tiles
+    return (w / w.sum()).astype(f32)
+
+
+PRIORS = {"pow2": pow2_prior, "pow2z": pow2z_prior}
+
+
+def pow2z_device_evaluator(n, device):
+    """The "pow2z" stub as a registered external evaluator (torch tensors on `device`): value 0, prior pow2z_prior of the
+    row's legal cells.  pow2z_prior is defined only while some legal cell has a nonzero weight, which holds at every node
+    the restatement expands; the GPU tests then play the games to their ends for the harvest, and a late row without such
+    a cell gets the uniform row here."""
+    import torch
+
+    def evaluate(board, legal):
+        t = legal.to(torch.int64) - 1
+        d = torch.remainder(torch.div(t, n, rounding_mode="floor") - torch.remainder(t, n), 4)
+        one = torch.ones((), dtype=torch.float64, device=device)
+        zero = torch.zeros((), dtype=torch.float64, device=device)
+        w = torch.where((legal != 0) & (d != 3), torch.ldexp(one, -(1 + d)), zero)
+        w = torch.where(w.sum(1, keepdim=True) > 0, w, torch.where(legal != 0, one, zero))
+        return torch.zeros(len(board), dtype=torch.float32, device=device), (w / w.sum(1, keepdim=True)).to(torch.float32)
+    return evaluate
+
+
 class Search(fp.Search):
-    """fp.Search with the Gumbel rule: m = 0 is the parent class's search (no rule).  kind "pow2": value 0 and
-    pow2_prior in place of the 1/k table."""
+    """fp.Search with the Gumbel rule: m = 0 is the parent class's search (no rule; forced_k: its forcing rule).  kinds
+    "pow2" / "pow2z": value 0 and pow2_prior / pow2z_prior in place of the 1/k table."""
 
     def __init__(self, prefix, kind, m=0, c_visit=50.0, c_scale=1.0, seed=SEED, uid=0, greedy=False, cfg=DEFAULT,
-                 sims=None, bs=None):
+                 sims=None, bs=None, forced_k=0.0):
         self.m, self.c_visit, self.c_scale = int(m), float(c_visit), float(c_scale)
         self.seed, self.uid, self.ply, self.greedy = seed, uid, len(prefix), greedy
         self.nbt = (cfg.sims if sims is None else sims) // (cfg.bs if bs is None else bs) + 1
@@ -172,8 +211,9 @@ class Search(fp.Search):
         self.root_picks = []                                    # the child every root select descended into
         self.survivor_sets = []                                 # S after the candidates and after each halving
         self.safe = True
-        self.pow2, self.board_n = kind == "pow2", cfg.n
-        super().__init__(prefix, "uniform" if self.pow2 else kind, 0.0, sims=sims, bs=bs, cfg=cfg)
+        self.pow2, self.board_n = PRIORS.get(kind), cfg.n
+        assert not (m and forced_k)
+        super().__init__(prefix, "uniform" if self.pow2 else kind, forced_k, sims=sims, bs=bs, cfg=cfg)
         if self.m:
             self.finish()
 
@@ -181,7 +221,7 @@ class Search(fp.Search):
         first = self.num_nodes
         super().expand(node, k)
         if self.pow2 and k:
-            self.pp[first:first + k] = pow2_prior(self.moves[node], self.board_n)
+            self.pp[first:first + k] = self.pow2(self.moves[node], self.board_n)
 
     def root(self):
         sl = slice(self.first[0], self.first[0] + self.nch[0])
@@ -246,6 +286,12 @@ class Search(fp.Search):
 def prefixes_of(setup, kind):
     if kind == "pow2":
         return fp.prefixes("uniform")[:40]
+    if kind == "pow2z":
+        out = tuple(p for p in fp.prefixes("uniform") if len(p) <= POW2Z_MAX_PLIES)
+        if setup.family == "few":
+            out = tuple(p for p in out if nonzero_pow2z(p) < min(setup.m, DEFAULT.cells - len(p)))
+        assert len(out) >= 8
+        return out
     if setup.family == "5x5":
         return fp.prefixes(kind)
     if setup.family == "late":
@@ -259,6 +305,24 @@ def prefixes_of(setup, kind):
         rng = np.random.RandomState(7000 + n)                   # all with k > 64: two live register slots
         more = tuple(op.random_prefix(rng, setup.cfg, plies) for plies in (1, 3, 5, 7, 8, 9, 10, 12, 14))
     return tuple(op.sweep_prefixes(n)) + tuple(op.wide_hash_prefixes(n)) + more
+
+
+def nonzero_pow2z(prefix):
+    """The number of root children of `prefix` (default 5x5 setup) whose pow2z prior is not zero."""
+    return int(np.count_nonzero(pow2z_prior(game_at(prefix, DEFAULT).legal_moves(), DEFAULT.n)))
+
+
+@functools.lru_cache(maxsize=None)
+def forced_positions_pow2z(k=fp.K_FORCED):
+    """fp.position()'s dicts (without the rule-off root) for the forcing rule under the pow2z priors, on the "m8_pow2z"
+    prefixes."""
+    out = []
+    for prefix in prefixes_of(SETUP["m8_pow2z"], "pow2z"):
+        on = Search(prefix, "pow2z", forced_k=k)
+        r = fp.prune(on.n, on.w, on.p, k, DEFAULT.c_puct)
+        out.append(dict(prefix=list(prefix), n=on.n, w=on.w, p=on.p, forced=on.forced, overrode=on.overrode,
+                        forced_at=tuple(on.forced_at), r=r, removed=int((on.n - r).sum())))
+    return tuple(out)
 
 
 @functools.lru_cache(maxsize=None)

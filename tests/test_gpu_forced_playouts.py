@@ -153,6 +153,33 @@ def test_reference_rows_at_temperature_one_are_the_pruned_shares():
     assert stats["visits_removed"] == sum(r["removed"] for r in refs)
 
 
+@pytest.mark.parametrize("prune", [False, True], ids=["noprune", "prune"])
+def test_exact_zeros_among_the_priors(prune):
+    """A registered external evaluator hands out rows with exact zeros (tests/gumbel_reference.py's "pow2z"): the forced set
+    compares n * n < (k * P) * S, which no child with P = 0 passes, and the prune's f = sqrt((k * P) * S) is 0 there.  The
+    counts, the pruned row and the statistics against the restatement under the same priors, exactly as above."""
+    from azalea_amd import engine as eng
+    import gumbel_reference as gref
+    refs = gref.forced_positions_pow2z(K)
+    assert all((r["p"] == 0).any() and all(r["p"][j] > 0 for j in r["forced_at"]) for r in refs)
+    assert any(((r["p"] == 0) & (r["n"] > 0)).any() for r in refs)
+    E = make(eng.EVAL_EXTERNAL, len(refs))
+    E.set_external_evaluator(gref.pow2z_device_evaluator(N, DEV))
+    E.set_train_targets("visits")
+    E.set_forced_playouts(K, prune)
+    got, stats = first_rows(E, [r["prefix"] for r in refs])
+    E.close()
+    for (row, m), r in zip(got, refs):
+        k = len(r["n"])
+        want = r["r"] if prune else r["n"]
+        assert raw_sum(m) == int(r["n"].sum()) and m[1] == (r["n"] > 0).sum(), r["prefix"]
+        assert np.array_equal(bits(row[:k]), bits(ref.shares(want))) and (row[k:] == 0).all(), (r["prefix"], row[:k], want)
+    print("pow2z", "prune" if prune else "noprune", stats)
+    assert stats == dict(full_plies=len(refs), forced_selects=sum(r["forced"] for r in refs),
+                         rows_pruned=sum(r["removed"] > 0 for r in refs) if prune else 0,
+                         visits_removed=sum(r["removed"] for r in refs) if prune else 0)
+
+
 # ---- 2. whole games --------------------------------------------------------------------------------------------------
 def check_games(rows, m=None):
     """Every game's rows: contiguous, one per ply from the empty board; a valid distribution each (non-negative, zero

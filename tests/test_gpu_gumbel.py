@@ -231,6 +231,53 @@ def test_improved_rows_under_non_uniform_priors_keep_the_ln_p_term():
     check_state_and_stats(refs, state, stats, improved=True)
 
 
+@pytest.mark.parametrize("setup", ref.POW2Z, ids=[s.name for s in ref.POW2Z])
+def test_exact_zeros_among_the_priors(setup):
+    """ln P = -inf for a child of prior 0, in the candidates' keys, the halvings and the improved row.  With m = 8 no such
+    child may become a candidate; with m = 16 on positions with fewer children of nonzero prior than candidates some
+    must, are visited, and are halved away.  One run records the visit shares (the root picks, select by select, decide
+    the counts), one the improved rows; both against the restatement: candidates, survivors, counts, the move, the row
+    within the bounds of the tests above -- and the row finite, exactly 0 where P = 0, its sum within 1e-5 of 1."""
+    from azalea_amd import engine as eng
+    refs = ref.positions(setup.name, "pow2z")
+    assert all(r["safe"] for r in refs)
+    zero = [r["p"] == 0 for r in refs]
+    assert all(z.any() and not z.all() for z in zero)
+    if setup.family == "few":
+        assert all(ref.nonzero_pow2z(r["prefix"]) < r["m0"] for r in refs)
+        assert all(z[r["candidates"]].any() and (r["n"][z] > 0).any() and not z[r["survivors"]].any()
+                   for r, z in zip(refs, zero))
+    else:
+        assert not any(z[r["candidates"]].any() for r, z in zip(refs, zero))
+    for improved in (False, True):
+        E = make(eng.EVAL_EXTERNAL, len(refs), setup.cfg)
+        E.set_external_evaluator(ref.pow2z_device_evaluator(setup.cfg.n, DEV))
+        if not improved:
+            E.set_train_targets("visits")
+        E.set_gumbel(setup.m, setup.c_visit, setup.c_scale, improved_rows=improved)
+        got, state, stats = first_rows(E, [r["prefix"] for r in refs], setup.cfg)
+        E.close()
+        worst_row = worst_lp = 0.0
+        for (row, m, cell), r, z in zip(got, refs, zero):
+            k, S = r["k"], raw_sum(m)
+            assert S == int(r["n"].sum()), (r["prefix"], S)
+            assert np.isfinite(row).all() and (row >= 0).all() and (row[k:] == 0).all()
+            if improved:
+                assert (row[:k][z] == 0).all() and (row[:k][~z] > 0).all(), (r["prefix"], row[:k])
+                assert abs(float(row[:k].astype(np.float64).sum()) - 1.0) <= 1e-5
+                worst_row = max(worst_row, float(np.abs(row[:k].astype(np.float64) - r["pi"]).max()))
+            else:
+                assert np.array_equal(np.rint(row[:k].astype(np.float64) * S), r["n"]), (r["prefix"], row[:k] * S, r["n"])
+            assert np.isfinite(m).all()
+            worst_lp = max(worst_lp, abs(float(m[2]) - float(np.log(r["pi"][r["move"]]))))
+            if cell is not None:
+                assert cell == legal_cells(r["prefix"], setup.cfg)[r["move"]], (r["prefix"], cell, r["move"])
+        print(setup.name, "improved rows" if improved else "visit shares", "positions", len(refs),
+              "max |row - pi| %.3g, max |metric 2 - ln pi_chosen| %.3g" % (worst_row, worst_lp))
+        assert worst_row <= 5e-4 and worst_lp <= 1e-3
+        check_state_and_stats(refs, state, stats, improved=improved)
+
+
 @pytest.mark.parametrize("name,kind", ref.CASES)
 def test_improved_rows_are_the_restatements_softmax(name, kind, monkeypatch):
     """The row against the restatement's float64 pi within 5e-4 absolute (an argument error delta of about 1e-4 gives a

@@ -338,6 +338,36 @@ def test_at_most_a_tenth_of_a_cases_positions_is_left_out(name, kind):
     assert len(refs) >= 5 and unsafe <= ref.MAX_UNSAFE_SHARE * len(refs)
 
 
+@pytest.mark.parametrize("setup", ref.POW2Z, ids=[s.name for s in ref.POW2Z])
+def test_the_zero_prior_positions_are_what_the_gpu_test_needs(setup):
+    """Exact zeros among the priors ("pow2z"): every expanded node kept a legal cell of nonzero weight (pow2z_prior asserts
+    it), every decision is safe, the improved row is finite and 0 exactly where P = 0; with m = 8 no zero-prior child is a
+    candidate, on the "few" positions (m = 16) some must be, are visited and never survive.  The device stub computes the
+    same rows to the bit (on the CPU here), and the forcing rule under these priors never forces a child with P = 0."""
+    import torch
+    refs = ref.positions(setup.name, "pow2z")
+    assert len(refs) >= 8 and all(r["safe"] for r in refs)
+    assert all(len(r["prefix"]) <= ref.POW2Z_MAX_PLIES for r in refs)
+    for r in refs:
+        z = r["p"] == 0
+        assert z.any() and not z.all() and np.isfinite(r["pi"]).all() and abs(r["pi"].sum() - 1.0) <= 1e-12
+        assert np.array_equal(r["pi"] == 0, z) and not z[r["survivors"]].any() and not z[r["move"]]
+        if setup.family == "few":
+            assert ref.nonzero_pow2z(r["prefix"]) < r["m0"] and z[r["candidates"]].any() and (r["n"][z] > 0).any()
+        else:
+            assert not z[r["candidates"]].any()
+        legal = ref.game_at(r["prefix"], setup.cfg).legal_moves()
+        row = np.zeros((1, setup.cfg.cells), np.int32)
+        row[0, :len(legal)] = legal
+        v, p = ref.pow2z_device_evaluator(setup.cfg.n, torch.device("cpu"))(torch.zeros(1, 5, 5), torch.tensor(row))
+        assert float(v[0]) == 0 and np.array_equal(bits(p[0, :len(legal)].numpy()), bits(r["p"])) and not p[0, len(legal):].any()
+    if setup.family != "few":
+        fz = ref.forced_positions_pow2z()
+        assert len(fz) == len(refs) and sum(r["forced"] for r in fz) > 100 and sum(r["removed"] for r in fz) > 100
+        assert all(r["p"][j] > 0 for r in fz for j in r["forced_at"])
+        assert any(((r["p"] == 0) & (r["n"] > 0)).any() for r in fz)            # bare Q does reach a zero-prior child
+
+
 def test_the_safe_decision_rule_on_hand_made_keys():
     keys = np.array([3.0, 2.0005, 2.0, 1.0])
     ident = [(0.0, 0.25, 1.0, 0.0)] * 4
@@ -351,6 +381,10 @@ def test_the_safe_decision_rule_on_hand_made_keys():
     # ties go to the lower index
     kept, dropped = ref.top(np.array([1.0, 2.0, 2.0, 2.0]), np.arange(4), 2)
     assert kept.tolist() == [1, 2] and dropped.tolist() == [0, 3]
+    # two zero priors (ln 0 = -inf on both sides) tie exactly whatever else differs; -inf against a finite key is safe
+    ninf = np.array([1.0, -np.inf, -np.inf, -np.inf])
+    kept, dropped = ref.top(ninf, np.arange(4), 2)
+    assert kept.tolist() == [0, 1] and dropped.tolist() == [2, 3] and ref.safe_cut(ninf, kept, dropped, other)
     # sigma: the completion is the prior-weighted mean of the visited children's qh
     sig = ref.sigma_of([2, 0, 1], [1.0, 0.0, -1.0], [0.5, 0.25, 0.25], 50.0, 1.0)
     qh = [0.5 * (-1.0 / 2) + 0.5, None, 0.5 * (1.0 / 1) + 0.5]
