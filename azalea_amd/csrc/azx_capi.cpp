@@ -54,6 +54,40 @@ static int fail(int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                              \
     } while (0)
 
+// The self-play options as the host holds them (azx_set_playout_cap, azx_set_resign, azx_set_early_stop,
+// azx_set_train_targets, azx_set_forced_playouts, azx_set_gumbel): a default-constructed value is every option off.
+// e->d carries "off" except inside the throughput self-play calls (SelfplayScope).
+struct SelfplayOptions {
+    bool cap_on = false;
+    double cap_full_prob = 1.0;
+    int cap_fast_sims = 0;
+    bool resign_on = false;
+    double resign_thr = -1.0, resign_keep = 0.0;
+    int resign_min_ply = 0;
+    bool estop_on = false;
+    int tt_rows = AZX_ROWS_REFERENCE;
+    float tt_mix = 0.0f;
+    bool tt_on() const { return tt_rows != AZX_ROWS_REFERENCE || tt_mix > 0.0f; }
+    float fp_k = 0.0f;
+    int fp_prune = 0;
+    int gm_m = 0, gm_rows = 0;
+    float gm_c_visit = 0.0f, gm_c_scale = 0.0f;
+
+    // the option fields of a DevEngine for these settings, every one of them (so the default value writes "off")
+    void write(DevEngine &d) const {
+        d.cap_fast_batches = cap_on ? cap_fast_sims / d.bs + 1 : 0;      // mcts.py:268 applied to fast_simulations
+        d.cap_thr_m1 = cap_on ? azx_cap_threshold_m1(cap_full_prob) : 0u;
+        d.resign_mode = !resign_on ? AZX_RESIGN_OFF : resign_keep > 0.0 ? AZX_RESIGN_DRAW_EXEMPT : AZX_RESIGN_NONE_EXEMPT;
+        d.resign_min_ply = resign_on ? resign_min_ply : 0;
+        d.resign_thr = resign_on ? (float)resign_thr : 0.0f;
+        d.resign_keep_m1 = resign_on && resign_keep > 0.0 ? azx_resign_threshold_m1(resign_keep) : 0u;
+        d.early_stop = estop_on ? 1 : 0;
+        d.tt_rows = tt_rows; d.tt_mix = tt_mix;
+        d.fp_k = fp_k; d.fp_prune = fp_prune;
+        d.gm_m = gm_m; d.gm_rows = gm_rows; d.gm_c_visit = gm_c_visit; d.gm_c_scale = gm_c_scale;
+    }
+};
+
 struct azx_engine {
     azx_config cfg;
     DevEngine d;
@@ -138,64 +172,21 @@ struct azx_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
     int32_t *stagger_ctr = nullptr;     // azx_net_eval_rows_behind's count and azx_debug_stagger's counters (4 ints)
     int64_t dbg_qcap = 0;               // azx_debug_set_queue_cap
-    // playout cap (azx_set_playout_cap): e->d carries "off" except inside the throughput self-play calls (CapScope)
-    bool cap_on = false;
-    double cap_full_prob = 1.0;
-    int cap_fast_sims = 0;
+    SelfplayOptions opt;                // what the azx_set_* of the self-play options last stored
     unsigned long long cap_base[3] = {0, 0, 0};   // CTR_CAP_* sums when the cap was last set
-    // resignation (azx_set_resign): handed to the same launches, by the same scope
-    bool resign_on = false;
-    double resign_thr = -1.0, resign_keep = 0.0;
-    int resign_min_ply = 0;
-    // early stop (azx_set_early_stop): handed to the same launches, by the same scope
-    bool estop_on = false;
-    // training targets (azx_set_train_targets): handed to the same launches, by the same scope
-    int tt_rows = AZX_ROWS_REFERENCE;
-    float tt_mix = 0.0f;
-    bool tt_on() const { return tt_rows != AZX_ROWS_REFERENCE || tt_mix > 0.0f; }
-    // forced playouts and policy target pruning (azx_set_forced_playouts): handed to the same launches, by the same scope
-    float fp_k = 0.0f;
-    int fp_prune = 0;
-    // Gumbel root search with sequential halving (azx_set_gumbel): handed to the same launches, by the same scope
-    int gm_m = 0, gm_rows = 0;
-    float gm_c_visit = 0.0f, gm_c_scale = 0.0f;
     // self-play opening book (azx_set_selfplay_openings): the device tables e->d.bk_* point at (the engine owns them;
     // replaced as a whole, freed by azx_destroy).  Not scoped: e->d carries the book in every launch (azx_dev.h)
     void *book_allocs[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
-// The throughput self-play calls hand their launches the configured playout cap; every other launch of the engine
-// (azx_search, the phase API, matches) reads "off" from e->d.  Resignation (azx_set_resign) and early stop
-// (azx_set_early_stop) travel the same way, and so do the training targets (azx_set_train_targets) and forced
-// playouts (azx_set_forced_playouts) and the Gumbel root search (azx_set_gumbel).
-struct CapScope {
+// The throughput self-play calls hand their launches the engine's self-play options; every other launch of the engine
+// (azx_search, the phase API, matches) reads "off" from e->d.  (The opening book is not scoped: azx_dev.h.)
+struct SelfplayScope {
     DevEngine &d;
-    explicit CapScope(azx_engine *e) : d(e->d) {
-        if (e->cap_on) {
-            d.cap_fast_batches = e->cap_fast_sims / e->cfg.search_batch_size + 1;   // mcts.py:268 applied to fast_simulations
-            d.cap_thr_m1 = azx_cap_threshold_m1(e->cap_full_prob);
-        }
-        if (e->resign_on) {
-            d.resign_mode = e->resign_keep > 0.0 ? AZX_RESIGN_DRAW_EXEMPT : AZX_RESIGN_NONE_EXEMPT;
-            d.resign_min_ply = e->resign_min_ply;
-            d.resign_thr = (float)e->resign_thr;
-            d.resign_keep_m1 = e->resign_keep > 0.0 ? azx_resign_threshold_m1(e->resign_keep) : 0u;
-        }
-        if (e->estop_on) d.early_stop = 1;
-        d.tt_rows = e->tt_rows; d.tt_mix = e->tt_mix;
-        d.fp_k = e->fp_k; d.fp_prune = e->fp_prune;
-        d.gm_m = e->gm_m; d.gm_rows = e->gm_rows; d.gm_c_visit = e->gm_c_visit; d.gm_c_scale = e->gm_c_scale;
-    }
-    ~CapScope() {
-        d.cap_fast_batches = 0; d.cap_thr_m1 = 0u;
-        d.resign_mode = AZX_RESIGN_OFF; d.resign_min_ply = 0; d.resign_thr = 0.0f; d.resign_keep_m1 = 0u;
-        d.early_stop = 0;
-        d.tt_rows = AZX_ROWS_REFERENCE; d.tt_mix = 0.0f;
-        d.fp_k = 0.0f; d.fp_prune = 0;
-        d.gm_m = 0; d.gm_rows = 0; d.gm_c_visit = 0.0f; d.gm_c_scale = 0.0f;
-    }
-    CapScope(const CapScope &) = delete;
-    CapScope &operator=(const CapScope &) = delete;
+    explicit SelfplayScope(azx_engine *e) : d(e->d) { e->opt.write(d); }
+    ~SelfplayScope() { SelfplayOptions().write(d); }
+    SelfplayScope(const SelfplayScope &) = delete;
+    SelfplayScope &operator=(const SelfplayScope &) = delete;
 };
 
 template <typename T>
@@ -491,40 +482,77 @@ static int pipeline_streams(azx_engine *e) {
     return AZX_OK;
 }
 
-static std::string resign_text(const azx_engine *e) {
-    if (!e->resign_on) return "off";
-    char t[96];
-    snprintf(t, sizeof t, "%.6g/%d/%.6g", e->resign_thr, e->resign_min_ply, e->resign_keep);
+// ---- the self-play options as the host describes them, in the order azx_kernel_info lists them and matches refuse them ----
+static std::string strf(const char *fmt, ...) {
+    char t[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t, sizeof t, fmt, ap);
+    va_end(ap);
     return t;
 }
 
-static std::string targets_text(const azx_engine *e) {
-    if (!e->tt_on()) return "off";
-    char t[64];
-    snprintf(t, sizeof t, "%s/%.9g", e->tt_rows == AZX_ROWS_VISITS ? "visits" : "reference", (double)e->tt_mix);
-    return t;
+struct OptionInfo {
+    const char *field;                          // azx_kernel_info: " <field>=<text>", "off" while the option is not set
+    bool (*is_set)(const azx_engine *);
+    std::string (*text)(const azx_engine *);
+    const char *noun;                           // a refusal: "engine <i> has <noun> set: <reason> (<clear>)",
+    const char *reason;                         // ... {} standing for "match" / "tournament" in both clauses
+    const char *clear;
+};
+
+static const OptionInfo SELFPLAY_OPTIONS[] = {
+    {"cap", [](const azx_engine *e) { return e->opt.cap_on; },
+     [](const azx_engine *e) { return strf("%.6g/%d", e->opt.cap_full_prob, e->opt.cap_fast_sims); },
+     "a playout cap", "a {} records one row per moved ply", "clear it with azx_set_playout_cap(e, 1.0, 0)"},
+    {"resign", [](const azx_engine *e) { return e->opt.resign_on; },
+     [](const azx_engine *e) { return strf("%.6g/%d/%.6g", e->opt.resign_thr, e->opt.resign_min_ply, e->opt.resign_keep); },
+     "resignation", "a {} plays every game to the end and records one row per moved ply", "clear it with azx_clear_resign"},
+    {"estop", [](const azx_engine *e) { return e->opt.estop_on; },
+     [](const azx_engine *) { return std::string("on"); },
+     "early stop", "a {} searches every ply in full", "clear it with azx_set_early_stop(e, 0)"},
+    {"targets", [](const azx_engine *e) { return e->opt.tt_on(); },
+     [](const azx_engine *e) {
+         return strf("%s/%.9g", e->opt.tt_rows == AZX_ROWS_VISITS ? "visits" : "reference", (double)e->opt.tt_mix);
+     },
+     "training targets", "a {}'s harvest records the reference's rows and the outcome",
+     "clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0)"},
+    {"forced", [](const azx_engine *e) { return e->opt.fp_k > 0.0f; },
+     [](const azx_engine *e) { return strf("%.9g/%s", (double)e->opt.fp_k, e->opt.fp_prune ? "prune" : "noprune"); },
+     "forced playouts", "a {} searches and draws every ply as the reference does",
+     "clear them with azx_set_forced_playouts(e, 0, 0)"},
+    {"gumbel", [](const azx_engine *e) { return e->opt.gm_m != 0; },
+     [](const azx_engine *e) {
+         return strf("%d/%.9g/%.9g/%s", e->opt.gm_m, (double)e->opt.gm_c_visit, (double)e->opt.gm_c_scale,
+                     e->opt.gm_rows ? "rows" : "norows");
+     },
+     "the Gumbel root search", "a {} searches and draws every ply as the reference does",
+     "clear it with azx_set_gumbel(e, 0, 0, 1, 0)"},
+    {"book", [](const azx_engine *e) { return e->d.bk_n > 0; },
+     [](const azx_engine *e) { return std::to_string(e->d.bk_n); },
+     "a self-play opening book", "a {} starts its games from its own book",
+     "azx_{}_set_openings; clear the engine's with azx_set_selfplay_openings(e, 0, ...)"},
+};
+
+static std::string selfplay_option_fields(const azx_engine *e) {
+    std::string out;
+    for (const OptionInfo &o : SELFPLAY_OPTIONS)
+        out += std::string(" ") + o.field + "=" + (o.is_set(e) ? o.text(e) : std::string("off"));
+    return out;
 }
 
-static std::string forced_text(const azx_engine *e) {
-    if (!(e->fp_k > 0.0f)) return "off";
-    char t[64];
-    snprintf(t, sizeof t, "%.9g/%s", (double)e->fp_k, e->fp_prune ? "prune" : "noprune");
-    return t;
-}
-
-static std::string gumbel_text(const azx_engine *e) {
-    if (e->gm_m == 0) return "off";
-    char t[96];
-    snprintf(t, sizeof t, "%d/%.9g/%.9g/%s", e->gm_m, (double)e->gm_c_visit, (double)e->gm_c_scale,
-             e->gm_rows ? "rows" : "norows");
-    return t;
-}
-
-static std::string cap_text(const azx_engine *e) {
-    if (!e->cap_on) return "off";
-    char t[64];
-    snprintf(t, sizeof t, "%.6g/%d", e->cap_full_prob, e->cap_fast_sims);
-    return t;
+// A match or tournament (`what`) takes no engine with a self-play option set: AZX_EINVAL for the first option of the
+// table that any engine has, naming the first engine that has it -- by its letter of `letters`, else by its index.
+static int refuse_selfplay_options(azx_engine *const *eng, int n, const char *what, const char *letters) {
+    for (const OptionInfo &o : SELFPLAY_OPTIONS)
+        for (int k = 0; k < n; ++k) {
+            if (!o.is_set(eng[k])) continue;
+            std::string clauses = std::string(o.reason) + " (" + o.clear + ")";
+            for (size_t at; (at = clauses.find("{}")) != std::string::npos;) clauses.replace(at, 2, what);
+            const std::string who = letters ? std::string(1, letters[k]) : std::to_string(k);
+            return fail(AZX_EINVAL, "engine %s has %s set: %s", who.c_str(), o.noun, clauses.c_str());
+        }
+    return AZX_OK;
 }
 
 extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
@@ -554,13 +582,7 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " AZX_PIPELINE_STAGGER=" + (e->stagger ? "1" : "0") +
                        " reserved_cus=" + std::to_string(e->reserved_cus) +
                        " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
-                       " cap=" + cap_text(e) +
-                       " resign=" + resign_text(e) +
-                       " estop=" + (e->estop_on ? "on" : "off") +
-                       " targets=" + targets_text(e) +
-                       " forced=" + forced_text(e) +
-                       " gumbel=" + gumbel_text(e) +
-                       " book=" + (d.bk_n > 0 ? std::to_string(d.bk_n) : std::string("off")) +
+                       selfplay_option_fields(e) +
                        (e->ro_R > 0 ? " eval=rollout(" + std::to_string(e->ro_R) + ")" : std::string()) +
                        "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
     snprintf(buf, (size_t)cap, "%s", text.c_str());
@@ -1623,7 +1645,7 @@ extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stat
     if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
         return fail(AZX_ESTATE, "play mode needs a device evaluator");
     memset(stats, 0, sizeof *stats);
-    CapScope cap_scope(e);
+    SelfplayScope selfplay_scope(e);
     TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 16), 1));
     TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
     CounterSnap a, b;
@@ -1670,7 +1692,7 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
                       unsigned long long *rows_out) {
     DevEngine &d = e->d;
     memset(stats, 0, sizeof *stats);
-    CapScope cap_scope(e);
+    SelfplayScope selfplay_scope(e);
     const int64_t worst = min_positions + (int64_t)d.G * d.ncells;
     TRY(play_setup(e, worst, 0));
     if (e->dbg_qcap > 0)                                // tests (azx_debug_set_queue_cap): a queue too small, so that slots get parked
@@ -2163,6 +2185,25 @@ extern "C" int azx_debug_choose(azx_engine *e, int32_t *move_id, float *moves_pr
     return AZX_OK;
 }
 
+// ---- the options' statistics: [G][count] accumulators per game (no device atomics), summed over the games here ----
+static int sum_game_counters(azx_engine *e, const unsigned long long *ctr, int count, int64_t *out, int n_out) {
+    const size_t G = e->d.G;
+    std::vector<unsigned long long> hc(G * count);
+    HIPCHECK(hipMemcpyAsync(hc.data(), ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    std::fill(out, out + n_out, (int64_t)0);
+    for (size_t g = 0; g < G; ++g)
+        for (int j = 0; j < count && j < n_out; ++j) out[j] += (int64_t)hc[g * count + j];
+    return AZX_OK;
+}
+
+// ... and zeroed, with the stream waited for, at the top of the option's setter
+static int zero_game_counters(azx_engine *e, unsigned long long *ctr, int count) {
+    HIPCHECK(hipMemsetAsync(ctr, 0, (size_t)e->d.G * count * sizeof(unsigned long long), e->stream));
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    return AZX_OK;
+}
+
 // ---- playout cap randomisation (include/azx.h; NOT the reference's behaviour) ---------------
 extern "C" int azx_playout_cap_is_full(uint64_t seed, int64_t uid, int ply, double full_prob) {
     if (!(full_prob > 0.0 && full_prob <= 1.0)) return fail(AZX_EINVAL, "full_prob %g outside (0, 1]", full_prob);
@@ -2181,9 +2222,9 @@ extern "C" int azx_set_playout_cap(azx_engine *e, double full_prob, int fast_sim
     ENGINE_GUARD(e);
     CounterSnap now;
     TRY(snap_counters(e, &now));
-    e->cap_on = !(named_clear || (full_prob == 1.0 && fast_simulations == e->cfg.simulations));
-    e->cap_full_prob = e->cap_on ? full_prob : 1.0;
-    e->cap_fast_sims = e->cap_on ? fast_simulations : 0;
+    e->opt.cap_on = !(named_clear || (full_prob == 1.0 && fast_simulations == e->cfg.simulations));
+    e->opt.cap_full_prob = e->opt.cap_on ? full_prob : 1.0;
+    e->opt.cap_fast_sims = e->opt.cap_on ? fast_simulations : 0;
     e->cap_base[0] = now.c[CTR_CAP_FULL];
     e->cap_base[1] = now.c[CTR_CAP_FAST];
     e->cap_base[2] = now.c[CTR_CAP_EMPTY];
@@ -2216,10 +2257,8 @@ extern "C" int azx_resign_is_exempt(uint64_t seed, int64_t uid, double keep_prob
 // the games in progress leave the statistics, which start again from zero
 static int resign_restart_stats(azx_engine *e) {
     azx_launch_resign_mark(e->d, e->stream);
-    HIPCHECK(hipMemsetAsync(e->d.resign_ctr, 0, (size_t)e->d.G * RS_COUNT * sizeof(unsigned long long), e->stream));
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    return AZX_OK;
+    return zero_game_counters(e, e->d.resign_ctr, RS_COUNT);
 }
 
 extern "C" int azx_set_resign(azx_engine *e, double threshold, int min_ply, double keep_prob) {
@@ -2230,34 +2269,28 @@ extern "C" int azx_set_resign(azx_engine *e, double threshold, int min_ply, doub
     if (resign_keep_problem(keep_prob)) return fail(AZX_EINVAL, "resign: keep_prob %g outside [0, 1]", keep_prob);
     ENGINE_GUARD(e);
     TRY(resign_restart_stats(e));
-    e->resign_on = true;
-    e->resign_thr = threshold;
-    e->resign_min_ply = min_ply;
-    e->resign_keep = keep_prob;
+    e->opt.resign_on = true;
+    e->opt.resign_thr = threshold;
+    e->opt.resign_min_ply = min_ply;
+    e->opt.resign_keep = keep_prob;
     return AZX_OK;
 }
 
 extern "C" int azx_clear_resign(azx_engine *e) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     ENGINE_GUARD(e);
-    e->resign_on = false;
-    e->resign_thr = -1.0;
-    e->resign_min_ply = 0;
-    e->resign_keep = 0.0;
+    e->opt.resign_on = false;
+    e->opt.resign_thr = -1.0;
+    e->opt.resign_min_ply = 0;
+    e->opt.resign_keep = 0.0;
     return AZX_OK;
 }
 
 extern "C" int azx_resign_stats(azx_engine *e, int64_t out8[8]) {
     if (!e || !out8) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    const size_t G = e->d.G;
-    std::vector<unsigned long long> hc(G * RS_COUNT);
-    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.resign_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 8; ++j) out8[j] = 0;
-    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
-        for (int j = 0; j < RS_COUNT; ++j) out8[j] += (int64_t)hc[g * RS_COUNT + j];
-    out8[7] = 0;
+    TRY(sum_game_counters(e, e->d.resign_ctr, RS_COUNT, out8, 8));
+    out8[7] = 0;                        // (reserved)
     return AZX_OK;
 }
 
@@ -2265,27 +2298,20 @@ extern "C" int azx_resign_stats(azx_engine *e, int64_t out8[8]) {
 extern "C" int azx_set_early_stop(azx_engine *e, int on) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     if (on != 0 && on != 1) return fail(AZX_EINVAL, "early stop: on must be 0 or 1, got %d", on);
-    if (on != 0 && e->gm_m != 0)
+    if (on != 0 && e->opt.gm_m != 0)
         return fail(AZX_EINVAL, "early stop: the engine has the Gumbel root search set, which does not play the PUCT visit "
                                 "leader (clear it with azx_set_gumbel(e, 0, 0, 1, 0))");
     ENGINE_GUARD(e);
-    HIPCHECK(hipMemsetAsync(e->d.estop_ctr, 0, (size_t)e->d.G * ES_COUNT * sizeof(unsigned long long), e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    e->estop_on = on != 0;
+    TRY(zero_game_counters(e, e->d.estop_ctr, ES_COUNT));
+    e->opt.estop_on = on != 0;
     return AZX_OK;
 }
 
 extern "C" int azx_early_stop_stats(azx_engine *e, int64_t out4[4]) {
     if (!e || !out4) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    const size_t G = e->d.G;
-    std::vector<unsigned long long> hc(G * ES_COUNT);
-    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.estop_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 4; ++j) out4[j] = 0;
-    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
-        for (int j = 0; j < ES_COUNT; ++j) out4[j] += (int64_t)hc[g * ES_COUNT + j];
-    out4[3] = 0;
+    TRY(sum_game_counters(e, e->d.estop_ctr, ES_COUNT, out4, 4));
+    out4[3] = 0;                        // (reserved)
     return AZX_OK;
 }
 
@@ -2297,31 +2323,24 @@ extern "C" int azx_set_train_targets(azx_engine *e, int policy_rows, float value
     if (!(value_mix >= 0.0f && value_mix <= 1.0f))      // NaN fails both comparisons
         return fail(AZX_EINVAL, "train targets: value_mix must be in [0, 1], got %g", (double)value_mix);
     ENGINE_GUARD(e);
-    HIPCHECK(hipMemsetAsync(e->d.tt_ctr, 0, (size_t)e->d.G * TT_COUNT * sizeof(unsigned long long), e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    e->tt_rows = policy_rows;
-    e->tt_mix = value_mix;
+    TRY(zero_game_counters(e, e->d.tt_ctr, TT_COUNT));
+    e->opt.tt_rows = policy_rows;
+    e->opt.tt_mix = value_mix;
     return AZX_OK;
 }
 
 extern "C" int azx_get_train_targets(azx_engine *e, int *policy_rows, float *value_mix) {
     if (!e || !policy_rows || !value_mix) return fail(AZX_EINVAL, "null argument");
-    *policy_rows = e->tt_rows;
-    *value_mix = e->tt_mix;
+    *policy_rows = e->opt.tt_rows;
+    *value_mix = e->opt.tt_mix;
     return AZX_OK;
 }
 
 extern "C" int azx_train_targets_stats(azx_engine *e, int64_t out4[4]) {
     if (!e || !out4) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    const size_t G = e->d.G;
-    std::vector<unsigned long long> hc(G * TT_COUNT);
-    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.tt_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 4; ++j) out4[j] = 0;
-    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
-        for (int j = 0; j < TT_COUNT; ++j) out4[j] += (int64_t)hc[g * TT_COUNT + j];
-    out4[3] = 0;
+    TRY(sum_game_counters(e, e->d.tt_ctr, TT_COUNT, out4, 4));
+    out4[3] = 0;                        // (reserved)
     return AZX_OK;
 }
 
@@ -2333,34 +2352,27 @@ extern "C" int azx_set_forced_playouts(azx_engine *e, float k, int prune) {
     if (prune != 0 && prune != 1) return fail(AZX_EINVAL, "forced playouts: prune must be 0 or 1, got %d", prune);
     if (k == 0.0f && prune == 1)
         return fail(AZX_EINVAL, "forced playouts: pruning needs forcing (k > 0): the prune gives back at most the forced quota");
-    if (k != 0.0f && e->gm_m != 0)
+    if (k != 0.0f && e->opt.gm_m != 0)
         return fail(AZX_EINVAL, "forced playouts: the engine has the Gumbel root search set, whose root selects are not "
                                 "PUCT's (clear it with azx_set_gumbel(e, 0, 0, 1, 0))");
     ENGINE_GUARD(e);
-    HIPCHECK(hipMemsetAsync(e->d.fp_ctr, 0, (size_t)e->d.G * FP_COUNT * sizeof(unsigned long long), e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    e->fp_k = k == 0.0f ? 0.0f : k;                     // (-0.0f is off too)
-    e->fp_prune = prune;
+    TRY(zero_game_counters(e, e->d.fp_ctr, FP_COUNT));
+    e->opt.fp_k = k == 0.0f ? 0.0f : k;                     // (-0.0f is off too)
+    e->opt.fp_prune = prune;
     return AZX_OK;
 }
 
 extern "C" int azx_get_forced_playouts(azx_engine *e, float *k, int *prune) {
     if (!e || !k || !prune) return fail(AZX_EINVAL, "null argument");
-    *k = e->fp_k;
-    *prune = e->fp_prune;
+    *k = e->opt.fp_k;
+    *prune = e->opt.fp_prune;
     return AZX_OK;
 }
 
 extern "C" int azx_forced_playouts_stats(azx_engine *e, int64_t out4[4]) {
     if (!e || !out4) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    const size_t G = e->d.G;
-    std::vector<unsigned long long> hc(G * FP_COUNT);
-    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.fp_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 4; ++j) out4[j] = 0;
-    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
-        for (int j = 0; j < FP_COUNT; ++j) out4[j] += (int64_t)hc[g * FP_COUNT + j];
+    TRY(sum_game_counters(e, e->d.fp_ctr, FP_COUNT, out4, 4));
     return AZX_OK;
 }
 
@@ -2375,43 +2387,36 @@ extern "C" int azx_set_gumbel(azx_engine *e, int m, float c_visit, float c_scale
             return fail(AZX_EINVAL, "gumbel: c_scale must be in (0, 100], got %g", (double)c_scale);
         if (improved_rows != 0 && improved_rows != 1)
             return fail(AZX_EINVAL, "gumbel: improved_rows must be 0 or 1, got %d", improved_rows);
-        if (e->fp_k > 0.0f)
+        if (e->opt.fp_k > 0.0f)
             return fail(AZX_EINVAL, "gumbel: the engine has forced playouts set, a rule about PUCT's root selects "
                                     "(clear them with azx_set_forced_playouts(e, 0, 0))");
-        if (e->estop_on)
+        if (e->opt.estop_on)
             return fail(AZX_EINVAL, "gumbel: the engine has early stop set, a rule about the PUCT visit leader "
                                     "(clear it with azx_set_early_stop(e, 0))");
     }
     ENGINE_GUARD(e);
-    HIPCHECK(hipMemsetAsync(e->d.gm_ctr, 0, (size_t)e->d.G * GM_COUNT * sizeof(unsigned long long), e->stream));
     HIPCHECK(hipMemsetAsync(e->d.gm_state, 0, (size_t)e->d.G * GM_STATE_WORDS * sizeof(uint64_t), e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    e->gm_m = m;
-    e->gm_c_visit = m ? c_visit + 0.0f : 0.0f;
-    e->gm_c_scale = m ? c_scale : 0.0f;
-    e->gm_rows = m ? improved_rows : 0;
+    TRY(zero_game_counters(e, e->d.gm_ctr, GM_COUNT));
+    e->opt.gm_m = m;
+    e->opt.gm_c_visit = m ? c_visit + 0.0f : 0.0f;
+    e->opt.gm_c_scale = m ? c_scale : 0.0f;
+    e->opt.gm_rows = m ? improved_rows : 0;
     return AZX_OK;
 }
 
 extern "C" int azx_get_gumbel(azx_engine *e, int *m, float *c_visit, float *c_scale, int *improved_rows) {
     if (!e || !m || !c_visit || !c_scale || !improved_rows) return fail(AZX_EINVAL, "null argument");
-    *m = e->gm_m;
-    *c_visit = e->gm_c_visit;
-    *c_scale = e->gm_c_scale;
-    *improved_rows = e->gm_rows;
+    *m = e->opt.gm_m;
+    *c_visit = e->opt.gm_c_visit;
+    *c_scale = e->opt.gm_c_scale;
+    *improved_rows = e->opt.gm_rows;
     return AZX_OK;
 }
 
 extern "C" int azx_gumbel_stats(azx_engine *e, int64_t out4[4]) {
     if (!e || !out4) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    const size_t G = e->d.G;
-    std::vector<unsigned long long> hc(G * GM_COUNT);
-    HIPCHECK(hipMemcpyAsync(hc.data(), e->d.gm_ctr, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 4; ++j) out4[j] = 0;
-    for (size_t g = 0; g < G; ++g)      // per-game accumulators (no device atomics): sum here
-        for (int j = 0; j < GM_COUNT; ++j) out4[j] += (int64_t)hc[g * GM_COUNT + j];
+    TRY(sum_game_counters(e, e->d.gm_ctr, GM_COUNT, out4, 4));
     return AZX_OK;
 }
 
@@ -2870,29 +2875,8 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (!m) return fail(AZX_EINVAL, "null match");
     if (first_game < 0 || n_games < 1) return fail(AZX_EINVAL, "first_game must be >= 0 and n_games >= 1");
     azx_engine *a = m->a, *b = m->b;
-    if (a->cap_on || b->cap_on)
-        return fail(AZX_EINVAL, "engine %s has a playout cap set: a match records one row per moved ply "
-                                "(clear it with azx_set_playout_cap(e, 1.0, 0))", a->cap_on ? "a" : "b");
-    if (a->resign_on || b->resign_on)
-        return fail(AZX_EINVAL, "engine %s has resignation set: a match plays every game to the end and records one "
-                                "row per moved ply (clear it with azx_clear_resign)", a->resign_on ? "a" : "b");
-    if (a->estop_on || b->estop_on)
-        return fail(AZX_EINVAL, "engine %s has early stop set: a match searches every ply in full "
-                                "(clear it with azx_set_early_stop(e, 0))", a->estop_on ? "a" : "b");
-    if (a->tt_on() || b->tt_on())
-        return fail(AZX_EINVAL, "engine %s has training targets set: a match's harvest records the reference's rows and "
-                                "the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))",
-                    a->tt_on() ? "a" : "b");
-    if (a->fp_k > 0.0f || b->fp_k > 0.0f)
-        return fail(AZX_EINVAL, "engine %s has forced playouts set: a match searches and draws every ply as the "
-                                "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", a->fp_k > 0.0f ? "a" : "b");
-    if (a->gm_m != 0 || b->gm_m != 0)
-        return fail(AZX_EINVAL, "engine %s has the Gumbel root search set: a match searches and draws every ply as the "
-                                "reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", a->gm_m != 0 ? "a" : "b");
-    if (a->d.bk_n > 0 || b->d.bk_n > 0)
-        return fail(AZX_EINVAL, "engine %s has a self-play opening book set: a match starts its games from its own book "
-                                "(azx_match_set_openings; clear the engine's with azx_set_selfplay_openings(e, 0, ...))",
-                    a->d.bk_n > 0 ? "a" : "b");
+    azx_engine *const both[2] = {a, b};
+    TRY(refuse_selfplay_options(both, 2, "match", "ab"));
     ENGINE_GUARD(a);
     if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
     if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
@@ -3152,35 +3136,7 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     if (first_game < 0 || rounds < 1 || tables_per_pair < 1)
         return fail(AZX_EINVAL, "first_game must be >= 0, rounds >= 1 and tables_per_pair >= 1");
     const int K = (int)t->eng.size(), P = n_pairs, T = tables_per_pair;
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->cap_on)
-            return fail(AZX_EINVAL, "engine %d has a playout cap set: a tournament records one row per moved ply "
-                                    "(clear it with azx_set_playout_cap(e, 1.0, 0))", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->resign_on)
-            return fail(AZX_EINVAL, "engine %d has resignation set: a tournament plays every game to the end and "
-                                    "records one row per moved ply (clear it with azx_clear_resign)", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->estop_on)
-            return fail(AZX_EINVAL, "engine %d has early stop set: a tournament searches every ply in full "
-                                    "(clear it with azx_set_early_stop(e, 0))", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->tt_on())
-            return fail(AZX_EINVAL, "engine %d has training targets set: a tournament's harvest records the reference's "
-                                    "rows and the outcome (clear them with azx_set_train_targets(e, AZX_ROWS_REFERENCE, 0))", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->fp_k > 0.0f)
-            return fail(AZX_EINVAL, "engine %d has forced playouts set: a tournament searches and draws every ply as the "
-                                    "reference does (clear them with azx_set_forced_playouts(e, 0, 0))", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->gm_m != 0)
-            return fail(AZX_EINVAL, "engine %d has the Gumbel root search set: a tournament searches and draws every ply as "
-                                    "the reference does (clear it with azx_set_gumbel(e, 0, 0, 1, 0))", k);
-    for (int k = 0; k < K; ++k)
-        if (t->eng[k]->d.bk_n > 0)
-            return fail(AZX_EINVAL, "engine %d has a self-play opening book set: a tournament starts its games from its own "
-                                    "book (azx_tournament_set_openings; clear the engine's with "
-                                    "azx_set_selfplay_openings(e, 0, ...))", k);
+    TRY(refuse_selfplay_options(t->eng.data(), K, "tournament", nullptr));
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);

@@ -564,6 +564,12 @@ class Engine:
         self._check(self.L.azx_play_steps(self.h, int(plies), C.byref(st)))
         return st.as_dict()
 
+    def _stats(self, fn, names):
+        """An option's fixed-size counters (the library fills at most 8 int64) as a dict of ints by `names`."""
+        out = np.zeros(8, np.int64)
+        check(fn(self.h, _p(out, C.c_int64)))
+        return {k: int(out[i]) for i, k in enumerate(names)}
+
     # ---- playout cap randomisation (azx_set_playout_cap; NOT the reference's behaviour) ------------
     def set_playout_cap(self, full_prob, fast_simulations):
         """azx_set_playout_cap: every ply of the following play / play_device / replay_fill / play_steps calls is with
@@ -584,9 +590,7 @@ class Engine:
     def playout_cap_stats(self):
         """azx_playout_cap_stats since the cap was last set: dict(full_plies, fast_plies, empty_games) -- empty_games
         are the finished games none of whose plies was a full search (they contributed no rows)."""
-        out = np.zeros(4, np.int64)
-        check(self.L.azx_playout_cap_stats(self.h, _p(out, C.c_int64)))
-        return dict(full_plies=int(out[0]), fast_plies=int(out[1]), empty_games=int(out[2]))
+        return self._stats(self.L.azx_playout_cap_stats, ("full_plies", "fast_plies", "empty_games"))
 
     # ---- weighted opening book of self-play (azx_set_selfplay_openings; NOT the reference's behaviour) ------------
     def set_selfplay_openings(self, openings, weights=None):
@@ -659,9 +663,7 @@ class Engine:
         dict(resigned, played_out, exempt, exempt_crossed, false_positives, sum_resign_ply, sum_plies_saved) --
         false_positives are the exempt games whose crossing mover went on to win, sum_plies_saved the plies between
         the exempt games' crossings and their ends."""
-        out = np.zeros(8, np.int64)
-        check(self.L.azx_resign_stats(self.h, _p(out, C.c_int64)))
-        return {k: int(out[i]) for i, k in enumerate(self.RESIGN_STATS)}
+        return self._stats(self.L.azx_resign_stats, self.RESIGN_STATS)
 
     # ---- early stop of decided searches (azx_set_early_stop; NOT the reference's behaviour) ------------
     def set_early_stop(self, on=True):
@@ -683,9 +685,7 @@ class Engine:
         """azx_early_stop_stats since the last set_early_stop: dict(t0_plies, stopped_plies, batches_skipped) -- the
         temperature-0 plies searched under the option, those stopped before their last batch, and the sum of the
         batches they had left."""
-        out = np.zeros(4, np.int64)
-        check(self.L.azx_early_stop_stats(self.h, _p(out, C.c_int64)))
-        return {k: int(out[i]) for i, k in enumerate(self.EARLY_STOP_STATS)}
+        return self._stats(self.L.azx_early_stop_stats, self.EARLY_STOP_STATS)
 
     # ---- training targets of the recorded rows (azx_set_train_targets; NOT the reference's behaviour) ----
     POLICY_ROWS = ("reference", "visits")      # AZX_ROWS_REFERENCE, AZX_ROWS_VISITS
@@ -726,9 +726,7 @@ class Engine:
         """azx_train_targets_stats since the last set_train_targets: dict(rows, greedy_rows, greedy_rows_wide) -- the
         rows recorded while the option is on, of those the rows of plies drawn at temperature 0, and of those the rows
         with more than one visited child (the rows that differ from the reference's)."""
-        out = np.zeros(4, np.int64)
-        check(self.L.azx_train_targets_stats(self.h, _p(out, C.c_int64)))
-        return {k: int(out[i]) for i, k in enumerate(self.TRAIN_TARGETS_STATS)}
+        return self._stats(self.L.azx_train_targets_stats, self.TRAIN_TARGETS_STATS)
 
     # ---- forced playouts and policy target pruning (azx_set_forced_playouts; NOT the reference's behaviour) ----
     def set_forced_playouts(self, k=2.0, prune=True):
@@ -770,9 +768,7 @@ class Engine:
         """azx_forced_playouts_stats since the last set_forced_playouts: dict(full_plies, forced_selects, rows_pruned,
         visits_removed) -- the full plies chosen under the option, the selects whose forced set was non-empty, the
         recorded rows with at least one reduced child and the visits removed from recorded rows."""
-        out = np.zeros(4, np.int64)
-        check(self.L.azx_forced_playouts_stats(self.h, _p(out, C.c_int64)))
-        return {k: int(out[i]) for i, k in enumerate(self.FORCED_PLAYOUTS_STATS)}
+        return self._stats(self.L.azx_forced_playouts_stats, self.FORCED_PLAYOUTS_STATS)
 
     # ---- Gumbel root search with sequential halving (azx_set_gumbel; NOT the reference's behaviour) ----
     def set_gumbel(self, m=16, c_visit=50.0, c_scale=1.0, improved_rows=True):
@@ -820,9 +816,7 @@ class Engine:
         """azx_gumbel_stats since the last set_gumbel: dict(plies, halvings, root_selects, improved_rows) -- the plies
         chosen under the option, the halvings performed, the root selects made under the option and the rows recorded
         as the improved policy."""
-        out = np.zeros(4, np.int64)
-        check(self.L.azx_gumbel_stats(self.h, _p(out, C.c_int64)))
-        return {k: int(out[i]) for i, k in enumerate(self.GUMBEL_STATS)}
+        return self._stats(self.L.azx_gumbel_stats, self.GUMBEL_STATS)
 
     def gumbel_state(self):
         """azx_gumbel_state: (candidates, survivors), two uint64[n_games, 3] arrays of bit masks by child index (bit

@@ -34,6 +34,9 @@ from .play_game import play_game
 from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags  # noqa: F401
 from .rollout import is_rollout_net, register_evaluator
 from .replay_buffer import ReplayDataFrame
+from .selfplay_options import (BY_NAME, GUMBEL_DEFAULT, OPTIONS, normalize_early_stop,  # noqa: F401 (re-exported)
+                               normalize_forced_playouts, normalize_gumbel, normalize_playout_cap, normalize_resign,
+                               normalize_selfplay_openings, normalize_train_targets)
 
 Metrics = Dict[str, float]
 
@@ -190,13 +193,11 @@ class Player:
                              "through the host loop, which does not reflect")
         self._engine_flags = _eng.FLAG_RANDOM_REFLECT if self.random_reflect else 0
         self._check_tower_precision()
-        self.playout_cap = self._check_playout_cap(playout_cap)
-        self.resign = self._check_resign(resign)
-        self.early_stop = self._check_early_stop(early_stop)
-        self.train_targets = self._check_train_targets(train_targets)
-        self.forced_playouts = self._check_forced_playouts(forced_playouts)
-        self.gumbel = self._check_gumbel(gumbel)
-        self.selfplay_openings = self._check_selfplay_openings(selfplay_openings, selfplay_opening_weights)
+        given = dict(selfplay_openings=selfplay_openings, selfplay_opening_weights=selfplay_opening_weights,
+                     playout_cap=playout_cap, resign=resign, early_stop=early_stop, train_targets=train_targets,
+                     forced_playouts=forced_playouts, gumbel=gumbel)
+        for opt in OPTIONS:             # self.playout_cap ... self.selfplay_openings: normalised, or off
+            setattr(self, opt.name, self._check_option(opt, *(given[k] for k in opt.keywords)))
         self._match = None             # device_match: (engine a, engine b, engine.Match)
         self._match_next = 0           # ... the first game index of the next chunk: no game index repeats
         self.role = role if (gather and azdist.is_distributed()) else None
@@ -331,167 +332,62 @@ class Player:
                 raise ValueError("agent %d asks for tower_precision='f16', but these games run through the host loop, "
                                  "which does not launch the device tower" % i)
 
-    def _check_playout_cap(self, cap):
-        """`playout_cap` as (full_prob, fast_simulations), or None; a ValueError naming what does not hold."""
-        if cap is None:
-            return None
-        full_prob, fast = normalize_playout_cap(cap)
+    def _check_option(self, opt, *given):
+        """One entry of selfplay_options.OPTIONS as this Player keeps it -- normalised, or opt.off -- or a ValueError
+        naming what does not hold: the normaliser's, "a self-play option" under device_match, an option it excludes,
+        "needs a device engine" where the host loop plays, and what the entry's own hooks hold.  No GPU needed."""
+        if opt.given is not None:
+            value = opt.given(*given)
+        else:
+            value = opt.off if given[0] is None else opt.normalize(given[0])
+        if not opt.is_on(value):
+            return opt.off
         if self.device_match:
-            raise ValueError("playout_cap is a self-play option: a device match records one row per moved ply "
-                             "(engine.Match refuses an engine with a cap)")
+            raise ValueError("%s is a self-play option: %s" % (opt.name, opt.match_reason))
+        other = opt.excluded_by(value, vars(self))
+        if other is not None:
+            raise ValueError(opt.exclusion_text(other))
+        if opt.requires is not None:
+            opt.requires(self)
         pol = self._external_policy() if self.external_batch else self._device_policy()
         if pol is None:
-            raise ValueError("playout_cap needs the games to run in a device engine (a single agent whose Policy "
-                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
-                             "which searches every ply in full")
-        if fast > pol.simulations:
-            raise ValueError("playout_cap: fast_simulations %d above the policy's simulations %d" % (fast, pol.simulations))
-        return full_prob, fast
+            raise ValueError("%s needs the games to run in a device engine (a single agent whose Policy holds a "
+                             "HexNetwork, or external_batch=True): these agents play through the host loop, which %s"
+                             % (opt.name, opt.host_reason))
+        return value if opt.fits is None else opt.fits(self, value, pol)
 
-    def _check_resign(self, resign):
-        """`resign` as (threshold, min_ply, keep_prob), or None; a ValueError naming what does not hold."""
-        if resign is None:
+    def _option_stats(self, name):
+        """The option's Engine stats of the self-play engine, or None while there is none or the option is not set."""
+        opt = BY_NAME[name]
+        if not opt.is_on(getattr(self, name)) or self._engine is None:
             return None
-        resign = normalize_resign(resign)
-        if self.device_match:
-            raise ValueError("resign is a self-play option: a device match plays every game to the end "
-                             "(engine.Match refuses an engine with resignation set)")
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("resign needs the games to run in a device engine (a single agent whose Policy holds a "
-                             "HexNetwork, or external_batch=True): these agents play through the host loop, which "
-                             "plays every game to the end")
-        return resign
-
-    def _check_early_stop(self, early_stop):
-        """`early_stop` as a bool; a ValueError naming what does not hold."""
-        early_stop = normalize_early_stop(early_stop)
-        if not early_stop:
-            return False
-        if self.device_match:
-            raise ValueError("early_stop is a self-play option: a device match searches every ply in full "
-                             "(engine.Match refuses an engine with early stop set)")
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("early_stop needs the games to run in a device engine (a single agent whose Policy holds "
-                             "a HexNetwork, or external_batch=True): these agents play through the host loop, which "
-                             "runs every search to its last simulation")
-        return True
-
-    def _check_train_targets(self, train_targets):
-        """`train_targets` as a (policy_rows, value_mix) pair, or None for off; a ValueError naming what does not hold."""
-        train_targets = normalize_train_targets(train_targets)
-        if train_targets is None:
-            return None
-        if self.device_match:
-            raise ValueError("train_targets is a self-play option: a device match's harvest records the reference's "
-                             "rows and the outcome (engine.Match refuses an engine with training targets set)")
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("train_targets needs the games to run in a device engine (a single agent whose Policy "
-                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
-                             "which records the reference's rows and the outcome")
-        return train_targets
-
-    def _check_forced_playouts(self, forced_playouts):
-        """`forced_playouts` as a (k, prune) pair, or None for off; a ValueError naming what does not hold."""
-        forced_playouts = normalize_forced_playouts(forced_playouts)
-        if forced_playouts is None:
-            return None
-        if self.device_match:
-            raise ValueError("forced_playouts is a self-play option: a device match searches and draws every ply as "
-                             "the reference does (engine.Match refuses an engine with forced playouts set)")
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("forced_playouts needs the games to run in a device engine (a single agent whose Policy "
-                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
-                             "which selects by PUCT alone and records every visit")
-        return forced_playouts
-
-    def _check_gumbel(self, gumbel):
-        """`gumbel` as an (m, c_visit, c_scale, improved_rows) tuple, or None for off; a ValueError naming what does not
-        hold."""
-        gumbel = normalize_gumbel(gumbel)
-        if gumbel is None:
-            return None
-        if self.device_match:
-            raise ValueError("gumbel is a self-play option: a device match searches and draws every ply as the "
-                             "reference does (engine.Match refuses an engine with the Gumbel root search set)")
-        if self.forced_playouts is not None or self.early_stop:
-            raise ValueError("gumbel cannot be set together with %s: that option is a rule about PUCT visit leaders, "
-                             "which a Gumbel root search does not play"
-                             % ("forced_playouts" if self.forced_playouts is not None else "early_stop"))
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("gumbel needs the games to run in a device engine (a single agent whose Policy holds a "
-                             "HexNetwork, or external_batch=True): these agents play through the host loop, which "
-                             "selects by PUCT and draws from the visit counts")
-        return gumbel
-
-    def _check_selfplay_openings(self, openings, weights):
-        """`selfplay_openings` as a (book, weights or None) pair, or None for off; a ValueError naming what does not
-        hold."""
-        if openings is None:
-            if weights is not None:
-                raise ValueError("selfplay_opening_weights given without selfplay_openings")
-            return None
-        if self.device_match:
-            raise ValueError("selfplay_openings is a self-play option: a device match starts its games from its own "
-                             "book (use openings=; engine.Match refuses an engine with a self-play book)")
-        if len(self.agents) != 1:
-            raise ValueError("selfplay_openings is a self-play option: it needs a single agent, got %d (two agents play "
-                             "through the host loop or, with device_match=True, a device match)" % len(self.agents))
-        pol = self._external_policy() if self.external_batch else self._device_policy()
-        if pol is None:
-            raise ValueError("selfplay_openings needs the games to run in a device engine (a single agent whose Policy "
-                             "holds a HexNetwork, or external_batch=True): these agents play through the host loop, "
-                             "which starts every game from the empty board")
-        n = self.agents[0].game.board_size
-        book, w = normalize_selfplay_openings(openings, n)
-        if weights is not None:
-            if w is not None:
-                raise ValueError("selfplay_openings: weights given twice (in the book's dict and as selfplay_opening_weights)")
-            book, w = normalize_selfplay_openings({"book": book, "weights": weights}, n)
-        _eng.openings_check(n, book)
-        return book, w
+        return getattr(self._engine, opt.stats)()
 
     def opening_stats(self):
         """Engine.selfplay_openings_stats() of the self-play engine, or None while there is none or selfplay_openings
         is not set."""
-        if self.selfplay_openings is None or self._engine is None:
-            return None
-        return self._engine.selfplay_openings_stats()
+        return self._option_stats("selfplay_openings")
 
     def gumbel_stats(self):
         """Engine.gumbel_stats() of the self-play engine, or None while there is none or gumbel is not set."""
-        if self.gumbel is None or self._engine is None:
-            return None
-        return self._engine.gumbel_stats()
+        return self._option_stats("gumbel")
 
     def forced_playouts_stats(self):
         """Engine.forced_playouts_stats() of the self-play engine, or None while there is none or forced_playouts is
         not set."""
-        if self.forced_playouts is None or self._engine is None:
-            return None
-        return self._engine.forced_playouts_stats()
+        return self._option_stats("forced_playouts")
 
     def train_targets_stats(self):
         """Engine.train_targets_stats() of the self-play engine, or None while there is none or train_targets is not set."""
-        if self.train_targets is None or self._engine is None:
-            return None
-        return self._engine.train_targets_stats()
+        return self._option_stats("train_targets")
 
     def early_stop_stats(self):
         """Engine.early_stop_stats() of the self-play engine, or None while there is none or early_stop is not set."""
-        if not self.early_stop or self._engine is None:
-            return None
-        return self._engine.early_stop_stats()
+        return self._option_stats("early_stop")
 
     def resign_stats(self):
         """Engine.resign_stats() of the self-play engine, or None while there is none or resign is not set."""
-        if self.resign is None or self._engine is None:
-            return None
-        return self._engine.resign_stats()
+        return self._option_stats("resign")
 
     def _external_policy(self) -> Policy:
         """The Policy whose duck-typed net evaluates the pool's leaf batches (external_batch=True); a ValueError
@@ -623,20 +519,8 @@ class Player:
                 num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                 flags=self._engine_flags | tower_flags(pol),
                 device=device, seed=self._seed_base, game_index_stride=world, game_index_offset=rank)
-            if self.selfplay_openings is not None:      # before any play: generation 0 follows the book too
-                self._engine.set_selfplay_openings(*self.selfplay_openings)
-            if self.playout_cap is not None:
-                self._engine.set_playout_cap(*self.playout_cap)
-            if self.resign is not None:
-                self._engine.set_resign(*self.resign)
-            if self.early_stop:
-                self._engine.set_early_stop(True)
-            if self.train_targets is not None:
-                self._engine.set_train_targets(*self.train_targets)
-            if self.forced_playouts is not None:
-                self._engine.set_forced_playouts(*self.forced_playouts)
-            if self.gumbel is not None:
-                self._engine.set_gumbel(*self.gumbel)
+            for opt in OPTIONS:          # (the book first, before any play: generation 0 follows it too)
+                opt.apply(self._engine, getattr(self, opt.name))
             self._engine_key = key
         return self._engine
 
@@ -752,247 +636,6 @@ class Player:
             eng.set_weights({k: (v.contiguous().data_ptr(), v.numel()) for k, v in sd.items()}, on_device=True)
         else:
             eng.set_weights({k: v.detach().cpu().numpy() for k, v in sd.items()})
-
-
-def normalize_playout_cap(cap):
-    """(full_prob, fast_simulations) of a pair or of a {"full_prob": ..., "fast_simulations": ...} mapping; a
-    ValueError unless full_prob is in (0, 1] and fast_simulations a whole number >= 1."""
-    try:
-        if isinstance(cap, dict):
-            if set(cap) != {"full_prob", "fast_simulations"}:
-                raise ValueError
-            full_prob, fast = cap["full_prob"], cap["fast_simulations"]
-        else:
-            full_prob, fast = cap
-        full_prob = float(full_prob)
-        if isinstance(fast, bool) or int(fast) != fast:
-            raise ValueError
-        fast = int(fast)
-    except (TypeError, ValueError, KeyError):
-        raise ValueError("playout_cap must be (full_prob, fast_simulations) or a dict with exactly these two keys, "
-                         "got %r" % (cap,)) from None
-    if not 0.0 < full_prob <= 1.0:
-        raise ValueError("playout_cap: full_prob %r outside (0, 1]" % full_prob)
-    if fast < 1:
-        raise ValueError("playout_cap: fast_simulations %d below 1" % fast)
-    return full_prob, fast
-
-
-def normalize_selfplay_openings(spec, board_size=None):
-    """(book, weights) of a self-play opening book -- book a list of move lists (tile + 1 in play order), weights a list
-    of floats or None for uniform -- or None for None.  Accepted: a list of move lists; {"book": [...]} with an optional
-    "weights": [...]; {"all": 1 | 2} for engine.all_openings(board_size, plies) (needs `board_size`); and in a dict an
-    optional "empty_share": s in [0, 1], which puts the empty opening first with weight s and gives the others 1 - s in
-    equal parts (not together with "weights").  A ValueError for anything else: unknown keys, both or neither of "book"
-    and "all", an empty book, moves that are not whole numbers, weights of another length, or negative, non-finite or
-    all zero.  The rules themselves (moves on the board, no tile twice, undecided) are engine.openings_check's."""
-    if spec is None:
-        return None
-    what = "selfplay_openings"
-    weights, share = None, None
-    if isinstance(spec, dict):
-        extra = set(spec) - {"book", "weights", "all", "empty_share"}
-        if extra:
-            raise ValueError("%s as a dict takes the keys 'book', 'weights', 'all' and 'empty_share', got %r"
-                             % (what, sorted(map(str, spec))))
-        if ("book" in spec) == ("all" in spec):
-            raise ValueError("%s as a dict needs exactly one of 'book' and 'all'" % what)
-        if "all" in spec:
-            plies = spec["all"]
-            if isinstance(plies, bool) or plies not in (1, 2):
-                raise ValueError("%s: 'all' must be 1 or 2 (plies), got %r" % (what, plies))
-            if board_size is None:
-                raise ValueError("%s: 'all' needs the board size" % what)
-            book = _eng.all_openings(int(board_size), int(plies))
-        else:
-            book = spec["book"]
-        weights, share = spec.get("weights"), spec.get("empty_share")
-    else:
-        book = spec
-    try:
-        if isinstance(book, (str, bytes, dict)):
-            raise TypeError
-        book = [list(o) for o in book]
-        for o in book:
-            for m in o:
-                if isinstance(m, bool) or int(m) != m:
-                    raise ValueError
-        book = [[int(m) for m in o] for o in book]
-    except (TypeError, ValueError):
-        raise ValueError("%s: the book must be a list of move lists (whole numbers, tile + 1 in play order), got %r"
-                         % (what, spec)) from None
-    if not book:
-        raise ValueError("%s: the book is empty (leave the option out to play from the empty board)" % what)
-    if share is not None:
-        if weights is not None:
-            raise ValueError("%s: 'empty_share' and 'weights' cannot be given together" % what)
-        if isinstance(share, bool) or not isinstance(share, (int, float, np.integer, np.floating)) \
-                or not 0.0 <= float(share) <= 1.0:
-            raise ValueError("%s: empty_share must be a number in [0, 1], got %r" % (what, share))
-        share = float(share)
-        weights = [share] + [(1.0 - share) / len(book)] * len(book)
-        book = [[]] + book
-    if weights is not None:
-        try:
-            if isinstance(weights, (str, bytes, dict)):
-                raise TypeError
-            weights = [float(w) for w in weights]
-        except (TypeError, ValueError):
-            raise ValueError("%s: weights must be a list of numbers, got %r" % (what, weights)) from None
-        if len(weights) != len(book):
-            raise ValueError("%s: %d weights for %d openings" % (what, len(weights), len(book)))
-        if any(not np.isfinite(w) or w < 0.0 for w in weights):
-            raise ValueError("%s: weights must be finite and >= 0, got %r" % (what, weights))
-        if not sum(weights) > 0.0:
-            raise ValueError("%s: the weights are all zero" % what)
-    return book, weights
-
-
-def normalize_train_targets(train_targets):
-    """(policy_rows, value_mix) of "visits" (= ("visits", 0.0)), of a pair or of a {"policy_rows": ..., "value_mix": ...}
-    mapping; None for None / False and for the pair that is "off", ("reference", 0.0).  A ValueError unless policy_rows
-    is "reference" or "visits" and value_mix a number in [0, 1]."""
-    if train_targets is None or train_targets is False:
-        return None
-    if isinstance(train_targets, str):
-        if train_targets != "visits":
-            raise ValueError("train_targets must be 'visits', a (policy_rows, value_mix) pair or a dict with those "
-                             "keys, got %r" % (train_targets,))
-        return "visits", 0.0
-    if isinstance(train_targets, dict):
-        if set(train_targets) != {"policy_rows", "value_mix"}:
-            raise ValueError("train_targets as a dict needs exactly the keys 'policy_rows' and 'value_mix', got %r"
-                             % (sorted(map(str, train_targets)),))
-        rows, mix = train_targets["policy_rows"], train_targets["value_mix"]
-    elif isinstance(train_targets, (tuple, list)) and len(train_targets) == 2:
-        rows, mix = train_targets
-    else:
-        raise ValueError("train_targets must be 'visits', a (policy_rows, value_mix) pair or a dict with those keys, "
-                         "got %r" % (train_targets,))
-    if rows not in ("reference", "visits"):
-        raise ValueError("train_targets: policy_rows must be 'reference' or 'visits', got %r" % (rows,))
-    if isinstance(mix, (bool, np.bool_)) or not isinstance(mix, (int, float, np.integer, np.floating)):
-        raise ValueError("train_targets: value_mix must be a number in [0, 1], got %r" % (mix,))
-    mix = float(mix)
-    if not 0.0 <= mix <= 1.0:                  # (NaN fails both comparisons)
-        raise ValueError("train_targets: value_mix must be in [0, 1], got %r" % (mix,))
-    if rows == "reference" and mix == 0.0:
-        return None
-    return rows, mix
-
-
-def normalize_forced_playouts(forced_playouts):
-    """(k, prune) of True (= (2.0, True)), a pair or a {"k": ..., "prune": ...} mapping, or None for off (None, False,
-    (0, False)); a ValueError unless k is a number in [0, 64], prune a bool, and k > 0 where prune is set."""
-    if forced_playouts is None or forced_playouts is False:
-        return None
-    if forced_playouts is True:
-        return 2.0, True
-    if isinstance(forced_playouts, dict):
-        if set(forced_playouts) != {"k", "prune"}:
-            raise ValueError("forced_playouts as a dict needs exactly the keys 'k' and 'prune', got %r"
-                             % (sorted(map(str, forced_playouts)),))
-        k, prune = forced_playouts["k"], forced_playouts["prune"]
-    elif isinstance(forced_playouts, (tuple, list)) and len(forced_playouts) == 2:
-        k, prune = forced_playouts
-    else:
-        raise ValueError("forced_playouts must be True, a (k, prune) pair or a dict with those keys, got %r"
-                         % (forced_playouts,))
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, float, np.integer, np.floating)):
-        raise ValueError("forced_playouts: k must be a number in [0, 64], got %r" % (k,))
-    k = float(k)
-    if not 0.0 <= k <= 64.0:                        # NaN fails both comparisons
-        raise ValueError("forced_playouts: k must be in [0, 64], got %r" % (k,))
-    if not isinstance(prune, (bool, np.bool_)):
-        raise ValueError("forced_playouts: prune must be True or False, got %r" % (prune,))
-    if k == 0.0:
-        if prune:
-            raise ValueError("forced_playouts: pruning needs forcing (k > 0), got k = 0 with prune = True")
-        return None
-    return k, bool(prune)
-
-
-GUMBEL_DEFAULT = (16, 50.0, 1.0, True)
-
-
-def normalize_gumbel(gumbel):
-    """(m, c_visit, c_scale, improved_rows) of True (= (16, 50.0, 1.0, True)), an int m, an (m, c_visit, c_scale)
-    triple or a mapping with the keys "m", "c_visit", "c_scale", "improved_rows" (any subset: the rest default), or None
-    for off (None, False, m = 0); a ValueError unless m is an int in [2, 64], c_visit a number in [0, 1e4], c_scale a
-    number in (0, 100] and improved_rows a bool.  The defaults 50 and 1.0 are the author's recollection of the paper's
-    board-game values and are not checked here."""
-    if gumbel is None or gumbel is False:
-        return None
-    m, c_visit, c_scale, rows = GUMBEL_DEFAULT
-    if gumbel is True:
-        pass
-    elif isinstance(gumbel, dict):
-        extra = set(gumbel) - {"m", "c_visit", "c_scale", "improved_rows"}
-        if extra:
-            raise ValueError("gumbel as a dict takes the keys 'm', 'c_visit', 'c_scale' and 'improved_rows', got %r"
-                             % (sorted(map(str, gumbel)),))
-        m, c_visit = gumbel.get("m", m), gumbel.get("c_visit", c_visit)
-        c_scale, rows = gumbel.get("c_scale", c_scale), gumbel.get("improved_rows", rows)
-    elif isinstance(gumbel, (tuple, list)) and len(gumbel) == 3:
-        m, c_visit, c_scale = gumbel
-    elif isinstance(gumbel, (int, np.integer)):
-        m = gumbel
-    else:
-        raise ValueError("gumbel must be True, an int m, an (m, c_visit, c_scale) triple or a dict with those keys, "
-                         "got %r" % (gumbel,))
-    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)):
-        raise ValueError("gumbel: m must be an int in [2, 64] (0 is off), got %r" % (m,))
-    m = int(m)
-    if m == 0:
-        return None
-    if not 2 <= m <= 64:
-        raise ValueError("gumbel: m must be in [2, 64] (0 is off), got %r" % (m,))
-    for name, v in (("c_visit", c_visit), ("c_scale", c_scale)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("gumbel: %s must be a number, got %r" % (name, v))
-    c_visit, c_scale = float(c_visit), float(c_scale)
-    if not 0.0 <= c_visit <= 1.0e4:                  # NaN fails both comparisons
-        raise ValueError("gumbel: c_visit must be in [0, 1e4], got %r" % (c_visit,))
-    if not 0.0 < c_scale <= 100.0:
-        raise ValueError("gumbel: c_scale must be in (0, 100], got %r" % (c_scale,))
-    if not isinstance(rows, (bool, np.bool_)):
-        raise ValueError("gumbel: improved_rows must be True or False, got %r" % (rows,))
-    return m, c_visit, c_scale, bool(rows)
-
-
-def normalize_early_stop(early_stop):
-    """`early_stop` as a bool; a ValueError for anything but True / False (None counts as False)."""
-    if early_stop is None:
-        return False
-    if not isinstance(early_stop, (bool, np.bool_)):
-        raise ValueError("early_stop must be True or False, got %r" % (early_stop,))
-    return bool(early_stop)
-
-
-def normalize_resign(resign):
-    """(threshold, min_ply, keep_prob) of a triple or of a {"threshold": ..., "min_ply": ..., "keep_prob": ...}
-    mapping; a ValueError unless threshold is in [-1, 1], min_ply a whole number >= 0 and keep_prob in [0, 1]."""
-    try:
-        if isinstance(resign, dict):
-            if set(resign) != {"threshold", "min_ply", "keep_prob"}:
-                raise ValueError
-            thr, min_ply, keep = resign["threshold"], resign["min_ply"], resign["keep_prob"]
-        else:
-            thr, min_ply, keep = resign
-        thr, keep = float(thr), float(keep)
-        if isinstance(min_ply, bool) or int(min_ply) != min_ply:
-            raise ValueError
-        min_ply = int(min_ply)
-    except (TypeError, ValueError, KeyError):
-        raise ValueError("resign must be (threshold, min_ply, keep_prob) or a dict with exactly these three keys, "
-                         "got %r" % (resign,)) from None
-    if not -1.0 <= thr <= 1.0:              # (false for NaN)
-        raise ValueError("resign: threshold %r outside [-1, 1]" % thr)
-    if min_ply < 0:
-        raise ValueError("resign: min_ply %d is negative" % min_ply)
-    if not 0.0 <= keep <= 1.0:
-        raise ValueError("resign: keep_prob %r outside [0, 1]" % keep)
-    return thr, min_ply, keep
 
 
 def _net_device(net) -> torch.device:

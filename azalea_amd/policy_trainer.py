@@ -398,43 +398,8 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     that fills the first buffer does NOT get it.  One log line says whether it is on.  A ValueError, before anything is
     built, for anything normalize_selfplay_openings or the rules refuse; Player refuses it where the games would run
     through the host loop.  Its effect on playing strength and on training efficiency is NOT measured."""
-    from .parallel_player import (normalize_early_stop, normalize_train_targets, normalize_forced_playouts, normalize_gumbel,
-                                  normalize_selfplay_openings)
-    try:
-        selfplay_openings = normalize_selfplay_openings(config.get("selfplay_openings"), config.get("board_size"))
-    except ValueError as exc:
-        raise ValueError("config['selfplay_openings']: %s" % exc) from None
-    try:
-        gumbel = normalize_gumbel(config.get("gumbel"))
-    except ValueError as exc:
-        raise ValueError("config['gumbel']: %s" % exc) from None
-    try:
-        forced_playouts = normalize_forced_playouts(config.get("forced_playouts"))
-    except ValueError as exc:
-        raise ValueError("config['forced_playouts']: %s" % exc) from None
-    try:
-        train_targets = normalize_train_targets(config.get("train_targets"))
-    except ValueError as exc:
-        raise ValueError("config['train_targets']: %s" % exc) from None
-    try:
-        early_stop = normalize_early_stop(config.get("early_stop"))
-    except ValueError as exc:
-        raise ValueError("config['early_stop']: %s" % exc) from None
-    if gumbel is not None and (forced_playouts is not None or early_stop):
-        raise ValueError("config['gumbel']: gumbel cannot be set together with config['%s']: that option is a rule about "
-                         "PUCT visit leaders, which a Gumbel root search does not play"
-                         % ("forced_playouts" if forced_playouts is not None else "early_stop"))
-    resign = None
-    if config.get("resign") is not None:
-        from .parallel_player import normalize_resign
-        resign = normalize_resign(config["resign"])
-    playout_cap = None
-    if config.get("playout_cap") is not None:
-        from .parallel_player import normalize_playout_cap
-        playout_cap = normalize_playout_cap(config["playout_cap"])
-        if playout_cap[1] > policy.simulations:
-            raise ValueError("config['playout_cap']: fast_simulations %d above simulations %d"
-                             % (playout_cap[1], policy.simulations))
+    from .selfplay_options import from_config
+    option_keywords, option_lines = from_config(config, policy)
     apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])
@@ -471,46 +436,10 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     lockstep_role = ("leader" if leader else "follower") if mode == "lockstep" else None
     player = Player(None, [agent], n_games=config.get("selfplay_games"), role=lockstep_role,
                     external_batch=bool(config.get("selfplay_external_batch", False)),
-                    random_reflect=bool(config.get("random_reflect", False)), playout_cap=playout_cap,
-                    resign=resign, early_stop=early_stop, train_targets=train_targets,
-                    forced_playouts=forced_playouts, gumbel=gumbel,
-                    selfplay_openings=None if selfplay_openings is None else selfplay_openings[0],
-                    selfplay_opening_weights=None if selfplay_openings is None else selfplay_openings[1])
+                    random_reflect=bool(config.get("random_reflect", False)), **option_keywords)
     if leader:
-        logging.info("self-play opening book (config['selfplay_openings']): %s",
-                     "off" if selfplay_openings is None else
-                     "on -- NOT the reference's behaviour: every game starts from one of %d openings, %s, drawn on the "
-                     "device from its uid" % (len(selfplay_openings[0]),
-                                              "uniform" if selfplay_openings[1] is None else "weighted"))
-    if leader:
-        logging.info("Gumbel root search (config['gumbel']): %s",
-                     "off" if gumbel is None else
-                     "on -- NOT the reference's behaviour: m = %d, c_visit = %g, c_scale = %g, rows = %s"
-                     % (gumbel[0], gumbel[1], gumbel[2], "the improved policy" if gumbel[3] else "from the visit counts"))
-    if leader:
-        logging.info("forced playouts (config['forced_playouts']): %s",
-                     "off" if forced_playouts is None else
-                     "on -- NOT the reference's behaviour: k = %g, policy target pruning %s"
-                     % (forced_playouts[0], "on" if forced_playouts[1] else "off"))
-    if leader:
-        logging.info("training targets (config['train_targets']): %s",
-                     "off" if train_targets is None else
-                     "on -- NOT the reference's behaviour: policy rows '%s', reward (1 - %g) * z + %g * v"
-                     % (train_targets[0], train_targets[1], train_targets[1]))
-    if leader:
-        logging.info("early stop (config['early_stop']): %s",
-                     "on -- NOT the reference's behaviour: a search drawn at temperature 0 stops once its leading root "
-                     "child cannot be caught" if early_stop else "off")
-    if leader:
-        logging.info("resignation (config['resign']): %s",
-                     "off" if resign is None else
-                     "on -- NOT the reference's behaviour: the mover resigns below a root value of %g from ply %d on; "
-                     "a share %g of the games is exempt and measures the false positives" % resign)
-    if leader:
-        logging.info("playout cap randomisation (config['playout_cap']): %s",
-                     "off" if playout_cap is None else
-                     "on -- NOT the reference's behaviour: a ply is a full search with probability %g, else %d "
-                     "simulations without noise and without a training row" % playout_cap)
+        for line in option_lines:
+            logging.info(line)
     if mode == "actor_learner" and player._device_policy() is None:
         raise ValueError("selfplay_mode 'actor_learner' needs a Policy that holds a HexNetwork; use 'lockstep'")
     from_ring = False
@@ -643,7 +572,7 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
                 if ahead is not None:
                     ahead.after_step()
                 refilled = replaybuf.consume(batch_size / oversampling, player)
-                if refilled and resign is not None and leader and ahead is None:
+                if refilled and option_keywords["resign"] is not None and leader and ahead is None:
                     log_resign(player)
                 if config.get("log_interval") and step % config["log_interval"] == 0:
                     if loss_dev is not None:
@@ -671,7 +600,7 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     if ahead is not None:
         ahead.stop()
         replaybuf.ahead = None
-        if resign is not None and leader:
+        if option_keywords["resign"] is not None and leader:
             log_resign(player)
         if history is not None:
             history["play_ahead"] = ahead.counters()

@@ -15,6 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import early_stop_reference as ref  # noqa: E402
+from option_api_stubs import _Agent, _RandomAgent, _cpu_policy, no_engines  # noqa: E402,F401
 
 NEW_SYMBOLS = ("azx_set_early_stop", "azx_early_stop_stats")
 
@@ -76,41 +77,7 @@ def test_the_python_surface():
     assert 'config["early_stop"]' in policy_trainer.train.__doc__
 
 
-# ---- Player and train: the refusal comes before anything touches a GPU (the stubs of test_playout_cap_api.py) -------
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
-
-
-class _RandomAgent:
-    def __init__(self, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.game = HexGame(n)
-
-
-def _cpu_policy():
-    from azalea_amd.policy import Policy
-    p = Policy()
-    p.initialize(dict(device="cpu", network="HexNetwork", board_size=5, num_blocks=1, base_chans=32, **SEARCH))
-    return p
-
-
-@pytest.fixture
-def no_engines(monkeypatch):
-    from azalea_amd import engine
-
-    def refuse(*a, **kw):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", refuse)
-    monkeypatch.setattr(engine, "Match", refuse)
-
-
+# ---- Player and train: the refusal comes before anything touches a GPU (the stubs of tests/option_api_stubs.py) -------
 def test_player_takes_the_option_for_device_self_play_and_refuses_it_elsewhere(no_engines):
     from azalea_amd.parallel_player import Player
     a, b = _Agent(_cpu_policy()), _Agent(_cpu_policy())

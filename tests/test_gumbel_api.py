@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import forced_playouts_reference as fp  # noqa: E402
 import gumbel_reference as ref  # noqa: E402
+from option_api_stubs import _Agent, _RandomAgent, _cpu_policy  # noqa: E402,F401
 
 NEW_SYMBOLS = ("azx_set_gumbel", "azx_get_gumbel", "azx_gumbel_stats", "azx_gumbel_variate", "azx_selftest_gumbel",
                "azx_gumbel_state")
@@ -120,30 +121,6 @@ def test_normalize_gumbel():
 
 
 # ---- Player, evaluate_throughput and train: the refusal comes before anything touches a GPU --------------------------
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
-
-
-class _RandomAgent:
-    def __init__(self, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.game = HexGame(n)
-
-
-def _cpu_policy():
-    from azalea_amd.policy import Policy
-    p = Policy()
-    p.initialize(dict(device="cpu", network="HexNetwork", board_size=5, num_blocks=1, base_chans=32, **SEARCH))
-    return p
-
-
 @pytest.fixture
 def no_engines(monkeypatch):
     from azalea_amd import engine

@@ -12,6 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import _Agent  # noqa: E402,F401
 MATCH_SYMBOLS = ("azx_match_create", "azx_match_destroy", "azx_match_play")
 
 
@@ -66,13 +67,6 @@ def test_match_create_rejects_null_engines():
     assert L.azx_last_error()
     assert L.azx_match_play(None, 0, 1, None, None, None, None) == -1
     L.azx_match_destroy(None)                                        # a null match is ignored
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
 
 
 def test_evaluate_throughput_rejects_agents_without_a_device_network():

@@ -4,19 +4,14 @@ The games themselves are tests/test_gpu_match_external.py's."""
 import inspect
 import os
 import re
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import SEARCH, _Agent, no_engines  # noqa: E402,F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
 
 
 def _hex_policy():
@@ -43,17 +38,6 @@ def _custom_policy():
     p.net = Custom()
     assert isinstance(p, Policy) and not p._uses_device_net()
     return p
-
-
-@pytest.fixture
-def no_engines(monkeypatch):
-    """Any attempt to create an engine or a match fails the test: the checks come before."""
-    from azalea_amd import engine
-
-    def refuse(*a, **kw):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", refuse)
-    monkeypatch.setattr(engine, "Match", refuse)
 
 
 def test_external_batch_is_a_keyword_of_evaluate_throughput_and_off_by_default():

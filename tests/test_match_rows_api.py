@@ -5,15 +5,17 @@ import ctypes as C
 import inspect
 import os
 import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import _Agent, _cpu_policy, no_engines  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("azx_match_set_harvest", "azx_match_set_first_mover", "azx_match_rows", "azx_tournament_set_harvest",
                "azx_tournament_set_first_mover", "azx_tournament_rows", "azx_rows_read")
 EINVAL = -1
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
 
 
 def header():
@@ -77,30 +79,6 @@ def test_the_header_says_what_a_match_does_to_the_queues_and_in_what_order_rows_
 
 
 # ---- the two-agent device Player: every refusal comes before anything touches a GPU -----------------------------
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
-
-
-def _cpu_policy():
-    from azalea_amd.policy import Policy
-    p = Policy()
-    p.initialize(dict(device="cpu", network="HexNetwork", board_size=5, num_blocks=1, base_chans=32, **SEARCH))
-    return p
-
-
-@pytest.fixture
-def no_engines(monkeypatch):
-    from azalea_amd import engine
-
-    def refuse(*a, **kw):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", refuse)
-    monkeypatch.setattr(engine, "Match", refuse)
-
-
 def test_device_match_is_a_keyword_of_player_and_off_by_default():
     from azalea_amd.parallel_player import Player
     p = inspect.signature(Player.__init__).parameters["device_match"]

@@ -7,9 +7,13 @@ import inspect
 import math
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import _Agent, _RandomAgent, _cpu_policy, no_engines  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("azx_set_resign", "azx_clear_resign", "azx_resign_is_exempt", "azx_resign_stats", "azx_resign_value")
@@ -150,41 +154,7 @@ def test_null_engines_are_einval_before_any_device_work():
     assert lib.azx_resign_value(None, None) == EINVAL
 
 
-# ---- Player and train: the refusal comes before anything touches a GPU (the stubs of test_playout_cap_api.py) -----
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
-
-
-class _RandomAgent:
-    def __init__(self, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.game = HexGame(n)
-
-
-def _cpu_policy():
-    from azalea_amd.policy import Policy
-    p = Policy()
-    p.initialize(dict(device="cpu", network="HexNetwork", board_size=5, num_blocks=1, base_chans=32, **SEARCH))
-    return p
-
-
-@pytest.fixture
-def no_engines(monkeypatch):
-    from azalea_amd import engine
-
-    def refuse(*a, **kw):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", refuse)
-    monkeypatch.setattr(engine, "Match", refuse)
-
-
+# ---- Player and train: the refusal comes before anything touches a GPU (the stubs of tests/option_api_stubs.py) -----
 BAD = (((-1.5, 4, 0.1), "threshold"), ((1.01, 4, 0.1), "threshold"), ((float("nan"), 4, 0.1), "threshold"),
        ((-0.9, -1, 0.1), "min_ply"), ((-0.9, 2.5, 0.1), "must be"), ((-0.9, True, 0.1), "must be"),
        ((-0.9, 4, -0.1), "keep_prob"), ((-0.9, 4, 1.5), "keep_prob"), ((-0.9, 4, float("nan")), "keep_prob"),

@@ -5,9 +5,13 @@ import ctypes as C
 import inspect
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import _Agent, _cpu_policy, no_engines  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("azx_set_selfplay_openings", "azx_selfplay_opening_word", "azx_selfplay_openings_bounds",
@@ -188,35 +192,7 @@ def test_the_normaliser_refuses(spec, size, word):
         norm(spec, size)
 
 
-# ---- the Player: the refusals come before anything touches a GPU (the stubs of tests/test_match_openings_api.py) ------
-SEARCH = dict(simulations=10, search_batch_size=2, exploration_coef=0.5, exploration_depth=3,
-              exploration_noise_alpha=0.3, exploration_noise_scale=0.25, exploration_temperature=1.0)
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
-
-
-def _cpu_policy():
-    from azalea_amd.policy import Policy
-    p = Policy()
-    p.initialize(dict(device="cpu", network="HexNetwork", board_size=5, num_blocks=1, base_chans=32, **SEARCH))
-    return p
-
-
-@pytest.fixture
-def no_engines(monkeypatch):
-    from azalea_amd import engine
-
-    def refuse(*a, **kw):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", refuse)
-    monkeypatch.setattr(engine, "Match", refuse)
-
-
+# ---- the Player: the refusals come before anything touches a GPU (the stubs of tests/option_api_stubs.py) ------
 def test_selfplay_openings_is_a_new_keyword_and_openings_keeps_its_refusal(no_engines):
     from azalea_amd.parallel_player import Player
     for name in ("selfplay_openings", "selfplay_opening_weights", "openings"):

@@ -5,8 +5,12 @@ import ctypes as C
 import inspect
 import os
 import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from option_api_stubs import _Agent  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOURNAMENT_SYMBOLS = ("azx_tournament_create", "azx_tournament_destroy", "azx_tournament_play")
@@ -65,13 +69,6 @@ def test_null_and_short_arguments_are_refused():
     assert L.azx_tournament_play(None, 1, pa, pb, 0, 1, 1, None, None, None, None) == AZX_EINVAL
     assert L.azx_last_error()
     L.azx_tournament_destroy(None)                                             # a null tournament is ignored
-
-
-class _Agent:
-    def __init__(self, policy, n=5):
-        from azalea_amd.game.hex import HexGame
-        self.policy = policy
-        self.game = HexGame(n)
 
 
 def test_evaluate_throughput_pooled_makes_the_same_checks_before_the_gpu():
