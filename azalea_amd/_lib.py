@@ -130,6 +130,7 @@ SYMBOLS = {
     "azx_debug_set_queue_cap": (C.c_int, [_vp, C.c_int64]),
     "azx_debug_stagger": (C.c_int, [_vp, _i32p]),
     "azx_debug_tower_tiles": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), _i32p]),
+    "azx_debug_tower_choice": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "azx_stream": (_vp, [_vp]),
     "azx_set_external_evaluator": (C.c_int, [_vp, _vp, _vp]),   # fn passed as a pointer (NULL = unregister)
     "azx_match_create": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),

@@ -613,6 +613,14 @@ extern "C" int azx_debug_tower_tiles(int board_size, const char *map, uint8_t *r
     return t.edge;
 }
 
+// host only: which tower and heads kernels azx_create would give a network of this shape (net_kernels.hip: net_plan)
+extern "C" int azx_debug_tower_choice(int board_size, int num_blocks, int base_chans, int flags, char *buf, int cap) {
+    if (!buf || cap < 1) return fail(AZX_EINVAL, "null argument");
+    const int rc = azx_net_describe(board_size, num_blocks, base_chans, (flags & AZX_FLAG_TOWER_F16) ? 1 : 0, buf, cap);
+    if (rc < 0) g_err = azx_net_error();
+    return rc;
+}
+
 extern "C" int azx_debug_set_queue_cap(azx_engine *e, int64_t rows) {
     if (!e || rows < 0) return fail(AZX_EINVAL, "bad argument");
     e->dbg_qcap = rows;

@@ -8,11 +8,11 @@
 struct AzxNet;
 
 // tower_f16 != 0 (AZX_FLAG_TOWER_F16): the plain-f16 tower (k_tower_f16_s16, or k_stem_wide_f16 + k_conv_wide_f16_s16 per
-// layer) instead of the split-f16 one; AZX_EINVAL when the shape has none (azx_net_has_f16_tower) or AZX_TOWER=fp32 is set
+// layer) instead of the split-f16 one; AZX_EINVAL when the shape has none or AZX_TOWER=fp32 is set (net_priv.h: TowerChoice)
 int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, int tower_f16, hipStream_t st);
-bool azx_net_has_fused_tower(int N, int blocks, int chans);   // 64 channels, <= 121 cells, >= 1 block
-// a shape with a plain-f16 tower: the fused tower's, or the wide tower's (channels a multiple of 128) with >= 1 block
-bool azx_net_has_f16_tower(int N, int blocks, int chans);
+// host only, no device call: what azx_net_kernel_info would report for the network azx_net_create would make of these
+// arguments now, written to buf (truncated to cap - 1 bytes); its full length, or azx_net_create's refusal (< 0)
+int azx_net_describe(int N, int blocks, int chans, int tower_f16, char *buf, int cap);
 void azx_net_destroy(AzxNet *net);
 // the engine re-made its stream (azx_reserve_cus): use `st` from now on and make the wide tower's side streams on the
 // same CU mask (`mask` words, 0 words = all CUs); the old side streams are drained and dropped

@@ -2100,34 +2100,102 @@ __global__ __launch_bounds__(192 * HEADS_KSPLIT) void k_heads(NetDev P, const fl
 // host side
 // ============================================================================================
 
+static int raise_lds_limits();     // beside run_net's launches, below
 
-// Every tower kernel takes its LDS image as dynamic shared memory above the 64 KB default: the limit is raised to
-// the CU's 160 KB for all of them whenever a network is created (per device and idempotent; a process-wide "done"
-// flag would leave a second device, or a later network with a larger image, on the first one's setting -- which
-// ROCm 7.2 happens not to enforce, but the contract is the opt-in).
-static int raise_lds_limits() {
-    const int cap = 160 * 1024;
-    const void *fns[] = {(const void *)k_tower_f16x3_s16, (const void *)k_tower_f16_s16, (const void *)k_conv_wide_f16x3_s16,
-                         (const void *)k_conv_wide_f16_s16,
-                         (const void *)k_tower_mfma<64, 4, 2, 1, 2>, (const void *)k_tower_mfma<64, 6, 1, 2, 2>,
-                         (const void *)k_tower_mfma<32, 6, 2, 2, 1>, (const void *)k_heads_mfma, (const void *)k_heads};
-    for (const void *f : fns)
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess)
-            return nfail(AZX_EHIP, "net: raising a tower kernel's dynamic LDS limit failed");
+// ---- the choice of the tower ---------------------------------------------------------------------------------------
+// Which tower a shape runs and what that tower needs from the host (TowerChoice, net_priv.h): a pure function of the
+// shape, the engine flag AZX_FLAG_TOWER_F16 and the AZX_TOWER switch (`force`, may be null).  Every fact about a kind
+// is stated here, in its case, and nowhere else; run_net's launch switch is the only other place that names the kinds.
+static int tower_choose(int N, int blocks, int chans, bool flag_f16, const char *force, TowerChoice *out) {
+    const int ncells = N * N;
+    const bool want_fp32 = force && !strcmp(force, "fp32");
+    const bool fused = chans == 64 && ncells <= 121 && blocks >= 1;
+    const bool wide = chans % 128 == 0 && ncells <= 192;
+    if (flag_f16 && want_fp32)
+        return nfail(AZX_EINVAL, "net: the plain-f16 tower was asked for (AZX_FLAG_TOWER_F16) but AZX_TOWER=fp32 forces the fp32 tower");
+    if (flag_f16 && !(fused || (wide && blocks >= 1)))
+        return nfail(AZX_EINVAL, "net: the plain-f16 tower (AZX_FLAG_TOWER_F16) exists for the fused tower's shapes (64 channels, at most "
+                                 "121 cells) and the wide tower's (a multiple of 128 channels) only, with at least one block");
+    // AZX_TOWER=f16: the plain-f16 tower wherever the fused or the wide tower would run with at least one block, ignored
+    // elsewhere (a lenient knob, unlike the flag)
+    const bool want_f16 = flag_f16 || (force && !strcmp(force, "f16"));
+    TowerChoice c;
+    if (fused && !want_fp32) c.kind = TowerKind::Fused;
+    else if (chans == 64 && ncells <= 128) c.kind = TowerKind::Mfma64x4;
+    else if (chans == 64 && ncells <= 192) c.kind = TowerKind::Mfma64x6;
+    else if (chans == 32 && ncells <= 192) c.kind = TowerKind::Mfma32x6;
+    else if (wide && !want_fp32) c.kind = TowerKind::Wide;
+    const size_t mfma_board = (size_t)2 * (ncells + 1) * (chans + 4) * sizeof(float);   // k_tower_mfma: two images per board
+    switch (c.kind) {
+    case TowerKind::Generic: c.name = "k_stem_generic + k_conv_generic (VALU)"; c.wg = c.act23 = true; break;
+    case TowerKind::Mfma64x4: c.name = "k_tower_mfma<64,4,2,1,2> (fp32 MFMA)"; c.wp = true; c.lds_bytes = 2 * mfma_board; break;
+    case TowerKind::Mfma64x6: c.name = "k_tower_mfma<64,6,1,2,2> (fp32 MFMA)"; c.wp = true; c.lds_bytes = mfma_board; break;
+    case TowerKind::Mfma32x6: c.name = "k_tower_mfma<32,6,2,2,1> (fp32 MFMA)"; c.wp = true; c.lds_bytes = 2 * mfma_board; break;
+    case TowerKind::Fused:
+        c.f16 = want_f16;
+        c.name = c.f16 ? "k_tower_f16_s16" : "k_tower_f16x3_s16";
+        c.s16 = c.hd16 = c.f16_weights = c.hfeat = true;
+        c.tile_map = !c.f16;     // k_tower_f16x3_s16's position tiles (tower_tiles.h)
+        // boards + the zero rows (two in k_tower_f16x3_s16) and, with the tile map, the rows between its two boards
+        c.lds_bytes = (size_t)F16X3_BPB * 128 * 272 + 2 * 272 + (c.tile_map ? (size_t)AZX_TOWER_BOARD_GAP * 272 : 0);
+        break;
+    case TowerKind::Wide:
+        c.f16 = want_f16 && blocks >= 1;
+        c.name = c.f16 ? "k_stem_wide_f16 + k_conv_wide_f16_s16 per layer" : "k_stem_wide_f16x3 + k_conv_wide_f16x3_s16 per layer";
+        c.s32 = c.s16 = c.wide_perm = c.f16_weights = c.wide_xy = true;
+        c.rows_splittable = false;     // its layer launches run on side streams of their own
+        c.lds_bytes = (size_t)(ncells + 2) * WIDE_ROWB;   // two zero rows + the chunk image
+        break;
+    }
+    c.precision = want_fp32 ? "fp32" : c.f16 ? "f16" : "default";
+    *out = c;
     return AZX_OK;
 }
 
-bool azx_net_has_fused_tower(int N, int blocks, int chans) { return chans == 64 && N * N <= 121 && blocks >= 1; }
-static bool has_wide_tower(int N, int chans) { return chans % 128 == 0 && N * N <= 192; }     // tower variant 5
-bool azx_net_has_f16_tower(int N, int blocks, int chans) {
-    return azx_net_has_fused_tower(N, blocks, chans) || (has_wide_tower(N, chans) && blocks >= 1);
+// Everything azx_net_create decides before it touches the device, written into a fresh AzxNet: the tower, the diagnostic
+// switches (read here, once per network) and the text azx_net_kernel_info reports.  azx_net_describe answers from the
+// same function, on a network that never reaches the device.
+static int net_plan(AzxNet *net, int N, int blocks, int chans, int tower_f16, AzxTowerTiles *tiles) {
+    if (N < 2 || N > AZX_MAX_BOARD) return nfail(AZX_EINVAL, "net: board size out of range");
+    if (blocks < 0 || chans < 1) return nfail(AZX_EINVAL, "net: bad num_blocks/base_chans");
+    if (int rc = tower_choose(N, blocks, chans, tower_f16 != 0, getenv("AZX_TOWER"), &net->tower)) return rc;
+    const TowerChoice &t = net->tower;
+    bool heads_mfma = true, want_edge = true;     // AZX_HEADS=valu: the scalar-FMA k_heads behind the fused tower too
+    { const char *v = getenv("AZX_WIDE_STREAMS"); net->opt_wsplit = std::min(4, std::max(1, v ? atoi(v) : 2)); }
+    { const char *v = getenv("AZX_HEADS"); heads_mfma = !(v && !strcmp(v, "valu")); }
+    { const char *v = getenv("AZX_PACK"); net->pack_on_host = v && !strcmp(v, "host"); }
+    net->heads_mfma = t.hfeat && heads_mfma && N * N <= 128;
+    // k_tower_f16x3_s16's position tiles: AZX_TOWER_TILES=rows keeps 16 consecutive cells per tile, the default (edge)
+    // gives every wave one tile of pure edge cells whose padding taps it skips (tower_tiles.h)
+    { const char *v = getenv("AZX_TOWER_TILES"); want_edge = !(v && !strcmp(v, "rows")); }
+    azx_tower_tiles_build(N, t.tile_map && want_edge, tiles);
+    char b[320];
+    snprintf(b, sizeof b, "%s + %s (%dx%d on %dx%d; AZX_TOWER=%s AZX_TOWER_TILES=%s AZX_WIDE_STREAMS=%d AZX_HEADS=%s AZX_PACK=%s)",
+             t.name, net->heads_mfma ? "k_heads_mfma" : "k_heads", blocks, chans, N, N, t.precision,
+             // like the other switches, the setting is reported by every engine; only k_tower_f16x3_s16 has a tile map
+             want_edge && (tiles->edge || !t.tile_map) ? "edge" : "rows",
+             net->opt_wsplit, heads_mfma ? "mfma" : "valu", net->pack_on_host ? "host" : "device");
+    net->info = b;
+    return AZX_OK;
+}
+
+int azx_net_describe(int N, int blocks, int chans, int tower_f16, char *buf, int cap) {
+    AzxNet net;
+    AzxTowerTiles tiles;
+    if (int rc = net_plan(&net, N, blocks, chans, tower_f16, &tiles)) return rc;
+    if (buf && cap > 0) snprintf(buf, cap, "%s", net.info.c_str());
+    return (int)net.info.size();
 }
 
 int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, int tower_f16, hipStream_t st) {
-    if (N < 2 || N > AZX_MAX_BOARD) return nfail(AZX_EINVAL, "net: board size out of range");
-    if (blocks < 0 || chans < 1) return nfail(AZX_EINVAL, "net: bad num_blocks/base_chans");
-    if (int rc = raise_lds_limits()) return rc;
     AzxNet *net = new AzxNet();
+    AzxTowerTiles tiles;
+    int rc = net_plan(net, N, blocks, chans, tower_f16, &tiles);
+    if (!rc) rc = raise_lds_limits();
+    if (rc) {
+        delete net;
+        return rc;
+    }
     memset(&net->d, 0, sizeof net->d);
     net->d.N = N;
     net->d.ncells = N * N;
@@ -2136,84 +2204,29 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     net->d.layers = 2 * blocks;
     net->max_evals = max_evals;
     net->stream = st;
-    const int ncells = N * N;
-    // pick the fused MFMA tower when its tiling covers (C, N)
-    const char *force = getenv("AZX_TOWER");
-    const bool want_fp32 = force && !strcmp(force, "fp32");
-    const bool fused = azx_net_has_fused_tower(N, blocks, chans);
-    const bool has_f16 = azx_net_has_f16_tower(N, blocks, chans);
-    if (tower_f16 && (!has_f16 || want_fp32)) {
-        delete net;
-        return nfail(AZX_EINVAL, want_fp32 ? "net: the plain-f16 tower was asked for (AZX_FLAG_TOWER_F16) but AZX_TOWER=fp32 forces the fp32 tower"
-                                           : "net: the plain-f16 tower (AZX_FLAG_TOWER_F16) exists for the fused tower's shapes (64 channels, at most "
-                                             "121 cells) and the wide tower's (a multiple of 128 channels) only, with at least one block");
-    }
-    // AZX_TOWER=f16: the plain-f16 tower wherever the fused or the wide tower would run with at least one block, ignored
-    // elsewhere (a lenient knob, unlike the flag)
-    const bool want_f16 = tower_f16 || (force && !strcmp(force, "f16"));
-    if (fused && !want_fp32) { net->tower_variant = 4; net->tower_f16 = want_f16; }   // k_tower_f16x3_s16 | k_tower_f16_s16
-    else if (chans == 64 && ncells <= 128) net->tower_variant = 1;   // <64,4,2,1,2>
-    else if (chans == 64 && ncells <= 192) net->tower_variant = 2;   // <64,6,1,2,2>
-    else if (chans == 32 && ncells <= 192) net->tower_variant = 3;   // <32,6,2,2,1>
-    else if (has_wide_tower(N, chans) && !want_fp32) {     // k_conv_wide_f16x3_s16 | k_conv_wide_f16_s16 per layer
-        net->tower_variant = 5;
-        net->tower_f16 = want_f16 && blocks >= 1;
-    }
-    net->use_mfma = net->tower_variant != 0;
-    { const char *v = getenv("AZX_WIDE_STREAMS"); net->opt_wsplit = std::min(4, std::max(1, v ? atoi(v) : 2)); }
-    { const char *v = getenv("AZX_HEADS"); net->opt_heads_mfma = !(v && !strcmp(v, "valu")); }
-    { const char *v = getenv("AZX_PACK"); net->pack_on_host = v && !strcmp(v, "host"); }
-    // k_tower_f16x3_s16's position tiles: AZX_TOWER_TILES=rows keeps 16 consecutive cells per tile, the default (edge)
-    // gives every wave one tile of pure edge cells whose padding taps it skips (tower_tiles.h)
-    const bool x3 = net->tower_variant == 4 && !net->tower_f16;
-    AzxTowerTiles tiles;
-    bool want_edge = true;
-    { const char *v = getenv("AZX_TOWER_TILES"); want_edge = !(v && !strcmp(v, "rows")); }
-    azx_tower_tiles_build(N, x3 && want_edge, &tiles);
-    {
-        char b[320];
-        const char *tower = "k_stem_generic + k_conv_generic (VALU)";
-        if (net->tower_variant == 4) tower = net->tower_f16 ? "k_tower_f16_s16" : "k_tower_f16x3_s16";
-        else if (net->tower_variant == 5) tower = net->tower_f16 ? "k_stem_wide_f16 + k_conv_wide_f16_s16 per layer"
-                                                                 : "k_stem_wide_f16x3 + k_conv_wide_f16x3_s16 per layer";
-        else if (net->tower_variant == 1) tower = "k_tower_mfma<64,4,2,1,2> (fp32 MFMA)";
-        else if (net->tower_variant == 2) tower = "k_tower_mfma<64,6,1,2,2> (fp32 MFMA)";
-        else if (net->tower_variant == 3) tower = "k_tower_mfma<32,6,2,2,1> (fp32 MFMA)";
-        const bool hm = net->tower_variant == 4 && net->opt_heads_mfma && ncells <= 128;
-        snprintf(b, sizeof b, "%s + %s (%dx%d on %dx%d; AZX_TOWER=%s AZX_TOWER_TILES=%s AZX_WIDE_STREAMS=%d AZX_HEADS=%s AZX_PACK=%s)",
-                 tower, hm ? "k_heads_mfma" : "k_heads", blocks, chans, N, N, want_fp32 ? "fp32" : net->tower_f16 ? "f16" : "default",
-                 // like the other switches, the setting is reported by every engine; only k_tower_f16x3_s16 has a tile map
-                 want_edge && (tiles.edge || !x3) ? "edge" : "rows",
-                 net->opt_wsplit, net->opt_heads_mfma ? "mfma" : "valu", net->pack_on_host ? "host" : "device");
-        net->info = b;
-    }
-    const size_t E = max_evals;
+    const TowerChoice &t = net->tower;
+    const size_t E = max_evals, ncells = N * N;
     net->act = nalloc<float>(net, E * ncells * chans);
     net->logit = nalloc<float>(net, E * AZX_CELL_STRIDE);
-    if (net->tower_variant == 4) net->hfeat = nalloc<float>(net, E * 6 * ncells);
+    if (t.hfeat) net->hfeat = nalloc<float>(net, E * 6 * ncells);
     net->hb_board = nalloc<uint8_t>(net, E * AZX_CELL_STRIDE);
     net->hb_flip = nalloc<int32_t>(net, E);
     net->hb_value = nalloc<float>(net, E);
-    if (!net->use_mfma) {
+    if (t.act23) {
         net->act2 = nalloc<float>(net, E * ncells * chans);
         net->act3 = nalloc<float>(net, E * ncells * chans);
     }
-    if (net->tower_variant == 5) {
+    if (t.wide_xy) {
         net->wideX = nalloc<unsigned short>(net, E * ncells * chans * 2);
         net->wideY = nalloc<unsigned short>(net, E * ncells * chans * 2);
     }
     if (!net->act || !net->logit || !net->hb_board || !net->hb_flip || !net->hb_value ||
-        (!net->use_mfma && (!net->act2 || !net->act3)) || (net->tower_variant == 5 && (!net->wideX || !net->wideY))) {
+        (t.act23 && (!net->act2 || !net->act3)) || (t.wide_xy && (!net->wideX || !net->wideY))) {
         azx_net_destroy(net);
         return nfail(AZX_ENOMEM, "net: hipMalloc failed");
     }
-    const int bpb = net->tower_variant == 2 ? 1 : 2;
-    net->lds_bytes = (size_t)bpb * 2 * (ncells + 1) * (chans + 4) * sizeof(float);
-    if (net->tower_variant == 4) net->lds_bytes = (size_t)F16X3_BPB * 128 * 272 + 2 * 272;   // boards + the zero rows (two in k_tower_f16x3_s16)
-    if (x3) net->lds_bytes += (size_t)AZX_TOWER_BOARD_GAP * 272;     // ... and the rows between its two boards (tower_tiles.h)
-    if (net->tower_variant == 5) net->lds_bytes = (size_t)(ncells + 2) * WIDE_ROWB;   // two zero rows + the chunk image
     net->d.sat_flag = nalloc<uint32_t>(net, 4);
-    if (x3) {     // once per network: the kernel reads the table through NetDev
+    if (t.tile_map) {     // once per network: the kernel reads the table through NetDev
         uint8_t *tm = nalloc<uint8_t>(net, sizeof tiles.row);
         if (tm && hipMemcpy(tm, tiles.row, sizeof tiles.row, hipMemcpyHostToDevice) != hipSuccess) tm = nullptr;
         if (!tm) {
@@ -2231,8 +2244,8 @@ int azx_net_create(AzxNet **out, int N, int blocks, int chans, int max_evals, in
     return AZX_OK;
 }
 
-void azx_net_set_stream(AzxNet *net, hipStream_t st, const uint32_t *mask, int words) {
-    if (!net) return;
+// drains and drops the wide tower's side streams and their events; run_net makes them again on first use
+static void drop_side_streams(AzxNet *net) {
     for (int i = 0; i < 3; ++i) {
         if (net->stream2[i]) { (void)hipStreamSynchronize(net->stream2[i]); (void)hipStreamDestroy(net->stream2[i]); }
         if (net->ev_join[i]) (void)hipEventDestroy(net->ev_join[i]);
@@ -2240,24 +2253,20 @@ void azx_net_set_stream(AzxNet *net, hipStream_t st, const uint32_t *mask, int w
         net->ev_join[i] = nullptr;
     }
     if (net->ev_fork) (void)hipEventDestroy(net->ev_fork);
-    net->ev_fork = nullptr;           // run_net makes the side streams again on first use
+    net->ev_fork = nullptr;
     net->streams_ok = false;
+}
+
+void azx_net_set_stream(AzxNet *net, hipStream_t st, const uint32_t *mask, int words) {
+    if (!net) return;
+    drop_side_streams(net);
     net->cu_mask.assign(mask, mask + (mask ? words : 0));
     net->stream = st;
 }
 
-void azx_net_destroy(AzxNet *net) {
-    if (net) {
-        for (int i = 0; i < 3; ++i) {
-            if (net->stream2[i]) { (void)hipStreamSynchronize(net->stream2[i]); (void)hipStreamDestroy(net->stream2[i]); }
-            if (net->ev_join[i]) (void)hipEventDestroy(net->ev_join[i]);
-            net->stream2[i] = nullptr;
-            net->ev_join[i] = nullptr;
-        }
-        if (net->ev_fork) (void)hipEventDestroy(net->ev_fork);
-        net->ev_fork = nullptr;
-    }
 #ifdef AZX_NET_STAMP
+// the diagnostic build's report, when a network goes: the s_memtime sums the stamped kernels left since the last one
+static void report_stamps(const AzxNet *net) {
     {
         unsigned long long h[10] = {0};
         if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wide_stamp), sizeof h) == hipSuccess && h[7]) {
@@ -2311,16 +2320,23 @@ void azx_net_destroy(AzxNet *net) {
                         busy / ((double)(t1 - t0) * cu.size()), mn / 100.0, mx / 100.0, lastend_min / 100.0, lastend_max / 100.0);
             }
             int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_tower_f16x3_s16, F16X3_BPB * 128, net->lds_bytes);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_tower_f16x3_s16, F16X3_BPB * 128, net->tower.lds_bytes);
             hipFuncAttributes fa;
             memset(&fa, 0, sizeof fa);
             (void)hipFuncGetAttributes(&fa, (const void *)k_tower_f16x3_s16);
             fprintf(stderr, "  runtime occupancy: %d blocks/CU (dynamic LDS %zu B, static %zu B, %d VGPRs, max threads %d)\n", nb,
-                    net->lds_bytes, (size_t)fa.sharedSizeBytes, fa.numRegs, fa.maxThreadsPerBlock);
+                    net->tower.lds_bytes, (size_t)fa.sharedSizeBytes, fa.numRegs, fa.maxThreadsPerBlock);
         }
     }
+}
 #endif
+
+void azx_net_destroy(AzxNet *net) {
     if (!net) return;
+    drop_side_streams(net);
+#ifdef AZX_NET_STAMP
+    report_stamps(net);
+#endif
     for (void *p : net->allocs) (void)hipFree(p);
     if (net->raw_tab_host) (void)hipHostFree((void *)net->raw_tab_host);
     if (net->wmax_host) (void)hipHostFree((void *)net->wmax_host);
@@ -2329,6 +2345,74 @@ void azx_net_destroy(AzxNet *net) {
 
 bool azx_net_ready(const AzxNet *net) { return net && net->ready; }
 
+// the wide tower: the stem, then two launches per block over all boards (row0 = 0: its buffers are not split)
+static void run_wide_tower(AzxNet *net, const uint8_t *boards, const int32_t *n_eval_ptr, int n_host, int max_n, hipStream_t st) {
+    const NetDev &d = net->d;
+    const size_t lds = net->tower.lds_bytes;
+    const dim3 grid(max_n, d.C / 128), block(256);
+    const auto k_stem = net->tower.f16 ? k_stem_wide_f16 : k_stem_wide_f16x3;
+    const auto k_conv = net->tower.f16 ? k_conv_wide_f16_s16 : k_conv_wide_f16x3_s16;
+    hipLaunchKernelGGL(k_stem, grid, block, 0, st, d, boards, net->wideX,
+                       d.blocks == 0 ? net->act : (float *)nullptr, n_eval_ptr, n_host);
+    // A layer is one launch over all boards, and a launch ends with a partly filled round of blocks
+    // (9 964 blocks over 512 slots: 19.46 rounds, 2.7 % of a layer idle) -- 38 times per batch.  The
+    // boards are independent, so the batch is cut into AZX_WIDE_STREAMS parts that run their 38 launches
+    // on separate streams: one part's tail round fills up with the others' blocks, whichever layer
+    // those are in.
+    const int wsplit = net->opt_wsplit;
+    int parts = wsplit;
+    if (parts > 1 && !net->ev_fork) {
+        bool ok = hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < 3 && ok; ++i)
+            ok = (net->cu_mask.empty() ? hipStreamCreateWithFlags(&net->stream2[i], hipStreamNonBlocking)
+                                       : hipExtStreamCreateWithCUMask(&net->stream2[i], (uint32_t)net->cu_mask.size(), net->cu_mask.data())) == hipSuccess &&
+                 hipEventCreateWithFlags(&net->ev_join[i], hipEventDisableTiming) == hipSuccess;
+        net->streams_ok = ok;
+    }
+    if (parts > 1 && !net->streams_ok) parts = 1;
+    const int per = (((max_n + parts - 1) / parts + 7) / 8) * 8;     // boards per part, whole groups of 8
+    if (per >= max_n) parts = 1;
+    // the stem (and everything before it) is done; if the fork cannot be recorded or waited for, a
+    // later part's convolutions could start before the stem has finished: fall back to one stream
+    if (parts > 1 && hipEventRecord(net->ev_fork, st) != hipSuccess) parts = 1;
+    for (int part = 1; part < parts; ++part)
+        if (hipStreamWaitEvent(net->stream2[part - 1], net->ev_fork, 0) != hipSuccess) { parts = 1; break; }
+    const int per_ok = parts > 1 ? per : max_n;
+    for (int part = 0; part < parts; ++part) {
+        hipStream_t s = part ? net->stream2[part - 1] : st;
+        const int e0 = part * per_ok, e1 = std::min(max_n, e0 + per_ok);
+        if (e1 <= e0) continue;
+        const dim3 g(8 * (d.C / 128), (e1 - e0 + 7) / 8);
+        for (int b = 0; b < d.blocks; ++b) {
+            hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b, (const unsigned short *)net->wideX, net->wideY,
+                               (const unsigned short *)nullptr, (float *)nullptr, n_eval_ptr, n_host, e0, e1);
+            hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b + 1, (const unsigned short *)net->wideY, net->wideX,
+                               (const unsigned short *)net->wideX, b == d.blocks - 1 ? net->act : (float *)nullptr, n_eval_ptr, n_host, e0, e1);
+        }
+        if (part) {     // the heads read every board; if the join cannot be expressed on the streams, block
+            if (hipEventRecord(net->ev_join[part - 1], s) != hipSuccess ||
+                hipStreamWaitEvent(st, net->ev_join[part - 1], 0) != hipSuccess)
+                (void)hipStreamSynchronize(s);
+        }
+    }
+}
+
+// Every tower kernel takes its LDS image as dynamic shared memory above the 64 KB default: the limit is raised to
+// the CU's 160 KB for all of them whenever a network is created (per device and idempotent; a process-wide "done"
+// flag would leave a second device, or a later network with a larger image, on the first one's setting -- which
+// ROCm 7.2 happens not to enforce, but the contract is the opt-in).  The list is run_net's and run_wide_tower's
+// launches with dynamic LDS: a kernel added to them is added here.
+static int raise_lds_limits() {
+    const int cap = 160 * 1024;
+    const void *fns[] = {(const void *)k_tower_f16x3_s16, (const void *)k_tower_f16_s16, (const void *)k_conv_wide_f16x3_s16,
+                         (const void *)k_conv_wide_f16_s16,
+                         (const void *)k_tower_mfma<64, 4, 2, 1, 2>, (const void *)k_tower_mfma<64, 6, 1, 2, 2>,
+                         (const void *)k_tower_mfma<32, 6, 2, 2, 1>, (const void *)k_heads_mfma, (const void *)k_heads};
+    for (const void *f : fns)
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess)
+            return nfail(AZX_EHIP, "net: raising a tower kernel's dynamic LDS limit failed");
+    return AZX_OK;
+}
 
 // tower + heads over boards[0 .. n) (n read from n_eval_ptr on the device when given).  The scratch rows used are
 // [row0, row0 + max_n) of the net's buffers, so that two calls on disjoint row ranges may run at the same time on two
@@ -2342,71 +2426,10 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
     float *const act2 = net->act2 ? net->act2 + act_rows : nullptr;
     float *const act3 = net->act3 ? net->act3 + act_rows : nullptr;
     float *const hfeat_rows = net->hfeat ? net->hfeat + row0 * 6 * d.ncells : nullptr;
-    const float *hfeat = nullptr;    // set when the tower kernel already produced the heads' conv planes
-    if (net->use_mfma) {
-        const size_t lds = net->lds_bytes;
-        if (net->tower_variant == 4) {
-            const dim3 grid((max_n + F16X3_BPB - 1) / F16X3_BPB), block(F16X3_BPB * 128);
-            if (net->tower_f16) hipLaunchKernelGGL(k_tower_f16_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, hfeat_rows);
-            else hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, hfeat_rows);
-            hfeat = hfeat_rows;
-        } else if (net->tower_variant == 5) {
-            const dim3 grid(max_n, d.C / 128), block(256);
-            const auto k_stem = net->tower_f16 ? k_stem_wide_f16 : k_stem_wide_f16x3;
-            const auto k_conv = net->tower_f16 ? k_conv_wide_f16_s16 : k_conv_wide_f16x3_s16;
-            hipLaunchKernelGGL(k_stem, grid, block, 0, st, d, boards, net->wideX,
-                               d.blocks == 0 ? net->act : (float *)nullptr, n_eval_ptr, n_host);
-            // A layer is one launch over all boards, and a launch ends with a partly filled round of blocks
-            // (9 964 blocks over 512 slots: 19.46 rounds, 2.7 % of a layer idle) -- 38 times per batch.  The
-            // boards are independent, so the batch is cut into AZX_WIDE_STREAMS parts that run their 38 launches
-            // on separate streams: one part's tail round fills up with the others' blocks, whichever layer
-            // those are in.
-            const int wsplit = net->opt_wsplit;
-            {
-                int parts = wsplit;
-                if (parts > 1 && !net->ev_fork) {
-                    bool ok = hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming) == hipSuccess;
-                    for (int i = 0; i < 3 && ok; ++i)
-                        ok = (net->cu_mask.empty() ? hipStreamCreateWithFlags(&net->stream2[i], hipStreamNonBlocking)
-                                                   : hipExtStreamCreateWithCUMask(&net->stream2[i], (uint32_t)net->cu_mask.size(), net->cu_mask.data())) == hipSuccess &&
-                             hipEventCreateWithFlags(&net->ev_join[i], hipEventDisableTiming) == hipSuccess;
-                    net->streams_ok = ok;
-                }
-                if (parts > 1 && !net->streams_ok) parts = 1;
-                const int per = (((max_n + parts - 1) / parts + 7) / 8) * 8;     // boards per part, whole groups of 8
-                if (per >= max_n) parts = 1;
-                // the stem (and everything before it) is done; if the fork cannot be recorded or waited for, a
-                // later part's convolutions could start before the stem has finished: fall back to one stream
-                if (parts > 1 && hipEventRecord(net->ev_fork, st) != hipSuccess) parts = 1;
-                for (int part = 1; part < parts; ++part)
-                    if (hipStreamWaitEvent(net->stream2[part - 1], net->ev_fork, 0) != hipSuccess) { parts = 1; break; }
-                const int per_ok = parts > 1 ? per : max_n;
-                for (int part = 0; part < parts; ++part) {
-                    hipStream_t s = part ? net->stream2[part - 1] : st;
-                    const int e0 = part * per_ok, e1 = std::min(max_n, e0 + per_ok);
-                    if (e1 <= e0) continue;
-                    const dim3 g(8 * (d.C / 128), (e1 - e0 + 7) / 8);
-                    for (int b = 0; b < d.blocks; ++b) {
-                        hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b, (const unsigned short *)net->wideX, net->wideY,
-                                           (const unsigned short *)nullptr, (float *)nullptr, n_eval_ptr, n_host, e0, e1);
-                        hipLaunchKernelGGL(k_conv, g, block, lds, s, d, 2 * b + 1, (const unsigned short *)net->wideY, net->wideX,
-                                           (const unsigned short *)net->wideX, b == d.blocks - 1 ? net->act : (float *)nullptr, n_eval_ptr, n_host, e0, e1);
-                    }
-                    if (part) {     // the heads read every board; if the join cannot be expressed on the streams, block
-                        if (hipEventRecord(net->ev_join[part - 1], s) != hipSuccess ||
-                            hipStreamWaitEvent(st, net->ev_join[part - 1], 0) != hipSuccess)
-                            (void)hipStreamSynchronize(s);
-                    }
-                }
-            }
-        } else if (net->tower_variant == 1) {
-            hipLaunchKernelGGL((k_tower_mfma<64, 4, 2, 1, 2>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
-        } else if (net->tower_variant == 2) {
-            hipLaunchKernelGGL((k_tower_mfma<64, 6, 1, 2, 2>), dim3(max_n), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
-        } else {
-            hipLaunchKernelGGL((k_tower_mfma<32, 6, 2, 2, 1>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
-        }
-    } else {
+    const float *const hfeat = hfeat_rows;     // the heads' conv planes, where the tower kernel leaves them
+    const size_t lds = net->tower.lds_bytes;
+    switch (net->tower.kind) {
+    case TowerKind::Generic: {
         const int grid = 2048;
         hipLaunchKernelGGL(k_stem_generic, dim3(grid), dim3(256), 0, st, d, boards, n_eval_ptr, n_host, max_n, act);
         float *x = act, *y = act2, *z = act3;
@@ -2417,8 +2440,28 @@ static void run_net(AzxNet *net, const uint8_t *boards, const int32_t *flip, con
         }
         if (x != act)   // heads read act
             (void)hipMemcpyAsync(act, x, (size_t)max_n * d.ncells * d.C * sizeof(float), hipMemcpyDeviceToDevice, st);
+        break;
     }
-    if (hfeat != nullptr && net->opt_heads_mfma && d.ncells <= 128) {
+    case TowerKind::Mfma64x4:
+        hipLaunchKernelGGL((k_tower_mfma<64, 4, 2, 1, 2>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
+        break;
+    case TowerKind::Mfma64x6:
+        hipLaunchKernelGGL((k_tower_mfma<64, 6, 1, 2, 2>), dim3(max_n), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
+        break;
+    case TowerKind::Mfma32x6:
+        hipLaunchKernelGGL((k_tower_mfma<32, 6, 2, 2, 1>), dim3((max_n + 1) / 2), dim3(256), lds, st, d, boards, n_eval_ptr, n_host, act);
+        break;
+    case TowerKind::Fused: {
+        const dim3 grid((max_n + F16X3_BPB - 1) / F16X3_BPB), block(F16X3_BPB * 128);
+        if (net->tower.f16) hipLaunchKernelGGL(k_tower_f16_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, hfeat_rows);
+        else hipLaunchKernelGGL(k_tower_f16x3_s16, grid, block, lds, st, d, boards, n_eval_ptr, n_host, (float *)nullptr, hfeat_rows);
+        break;
+    }
+    case TowerKind::Wide:
+        run_wide_tower(net, boards, n_eval_ptr, n_host, max_n, st);
+        break;
+    }
+    if (net->heads_mfma) {
         // the fused tower left the six head planes: the FC layers run as fp32 MFMA GEMMs over tiles of HM_MB boards
         const size_t hl = std::max((size_t)HM_MB * d.hm_lda, (size_t)HM_MB * AZX_CELL_STRIDE + (size_t)HM_MB * 64) * sizeof(float);
         hipLaunchKernelGGL(k_heads_mfma, dim3((max_n + HM_MB - 1) / HM_MB), dim3(256), hl, st, d, hfeat, boards, flip, n_eval_ptr, n_host, logit, value, prior);
@@ -2449,7 +2492,7 @@ void azx_net_eval(AzxNet *net, const DevEngine &e, hipStream_t st) {
     run_net(net, e.ev_board, e.ev_flip, e.n_eval, 0, net->max_evals, net->logit, e.ev_value, e.ev_prior, st);
 }
 
-bool azx_net_rows_splittable(const AzxNet *net) { return net && !(net->use_mfma && net->tower_variant == 5); }
+bool azx_net_rows_splittable(const AzxNet *net) { return net && net->tower.rows_splittable; }
 
 void azx_net_eval_rows(AzxNet *net, const DevEngine &e, int row0, int max_n, hipStream_t st) {
     run_net(net, e.ev_board, e.ev_flip, e.n_eval, 0, max_n, net->logit + (size_t)row0 * AZX_CELL_STRIDE, e.ev_value,

@@ -70,7 +70,7 @@ static std::vector<RawSlot> raw_slots(int C, int n2, int L) {
 // ---- the persistent packed buffers -----------------------------------------------------------------------------
 struct Plan {
     int C, N, n2, L, NT, NT16, NCH, KVp, KPp, NTP;
-    bool wg, wp, s32, s16, hd16;          // which tower operands this network's kernels read
+    TowerChoice tower;                    // which tower operands this network's kernels read (net_priv.h)
     size_t n_stemT, n_Wg, n_Wp, n_Ws, n_Ws16, n_Wh16, n_Whd16, n_hmP, n_hmV, n_fc2T, n_mfcT;
 };
 
@@ -79,13 +79,7 @@ static Plan make_plan(const AzxNet *net) {
     p.C = net->d.C; p.N = net->d.N; p.n2 = p.N * p.N; p.L = net->d.layers;
     p.NT = p.C / 32; p.NT16 = p.C / 16; p.NCH = p.C / 64;
     p.KVp = (2 * p.n2 + 15) & ~15; p.KPp = (4 * p.n2 + 15) & ~15; p.NTP = (p.n2 + 15) / 16;
-    const int v = net->tower_variant;
-    const bool f16 = v == 4 || v == 5;
-    p.wg = v == 0;                                     // k_conv_generic
-    p.wp = v >= 1 && v <= 3;                           // k_tower_mfma (fp32)
-    p.s32 = v == 5;                                    // the wide stem (k_stem_wide_f16x3) reads its table in 32x32x16 fragment order
-    p.s16 = f16;                                       // 16x16x32 fragment order: both split-f16 towers
-    p.hd16 = v == 4 && p.C == 64;
+    p.tower = net->tower;
     p.n_stemT = (size_t)28 * p.C;
     p.n_Wg = (size_t)p.L * 9 * p.C * p.C;
     p.n_Wp = p.n_Wg;
@@ -120,11 +114,12 @@ static int ensure_buffers(AzxNet *net, const Plan &p) {
               pbuf(net, "fc3w", d.fc3w, 64) && pbuf(net, "fc3b", d.fc3b, 1) &&
               pbuf(net, "mfcT", d.mfcT, p.n_mfcT) && pbuf(net, "mfcb", d.mfcb, AZX_CELL_STRIDE) &&
               pbuf(net, "hmP", d.hmP, p.n_hmP) && pbuf(net, "hmV", d.hmV, p.n_hmV);
-    if (ok && p.wg) ok = pbuf(net, "Wg", d.Wg, p.n_Wg);
-    if (ok && p.wp) ok = pbuf(net, "Wp", d.Wp, p.n_Wp);
-    if (ok && p.s32) ok = pbuf(net, "Ws", d.Ws, p.n_Ws);
-    if (ok && p.s16) ok = pbuf(net, "Ws16", d.Ws16, p.n_Ws16) && pbuf(net, "Wh16", d.Wh16, p.n_Wh16);
-    if (ok && p.hd16) ok = pbuf(net, "Whd16", d.Whd16, p.n_Whd16) && pbuf(net, "hbias16", d.hbias16, 16);
+    const TowerChoice &t = p.tower;
+    if (ok && t.wg) ok = pbuf(net, "Wg", d.Wg, p.n_Wg);
+    if (ok && t.wp) ok = pbuf(net, "Wp", d.Wp, p.n_Wp);
+    if (ok && t.s32) ok = pbuf(net, "Ws", d.Ws, p.n_Ws);
+    if (ok && t.s16) ok = pbuf(net, "Ws16", d.Ws16, p.n_Ws16) && pbuf(net, "Wh16", d.Wh16, p.n_Wh16);
+    if (ok && t.hd16) ok = pbuf(net, "Whd16", d.Whd16, p.n_Whd16) && pbuf(net, "hbias16", d.hbias16, 16);
     if (!ok) return azx_net_fail(AZX_ENOMEM, "net: hipMalloc of the packed weight buffers failed");
     d.hm_lda = ((p.KVp + p.KPp - 4 + 63) / 64) * 64 + 4;        // smallest stride = 4 (mod 64) that holds a row
     const int nf = p.C * (p.L + 1) + 6;
@@ -162,7 +157,8 @@ static inline unsigned short f16bits_host(float w, int part) {
 }
 
 static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, std::vector<float>> &T, float *wmax_out) {
-    const int C = net->d.C, N = net->d.N, n2 = N * N, L = net->d.layers;
+    const int C = plan.C, n2 = plan.n2, L = plan.L;
+    const TowerChoice &tw = plan.tower;
     std::string missing;
     auto get = [&](const std::string &name, size_t want) -> const std::vector<float> * {
         auto it = T.find(name);
@@ -216,7 +212,7 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
         for (int co = 0; co < C; ++co) bias[(size_t)l * C + co] = (float)sh[co];
     }
     std::vector<float> Wp;
-    if (net->use_mfma && net->tower_variant < 4) {
+    if (tw.wp) {
         // B-fragment order: [layer][tap][q][ntile][lane(j + 32 h)][t] = W[tap][cin 8q+4h+t][cout 32 ntile + j]
         const int NT = C / 32, Q = C / 8;
         Wp.resize((size_t)L * 9 * Q * NT * 64 * 4);
@@ -233,16 +229,8 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
                             }
     }
     std::vector<unsigned short> Ws;
-    if (net->tower_variant == 5) {
+    if (tw.s32) {
         const int NT = C / 32;
-        auto f16bits = [](float w, int part) -> unsigned short {
-            const _Float16 hi = (_Float16)w;
-            const _Float16 lo = (_Float16)(w - (float)hi);
-            const _Float16 v = part ? lo : hi;
-            unsigned short bits;
-            memcpy(&bits, &v, 2);
-            return part ? lo_round_bits(bits) : bits;
-        };
         // stem table as K = 27 (tap*3 + colour, padded to 32) x C weights:
         // [kk][ntile][part hi/lo][lane j + 32 h][t] = split(stemT[k = 16 kk + 8 h + t][cout 32 ntile + j])
         Ws.resize((size_t)2 * NT * 2 * 64 * 8);
@@ -254,20 +242,12 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
                         for (int t = 0; t < 8; ++t) {
                             const int j = ln & 31, h = ln >> 5;
                             const int k = 16 * kk + 8 * h + t, co = 32 * nt + j;
-                            Ws[os++] = f16bits(k < 27 ? stemT[(size_t)k * C + co] : 0.0f, part);
+                            Ws[os++] = f16bits_host(k < 27 ? stemT[(size_t)k * C + co] : 0.0f, part);
                         }
     }
     std::vector<unsigned short> Wh16, Ws16;
-    if (net->tower_variant == 4 || net->tower_variant == 5) {
+    if (tw.s16) {
         const int NT16 = C / 16, NCH = C / 64;
-        auto f16bits = [](float w, int part) -> unsigned short {
-            const _Float16 hi = (_Float16)w;
-            const _Float16 lo = (_Float16)(w - (float)hi);
-            const _Float16 v = part ? lo : hi;
-            unsigned short bits;
-            memcpy(&bits, &v, 2);
-            return part ? lo_round_bits(bits) : bits;
-        };
         // 16x16x32 A-operand order: lane (j = lane & 15: output channel in the tile, h = lane >> 4: k-group)
         // holds 8 consecutive k.  Stem: [ntile][hi,lo][lane][t] = split(stemT[k = 8 h + t][cout 16 ntile + j])
         Ws16.resize((size_t)NT16 * 2 * 64 * 8);
@@ -277,7 +257,7 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
                 for (int ln = 0; ln < 64; ++ln)
                     for (int t = 0; t < 8; ++t) {
                         const int j = ln & 15, h = ln >> 4, k = 8 * h + t, co = 16 * nt + j;
-                        Ws16[os++] = f16bits(k < 27 ? stemT[(size_t)k * C + co] : 0.0f, part);
+                        Ws16[os++] = f16bits_host(k < 27 ? stemT[(size_t)k * C + co] : 0.0f, part);
                     }
         // convs, one 32-channel k-step after the other:
         // [layer][tap][64-channel chunk][half][ntile][hi,lo][lane][t]
@@ -299,9 +279,9 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
                                         // group is channel 32 (n >> 1) + 8 lh + 4 (n & 1) + r of the group, so a
                                         // lane's accumulators are 8 consecutive channels per tile pair
                                         // (k_conv_wide_f16x3_s16's 16-byte epilogue pieces)
-                                        if (net->tower_variant == 5)
+                                        if (tw.wide_perm)
                                             co = 64 * (nt / 4) + 32 * ((nt % 4) >> 1) + 8 * (j >> 2) + 4 * (nt & 1) + (j & 3);
-                                        Wh16[o++] = f16bits(Wg[(((size_t)l * 9 + tap) * C + ci) * C + co], part);
+                                        Wh16[o++] = f16bits_host(Wg[(((size_t)l * 9 + tap) * C + ci) * C + co], part);
                                     }
     }
     // heads
@@ -319,15 +299,7 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
     }
     std::vector<unsigned short> Whd16;
     std::vector<float> hbias16(16, 0.f);
-    if (net->tower_variant == 4 && C == 64) {
-        auto f16bits = [](float w, int part) -> unsigned short {
-            const _Float16 hi = (_Float16)w;
-            const _Float16 lo = (_Float16)(w - (float)hi);
-            const _Float16 v = part ? lo : hi;
-            unsigned short bits;
-            memcpy(&bits, &v, 2);
-            return part ? lo_round_bits(bits) : bits;
-        };
+    if (tw.hd16) {
         Whd16.resize((size_t)2 * 2 * 64 * 8);
         size_t oh = 0;
         for (int ks = 0; ks < 2; ++ks)
@@ -336,7 +308,7 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
                     for (int t = 0; t < 8; ++t) {
                         const int o = ln & 15, ci = 32 * ks + 8 * (ln >> 4) + t;
                         const float w = o < 2 ? wv[(size_t)o * C + ci] : o < 6 ? wp[(size_t)(o - 2) * C + ci] : 0.0f;
-                        Whd16[oh++] = f16bits(w, part);
+                        Whd16[oh++] = f16bits_host(w, part);
                     }
         for (int o = 0; o < 6; ++o) hbias16[o] = o < 2 ? bv[o] : bp[o - 2];
     }
@@ -378,20 +350,21 @@ static int pack_host(AzxNet *net, const Plan &plan, const std::map<std::string, 
     if (hipStreamSynchronize(net->stream) != hipSuccess) return azx_net_fail(AZX_EHIP, "net: stream sync before the weight upload failed");
     bool ok = true;
     auto put = [&](const char *name, const void *src, size_t bytes) {
-        void *dst = const_cast<void *>(pack_ptr(net, name));
-        if (!dst) return;                                 // this network's kernels do not read that operand
-        ok = ok && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        void *dst = const_cast<void *>(pack_ptr(net, name));      // ensure_buffers made it from the same plan: a missing one is a bug
+        ok = ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
     };
 #define PUTV(name, vec) put(name, (vec).data(), (vec).size() * sizeof((vec)[0]))
     PUTV("stemT", stemT); PUTV("stem_b", stem_b); PUTV("bias", bias);
-    PUTV("Wg", Wg); PUTV("Wp", Wp); PUTV("Ws", Ws); PUTV("Ws16", Ws16); PUTV("Wh16", Wh16);
-    PUTV("Whd16", Whd16); PUTV("hbias16", hbias16);
+    if (tw.wg) PUTV("Wg", Wg);
+    if (tw.wp) PUTV("Wp", Wp);
+    if (tw.s32) PUTV("Ws", Ws);
+    if (tw.s16) { PUTV("Ws16", Ws16); PUTV("Wh16", Wh16); }
+    if (tw.hd16) { PUTV("Whd16", Whd16); PUTV("hbias16", hbias16); }
     PUTV("wv", wv); PUTV("bv", bv); PUTV("wp", wp); PUTV("bp", bp);
     PUTV("fc2T", fc2T); PUTV("fc2b", *fc2b); PUTV("fc3w", *fc3w); PUTV("fc3b", *fc3b);
     PUTV("mfcT", mfcT); PUTV("mfcb", mfcb); PUTV("hmP", hmP); PUTV("hmV", hmV);
 #undef PUTV
     if (!ok) return azx_net_fail(AZX_EHIP, "net: uploading the packed weights failed");
-    (void)plan;
     return AZX_OK;
 }
 
@@ -488,7 +461,7 @@ static int pack_device(AzxNet *net, const Plan &p) {
         }
         wave_atomic_max(wmax, out);
     });
-    if (p.s32) {
+    if (p.tower.s32) {
         unsigned short *Ws = const_cast<unsigned short *>(d.Ws);
         const int NT = p.NT;
         each(st, (size_t)2 * NT * 64, [=] __device__(size_t i, bool on) {     // [kk][ntile][hi,lo][lane][t]
@@ -504,7 +477,7 @@ static int pack_device(AzxNet *net, const Plan &p) {
             store_frag(base + (size_t)ln * 8, base + (size_t)(64 + ln) * 8, f);
         });
     }
-    if (p.s16) {
+    if (p.tower.s16) {
         unsigned short *Ws16 = const_cast<unsigned short *>(d.Ws16);
         each(st, (size_t)p.NT16 * 64, [=] __device__(size_t i, bool on) {     // [ntile][hi,lo][lane][t]
             if (!on) return;
@@ -521,7 +494,7 @@ static int pack_device(AzxNet *net, const Plan &p) {
     }
 
     // 3. tower filters, BN scale folded in, in the order the launched kernels walk them
-    if (p.wg) {
+    if (p.tower.wg) {
         float *Wg = const_cast<float *>(d.Wg);
         each(st, p.n_Wg, [=] __device__(size_t i, bool on) {                   // [layer][tap][cin][cout]
             float v = 0.f;
@@ -535,7 +508,7 @@ static int pack_device(AzxNet *net, const Plan &p) {
             wave_atomic_max(wmax + 1 + __shfl(l, 0), v);      // 9 C^2 is a multiple of 64: one layer per wave
         });
     }
-    if (p.wp) {
+    if (p.tower.wp) {
         float *Wp = const_cast<float *>(d.Wp);
         const int NT = p.NT, Q = C / 8;
         each(st, p.n_Wp / 4, [=] __device__(size_t i, bool on) {               // [layer][tap][q][ntile][lane][t]
@@ -556,10 +529,10 @@ static int pack_device(AzxNet *net, const Plan &p) {
             wave_atomic_max(wmax + 1 + __shfl(l, 0), m);
         });
     }
-    if (p.s16 && L > 0) {
+    if (p.tower.s16 && L > 0) {
         unsigned short *Wh16 = const_cast<unsigned short *>(d.Wh16);
         const int NT16 = p.NT16, NCH = p.NCH;
-        const bool wide = net->tower_variant == 5;
+        const bool wide = p.tower.wide_perm;
         // [layer][tap][chunk][half][ntile][hi,lo][lane][t]
         each(st, (size_t)L * 9 * NCH * 2 * NT16 * 64, [=] __device__(size_t i, bool on) {
             float m = 0.f;
@@ -603,7 +576,7 @@ static int pack_device(AzxNet *net, const Plan &p) {
             }
             wave_atomic_max(wmax + 1 + L, v);
         });
-        if (p.hd16) {
+        if (p.tower.hd16) {
             unsigned short *Whd16 = const_cast<unsigned short *>(d.Whd16);
             each(st, (size_t)2 * 64, [=] __device__(size_t i, bool on) {        // [kstep][hi,lo][lane][t]
                 if (!on) return;
@@ -721,11 +694,10 @@ int azx_net_set_weights(AzxNet *net, int n, const char *const *names, const void
         for (int g = 0; g < L + 2; ++g) memcpy(&wmax[g], &net->wmax_host[g], 4);
     }
     // range guard: the split-f16 towers carry every folded weight as hi + lo f16 halves
-    const bool f16 = net->tower_variant == 4 || net->tower_variant == 5;
     for (int g = 0; g < L + 2; ++g) {
         const bool finite = wmax[g] == wmax[g] && wmax[g] < INFINITY;
-        if (finite && (!f16 || wmax[g] <= F16_MAX)) continue;
-        if (g == L + 1 && finite && !plan.hd16) continue;       // the head convs are only split when the fused tower runs them
+        if (finite && (!plan.tower.f16_weights || wmax[g] <= F16_MAX)) continue;
+        if (g == L + 1 && finite && !plan.tower.hd16) continue;       // the head convs are only split when the fused tower runs them
         char what[160];
         if (g == 0) snprintf(what, sizeof what, "conv1.weight folded with bn1 and the embedding");
         else if (g <= L) snprintf(what, sizeof what, "resblocks.%d.conv%d.weight folded with resblocks.%d.bn%d", (g - 1) / 2, (g - 1) % 2 + 1, (g - 1) / 2, (g - 1) % 2 + 1);

@@ -54,11 +54,43 @@ static inline unsigned short lo_round_bits(unsigned short bits) {
     return (unsigned short)((bits + LO_RND) & LO_MASK);
 }
 
+// Which tower a (board, blocks, channels) shape runs and everything the host must know about it.  tower_choose
+// (net_kernels.hip) fills one in per network, once; beside it only run_net's launch switch names the kinds.  A new tower
+// is a new kind, its case in tower_choose and its launch in run_net.
+enum class TowerKind {
+    Generic,                          // k_stem_generic + k_conv_generic per layer (VALU): any shape
+    Mfma64x4, Mfma64x6, Mfma32x6,     // k_tower_mfma<C,MT,BPB,WM,WN> (fp32 MFMA): <64,4,2,1,2>, <64,6,1,2,2>, <32,6,2,2,1>
+    Fused,                            // k_tower_f16x3_s16 | k_tower_f16_s16: 64 channels, <= 121 cells, >= 1 block
+    Wide                              // k_stem_wide_* + k_conv_wide_*_s16 per layer: channels a multiple of 128
+};
+
+struct TowerChoice {
+    TowerKind kind = TowerKind::Generic;
+    bool f16 = false;                 // the plain-f16 kernels of the kind (AZX_FLAG_TOWER_F16 / AZX_TOWER=f16): one product, same packs
+    const char *name = "";            // azx_net_kernel_info's tower
+    const char *precision = "";       // ... and its AZX_TOWER= field: "fp32" (forced), "f16" or "default"
+    // weight operands the kernels read (net_pack.hip packs these and no others)
+    bool wg = false;                  // Wg: generic [layer][tap][cin][cout]
+    bool wp = false;                  // Wp: fp32 MFMA B fragments
+    bool s32 = false;                 // Ws: the stem table in 32x32x16 fragment order (the wide stem)
+    bool s16 = false;                 // Ws16, Wh16: hi + lo f16 halves in 16x16x32 fragment order
+    bool hd16 = false;                // Whd16, hbias16: the heads' six 1x1 filters as one more MFMA layer
+    bool wide_perm = false;           // Wh16's output channels in the wide tower's order (16-byte epilogue pieces)
+    bool f16_weights = false;         // every folded weight is carried as f16 halves: the weight-range guard applies
+    size_t lds_bytes = 0;             // dynamic LDS of the tower kernel (of each layer's launch for Wide)
+    // scratch buffers
+    bool act23 = false;               // act2, act3: the layer-by-layer VALU tower's ping-pong
+    bool wide_xy = false;             // wideX, wideY: the wide tower's split-f16 images
+    bool hfeat = false;               // the tower leaves the six head planes in hfeat (k_heads_mfma's input)
+    bool tile_map = false;            // reads NetDev::tile_map / tile_skip, its two boards AZX_TOWER_BOARD_GAP rows apart
+    bool rows_splittable = true;      // launches on disjoint scratch rows may overlap (azx_net_rows_splittable)
+};
+
 struct AzxNet {
     NetDev d;
     int max_evals = 0;
     bool ready = false;
-    bool use_mfma = false;
+    TowerChoice tower;
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
     float *act = nullptr, *act2 = nullptr, *act3 = nullptr;   // [E][ncells][C]
@@ -69,9 +101,6 @@ struct AzxNet {
     uint8_t *hb_board = nullptr;
     int32_t *hb_flip = nullptr;
     float *hb_value = nullptr;
-    size_t lds_bytes = 0;
-    int tower_variant = 0;
-    bool tower_f16 = false;     // variants 4 and 5: k_tower_f16_s16 / k_stem_wide_f16 + k_conv_wide_f16_s16 (one product, AZX_FLAG_TOWER_F16 / AZX_TOWER=f16) read the same packs
     // wide tower: the second half of a batch's boards runs its layer launches on a second stream
     hipStream_t stream2[3] = {nullptr, nullptr, nullptr};
     std::vector<uint32_t> cu_mask;   // azx_net_set_stream: the side streams are made on the engine's CU mask (empty = all CUs)
@@ -79,7 +108,7 @@ struct AzxNet {
     bool streams_ok = false;
     // diagnostic switches, read once per engine by azx_net_create (azx_net_kernel_info reports the outcome)
     int opt_wsplit = 2;         // AZX_WIDE_STREAMS: streams the wide tower's layer launches are spread over
-    bool opt_heads_mfma = true; // AZX_HEADS=valu: the scalar-FMA k_heads behind the fused tower too
+    bool heads_mfma = false;    // k_heads_mfma on the planes a tower left in hfeat (<= 128 cells; AZX_HEADS=valu: k_heads there too)
     std::string info;
     // ---- weight packing (net_pack.hip) ----
     bool pack_on_host = false;       // AZX_PACK=host: the host reference pack (debug / bit-identity tests)

@@ -1108,6 +1108,19 @@ class Tournament:
         return out
 
 
+def tower_choice(board_size, num_blocks, base_chans, flags=0):
+    """azx_debug_tower_choice: the `net=` field of kernel_info() of an EVAL_RESNET engine of this shape and these flags
+    created now (AZX_TOWER, AZX_HEADS, AZX_TOWER_TILES, AZX_WIDE_STREAMS and AZX_PACK as the environment holds them) --
+    which tower and heads kernels it would launch -- from the code the engine itself chooses with, on the host (no GPU
+    is needed).  AzxError with the engine's code and message where it would refuse the network."""
+    L = _lib.lib()
+    buf = C.create_string_buffer(512)
+    rc = L.azx_debug_tower_choice(int(board_size), int(num_blocks), int(base_chans), int(flags), buf, len(buf))
+    if rc < 0:
+        check(rc)
+    return buf.value.decode()
+
+
 def playout_cap_is_full(seed, uid, ply, full_prob):
     """azx_playout_cap_is_full: whether ply `ply` (from the empty board) of game `uid` of an engine created with
     `seed` is a full search under set_playout_cap(full_prob, ...) -- the function the kernels use, on the host (no

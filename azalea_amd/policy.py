@@ -92,7 +92,7 @@ def tower_flags(pol) -> int:
         raise ValueError("tower_precision='f16' selects a kernel of the built-in HexNetwork tower: this policy's "
                          "network runs through an external evaluator")
     n, blocks, chans = int(pol.board_size), int(pol.num_blocks), int(pol.base_chans)
-    fused, wide = chans == 64 and n * n <= 121, chans >= 128 and chans % 128 == 0      # net.h: azx_net_has_f16_tower
+    fused, wide = chans == 64 and n * n <= 121, chans >= 128 and chans % 128 == 0      # net_kernels.hip: tower_choose
     if not ((fused or wide) and blocks >= 1):
         raise ValueError("tower_precision='f16' needs a shape with a plain-f16 tower -- the fused tower's (64 channels, at "
                          "most 121 cells) or the wide tower's (a multiple of 128 channels) -- and at least one block: got "

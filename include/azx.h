@@ -786,6 +786,15 @@ int azx_debug_stagger(azx_engine *e, int32_t *out4);
  * engine runs (AZX_TOWER_TILES=edge|rows; engines on another tower report the setting, which they do not use).  Results do not depend on the map, bit for bit.
  * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_tower_tiles). */
 int azx_debug_tower_tiles(int board_size, const char *map, uint8_t *rows256, uint32_t *skip4, int32_t *light_slot);
+/* tests, host only (no engine, no GPU): which tower and heads kernels azx_create would give an AZX_EVAL_RESNET engine
+ * of this shape and these flags (AZX_FLAG_TOWER_F16 is the one that matters) under the switches AZX_TOWER, AZX_HEADS,
+ * AZX_TOWER_TILES, AZX_WIDE_STREAMS and AZX_PACK as the environment holds them now.  Writes the text of azx_kernel_info's
+ * `net=` field for that engine to buf (truncated to cap - 1 bytes) and returns its full length; where azx_create would
+ * refuse the network, returns its error code (AZX_EINVAL: the shape, or AZX_FLAG_TOWER_F16 on a shape without a plain-f16
+ * tower or against AZX_TOWER=fp32) with its message in azx_last_error.  The engine and this call build the text with
+ * the same code.
+ * An addition WITHIN ABI revision 7: callers detect it by symbol (dlsym azx_debug_tower_choice). */
+int azx_debug_tower_choice(int board_size, int num_blocks, int base_chans, int flags, char *buf, int cap);
 
 /* ---- evaluation matches between two engines, entirely on the device -------------------------
  * An addition WITHIN ABI revision 7 (azx_version stays 7): callers detect it by symbol (dlsym azx_match_create).

@@ -20,5 +20,6 @@ _lib.OPTIONAL.update(["azx_set_selfplay_openings", "azx_selfplay_opening_word", 
 _lib.OPTIONAL.update(["azx_set_gumbel", "azx_get_gumbel", "azx_gumbel_stats", "azx_gumbel_variate", "azx_selftest_gumbel",
                       "azx_gumbel_state"])
 _lib.OPTIONAL.update(["azx_set_rollout_evaluator", "azx_rollout_value", "azx_selftest_rollout", "azx_rollout_stats"])
+_lib.OPTIONAL.update(["azx_debug_tower_choice"])
 sys.argv = ["bench.py"] + sys.argv[2:]
 runpy.run_path(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), run_name="__main__")
