@@ -2705,19 +2705,27 @@ extern "C" int azx_selfplay_openings_stats(azx_engine *e, int64_t cap, int64_t *
 // and reads back ONE word, the number of games decided.  An engine with a registered external evaluator cannot be
 // enqueued whole: the host takes part at each of its evaluation points.  Its search is then a cursor (ExtCursor)
 // that the ply advances point by point, after everything that needs no host is on the streams and in turn with the
-// other engine's cursor when both are external (match_ply_searches).
-struct azx_match {
-    azx_engine *a = nullptr, *b = nullptr;
-    MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, -1};
-    int64_t out_cap = 0, moves_cap = 0;          // games the outcome / length and the moves buffers hold
-    int16_t *moves_buf = nullptr;
+// other engine's cursor when both are external (ply_searches).
+//
+// A tournament (further down) is P such matches side by side in the same ply loop.  What the two handles share is a
+// PlyLoop, and everything the host does around the two kernel families is written once, over it: the handle's shared
+// state, the setters, the prologue and epilogue of a play call and the ply loop itself.  A handle adds what is its
+// own: the device state of its kernel family (MatchDev / TourDev) and the result buffers behind it.
+struct PlyLoop {
+    std::vector<azx_engine *> eng;               // a match: {a, b}.  Engine 0's stream carries the turn and step kernels
+    const char *noun = "match";                  // the handle in messages: "match" or "tournament"
+    const char *letters = nullptr;               // the engines in messages: "ab" for a match, null = by index
+    bool interleave = true;                      // AZX_MATCH_INTERLEAVE=0 (a match only): each engine's whole search in turn
     unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, t0 = nullptr, t1 = nullptr;
-    bool interleave = true;                      // AZX_MATCH_INTERLEAVE=0: a's whole search, then b's (diagnostic)
-    bool harvest = false;                        // azx_match_set_harvest: won games' replay rows go to a's harvest queue
-    int first_mode = -1;                         // azx_match_set_first_mover
-    int64_t rows_last = 0;                       // rows the last azx_match_play harvested
-    MatchBook book = {nullptr, nullptr, 0, 0};   // azx_match_set_openings: device tables the match owns (n == 0: none)
+    hipEvent_t ev_fork = nullptr, t0 = nullptr, t1 = nullptr;
+    std::vector<hipEvent_t> ev_join;             // [K - 1]: engine k's stream back into engine 0's
+    std::vector<ExtCursor> cur;                  // [K]: the external engines' searches of the current ply
+    int sink = -1;                               // *_set_harvest: the engine whose harvest queue takes the won games' rows
+    int first_mode = -1;                         // *_set_first_mover
+    int64_t rows_last = 0;                       // rows the last play call harvested
+    MatchBook book = {nullptr, nullptr, 0, 0};   // *_set_openings: device tables the handle owns (n == 0: none)
+
+    std::string name(int k) const { return letters ? std::string(1, letters[k]) : std::to_string(k); }
 };
 
 static const char *match_engine_problem(const azx_engine *e) {
@@ -2727,19 +2735,71 @@ static const char *match_engine_problem(const azx_engine *e) {
     return nullptr;
 }
 
+// the shared state of a new handle, after the handle's own allocations (`err`: how those went) in one chain: whatever
+// fails, the caller destroys the partly built handle and returns AZX_ENOMEM
+static hipError_t loop_create(PlyLoop &L, hipError_t err, azx_engine *const *engines, int K, const char *noun,
+                              const char *letters) {
+    L.eng.assign(engines, engines + K);
+    L.noun = noun;
+    L.letters = letters;
+    L.ev_join.assign((size_t)K - 1, nullptr);
+    L.cur.assign((size_t)K, ExtCursor());
+    if (err == hipSuccess) err = hipHostMalloc((void **)&L.host_word, sizeof(unsigned long long), hipHostMallocDefault);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming);
+    for (hipEvent_t &ev : L.ev_join)
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventCreate(&L.t0);
+    if (err == hipSuccess) err = hipEventCreate(&L.t1);
+    return err;
+}
+
+// frees the device buffers `own` of a handle and its shared state (the caller holds the device and deletes the handle)
+static void loop_destroy(PlyLoop &L, std::initializer_list<const void *> own) {
+    for (const void *p : own)
+        if (p) (void)hipFree(const_cast<void *>(p));
+    for (const void *p : {(const void *)L.book.moves, (const void *)L.book.len})
+        if (p) (void)hipFree(const_cast<void *>(p));
+    if (L.host_word) (void)hipHostFree(L.host_word);
+    for (hipEvent_t ev : {L.ev_fork, L.t0, L.t1})
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : L.ev_join)
+        if (ev) (void)hipEventDestroy(ev);
+}
+
+// the bodies of azx_{match,tournament}_set_first_mover / _set_openings / _rows (L: null for a null handle, which
+// `noun` names in the message)
+static int loop_set_first_mover(PlyLoop *L, const char *noun, int mode) {
+    if (mode < -1 || mode > 1) return fail(AZX_EINVAL, "first mover mode %d: -1 (agent u & 1), 0 or 1", mode);
+    if (!L) return fail(AZX_EINVAL, "null %s", noun);
+    L->first_mode = mode;
+    return AZX_OK;
+}
+
+static int loop_set_openings(PlyLoop *L, const char *noun, int n_openings, int stride, const int16_t *moves,
+                             const int32_t *lengths) {
+    if (!L) return fail(AZX_EINVAL, "null %s", noun);
+    TRY(openings_args(n_openings, stride, moves, lengths));
+    ENGINE_GUARD(L->eng[0]);
+    return book_set(&L->book, L->eng[0]->d.N, n_openings, stride, moves, lengths);
+}
+
+static int loop_rows(const PlyLoop *L, int64_t *rows_out) {
+    if (!L || !rows_out) return fail(AZX_EINVAL, "null argument");
+    *rows_out = L->rows_last;
+    return AZX_OK;
+}
+
+struct azx_match {
+    PlyLoop loop;
+    MatchDev m = {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, -1};
+    int16_t *moves_buf = nullptr;
+    int64_t out_cap = 0, len_cap = 0, moves_cap = 0;     // elements the outcome, length and moves buffers hold
+};
+
 extern "C" void azx_match_destroy(azx_match *m) {
     if (!m) return;
-    DevGuard guard(m->a->cfg.device);
-    if (m->m.slot_game) (void)hipFree(m->m.slot_game);
-    if (m->m.ctr) (void)hipFree(m->m.ctr);
-    if (m->m.outcome) (void)hipFree(m->m.outcome);
-    if (m->m.length) (void)hipFree(m->m.length);
-    if (m->moves_buf) (void)hipFree(m->moves_buf);
-    if (m->book.moves) (void)hipFree(const_cast<int16_t *>(m->book.moves));
-    if (m->book.len) (void)hipFree(const_cast<int32_t *>(m->book.len));
-    if (m->host_word) (void)hipHostFree(m->host_word);
-    for (hipEvent_t ev : {m->ev_fork, m->ev_join, m->t0, m->t1})
-        if (ev) (void)hipEventDestroy(ev);
+    DevGuard guard(m->loop.eng[0]->cfg.device);
+    loop_destroy(m->loop, {m->m.slot_game, m->m.ctr, m->m.outcome, m->m.length, m->moves_buf});
     delete m;
 }
 
@@ -2754,16 +2814,11 @@ extern "C" int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out) {
     if (const char *why = match_engine_problem(b)) return fail(AZX_EINVAL, "engine b %s", why);
     DevGuard guard(a->cfg.device);
     azx_match *m = new azx_match();
-    m->a = a;
-    m->b = b;
-    { const char *v = getenv("AZX_MATCH_INTERLEAVE"); m->interleave = !(v && atoi(v) == 0); }
+    azx_engine *const both[2] = {a, b};
     hipError_t err = hipMalloc((void **)&m->m.slot_game, sizeof(int64_t) * (size_t)a->d.G);
     if (err == hipSuccess) err = hipMalloc((void **)&m->m.ctr, sizeof(unsigned long long) * MCTR_COUNT);
-    if (err == hipSuccess) err = hipHostMalloc((void **)&m->host_word, sizeof(unsigned long long), hipHostMallocDefault);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreate(&m->t0);
-    if (err == hipSuccess) err = hipEventCreate(&m->t1);
+    err = loop_create(m->loop, err, both, 2, "match", "ab");
+    { const char *v = getenv("AZX_MATCH_INTERLEAVE"); m->loop.interleave = !(v && atoi(v) == 0); }
     if (err != hipSuccess) {
         azx_match_destroy(m);
         return fail(AZX_ENOMEM, "allocating the match state failed: %s", hipGetErrorString(err));
@@ -2774,30 +2829,18 @@ extern "C" int azx_match_create(azx_engine *a, azx_engine *b, azx_match **out) {
 
 extern "C" int azx_match_set_harvest(azx_match *m, int on) {
     if (!m) return fail(AZX_EINVAL, "null match");
-    m->harvest = on != 0;
+    m->loop.sink = on ? 0 : -1;                          // won games' replay rows go to a's harvest queue
     return AZX_OK;
 }
 
 extern "C" int azx_match_set_first_mover(azx_match *m, int mode) {
-    if (mode < -1 || mode > 1) return fail(AZX_EINVAL, "first mover mode %d: -1 (agent u & 1), 0 or 1", mode);
-    if (!m) return fail(AZX_EINVAL, "null match");
-    m->first_mode = mode;
-    return AZX_OK;
+    return loop_set_first_mover(m ? &m->loop : nullptr, "match", mode);
 }
-
 extern "C" int azx_match_set_openings(azx_match *m, int n_openings, int stride, const int16_t *moves,
                                       const int32_t *lengths) {
-    if (!m) return fail(AZX_EINVAL, "null match");
-    TRY(openings_args(n_openings, stride, moves, lengths));
-    ENGINE_GUARD(m->a);
-    return book_set(&m->book, m->a->d.N, n_openings, stride, moves, lengths);
+    return loop_set_openings(m ? &m->loop : nullptr, "match", n_openings, stride, moves, lengths);
 }
-
-extern "C" int azx_match_rows(azx_match *m, int64_t *rows_out) {
-    if (!m || !rows_out) return fail(AZX_EINVAL, "null argument");
-    *rows_out = m->rows_last;
-    return AZX_OK;
-}
+extern "C" int azx_match_rows(azx_match *m, int64_t *rows_out) { return loop_rows(m ? &m->loop : nullptr, rows_out); }
 
 // the harvest queue of a harvesting match / tournament: no ring, room for every game at its longest (`cells` plies)
 static int harvest_setup(azx_engine *sink, int64_t n_games) {
@@ -2814,67 +2857,173 @@ static int harvest_setup(azx_engine *sink, int64_t n_games) {
     return AZX_OK;
 }
 
-// room for n_games results (and move records when asked for)
-static int match_reserve(azx_match *m, int64_t n_games, bool want_moves) {
-    if (n_games > m->out_cap) {
-        if (m->m.outcome) (void)hipFree(m->m.outcome);
-        if (m->m.length) (void)hipFree(m->m.length);
-        m->m.outcome = nullptr; m->m.length = nullptr; m->out_cap = 0;
-        if (hipMalloc((void **)&m->m.outcome, (size_t)n_games) != hipSuccess ||
-            hipMalloc((void **)&m->m.length, sizeof(int16_t) * (size_t)n_games) != hipSuccess)
-            return fail(AZX_ENOMEM, "hipMalloc of the results of %lld games failed", (long long)n_games);
-        m->out_cap = n_games;
+// a device buffer of at least `count` elements (grown, never shrunk; the contents are not kept)
+template <typename T>
+static int loop_grow(const PlyLoop &L, T **p, int64_t *cap, int64_t count, const char *what) {
+    if (count <= *cap) return AZX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc((void **)p, sizeof(T) * (size_t)count) != hipSuccess)
+        return fail(AZX_ENOMEM, "hipMalloc of the %s's %s (%lld) failed", L.noun, what, (long long)count);
+    *cap = count;
+    return AZX_OK;
+}
+
+// a failure inside a ply: nothing any engine has queued is left running, and the message says whose engine it was
+static int loop_fail(const PlyLoop &L, int k, int rc) {
+    for (azx_engine *e : L.eng) (void)hipStreamSynchronize(e->stream);
+    if (rc == AZX_EEXTERNAL) g_err = "engine " + L.name(k) + ": " + g_err;
+    return rc;
+}
+#define LOOP_TRY(k, expr)                           \
+    do {                                            \
+        int _rc = (expr);                           \
+        if (_rc) return loop_fail(L, (k), _rc);     \
+    } while (0)
+
+// Every engine's search and move draw of one ply, each on its engine's stream (all forked from engine 0's).
+// Interleaved: first what needs no host -- the whole search and draw of every device-evaluated engine -- then the
+// external engines' cursors in turn, so that each engine's next tree phase is on its stream before the host waits
+// for another engine's evaluation point.  Plain order: each engine's whole search in turn.  The streams' contents,
+// and so the games, are the same either way.
+static int ply_searches(PlyLoop &L) {
+    const int K = (int)L.eng.size();
+    if (!L.interleave) {
+        for (int k = 0; k < K; ++k) {
+            LOOP_TRY(k, enqueue_search(L.eng[k], false));
+            azx_launch_choose(L.eng[k]->d, L.eng[k]->stream);
+        }
+        return AZX_OK;
     }
-    if (want_moves && n_games > m->moves_cap) {
-        if (m->moves_buf) (void)hipFree(m->moves_buf);
-        m->moves_buf = nullptr; m->moves_cap = 0;
-        if (hipMalloc((void **)&m->moves_buf, sizeof(int16_t) * (size_t)n_games * m->a->d.ncells) != hipSuccess)
-            return fail(AZX_ENOMEM, "hipMalloc of the move records of %lld games failed", (long long)n_games);
-        m->moves_cap = n_games;
+    for (int k = 0; k < K; ++k)
+        if (!ext_registered(L.eng[k])) {
+            LOOP_TRY(k, enqueue_search(L.eng[k], false));
+            azx_launch_choose(L.eng[k]->d, L.eng[k]->stream);
+        }
+    for (int k = 0; k < K; ++k) {
+        L.cur[k] = ExtCursor();
+        if (ext_registered(L.eng[k])) LOOP_TRY(k, ext_search_begin(L.eng[k], &L.cur[k], false));
+    }
+    for (bool busy = true; busy;) {
+        busy = false;
+        for (int k = 0; k < K; ++k)
+            if (!L.cur[k].done) {
+                LOOP_TRY(k, ext_search_resume(L.eng[k], &L.cur[k]));
+                busy = true;
+            }
+    }
+    for (int k = 0; k < K; ++k)
+        if (ext_registered(L.eng[k])) azx_launch_choose(L.eng[k]->d, L.eng[k]->stream);
+    return AZX_OK;
+}
+
+// What a play call does before anything of its own reaches the device (the caller holds the device): the refusals,
+// `n_stats` stats blocks zeroed, and every engine's row area and noise.  The move draw records a replay row per draw
+// (choose_body), so the row area must exist: a game draws at most ceil(cells / 2) times per engine and n_rows restarts
+// with every game; the sink's is its harvest queue instead.
+static int loop_begin(PlyLoop &L, int64_t n_games, azx_match_stats *stats, int n_stats) {
+    const int K = (int)L.eng.size();
+    TRY(refuse_selfplay_options(L.eng.data(), K, L.noun, L.letters));
+    for (int k = 0; k < K; ++k)
+        if (const char *why = match_engine_problem(L.eng[k])) return fail(AZX_ESTATE, "engine %s %s", L.name(k).c_str(), why);
+    for (azx_engine *e : L.eng) TRY(ext_refuse(e));
+    if (stats) memset(stats, 0, sizeof *stats * (size_t)n_stats);
+    L.rows_last = 0;
+    for (int k = 0; k < K; ++k) {
+        azx_engine *e = L.eng[k];
+        if (k == L.sink) TRY(harvest_setup(e, n_games));
+        else TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
+        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
     }
     return AZX_OK;
 }
 
-// a failure inside a ply: nothing either engine has queued is left running, and the message says whose engine it was
-static int match_fail(azx_match *m, const azx_engine *e, int rc) {
-    (void)hipStreamSynchronize(m->a->stream);
-    (void)hipStreamSynchronize(m->b->stream);
-    if (rc == AZX_EEXTERNAL) g_err = std::string("engine ") + (e == m->a ? "a" : "b") + ": " + g_err;
-    return rc;
-}
-#define MATCH_TRY(e, expr)                           \
-    do {                                             \
-        int _rc = (expr);                            \
-        if (_rc) return match_fail(m, (e), _rc);     \
-    } while (0)
-
-// Both engines' searches and move draws of one ply, each on its engine's stream (b's stream has been forked).
-// Interleaved: first what needs no host -- the whole search and draw of a device-evaluated engine -- then the
-// external engines' cursors in turn, so that each engine's next tree phase is on its stream before the host waits
-// for the other engine's evaluation point.  Plain order: a's whole search, then b's.  The streams' contents, and so
-// the games, are the same either way.
-static int match_ply_searches(azx_match *m) {
-    azx_engine *eng[2] = {m->a, m->b};
-    if (!m->interleave) {
-        for (azx_engine *e : eng) {
-            MATCH_TRY(e, enqueue_search(e, false));
-            azx_launch_choose(e->d, e->stream);
+// The ply loop, from the handle's games in their slots (the caller has synchronised engine 0's stream after its init
+// kernels) until `*decided_dev` says all n_games are decided.  Per ply: turn() on engine 0's stream, the other
+// streams forked from it, every engine's search and draw, the streams joined, step(), and ONE word read back.
+template <typename Turn, typename Step>
+static int loop_play(PlyLoop &L, const unsigned long long *decided_dev, int64_t n_games, int64_t max_plies,
+                     const Turn &turn, const Step &step) {
+    const int K = (int)L.eng.size();
+    const hipStream_t s0 = L.eng[0]->stream;
+    HIPCHECK(hipEventRecord(L.t0, s0));
+    for (int64_t plies = 0;; ++plies) {
+        if (plies > max_plies)
+            return fail(AZX_ESTATE, "%s: %lld plies without deciding all %lld games (internal error)", L.noun,
+                        (long long)plies, (long long)n_games);
+        turn();
+        HIPCHECK(hipEventRecord(L.ev_fork, s0));
+        for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(L.eng[k]->stream, L.ev_fork, 0));
+        TRY(ply_searches(L));
+        for (int k = 1; k < K; ++k) {
+            HIPCHECK(hipEventRecord(L.ev_join[k - 1], L.eng[k]->stream));
+            HIPCHECK(hipStreamWaitEvent(s0, L.ev_join[k - 1], 0));
         }
-        return AZX_OK;
+        step();
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(L.host_word, decided_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s0));
+        // the error word of each external search's last import rides on the same read-back (every stream has joined)
+        for (azx_engine *e : L.eng)
+            if (ext_registered(e)) TRY(ext_info_enqueue(e, s0));
+        HIPCHECK(hipStreamSynchronize(s0));
+        for (int k = 0; k < K; ++k)
+            if (ext_registered(L.eng[k])) LOOP_TRY(k, ext_info_take(L.eng[k]));
+        if (*L.host_word >= (unsigned long long)n_games) break;
     }
-    ExtCursor cur[2];
-    for (azx_engine *e : eng)
-        if (!ext_registered(e)) {
-            MATCH_TRY(e, enqueue_search(e, false));
-            azx_launch_choose(e->d, e->stream);
-        }
-    for (int i = 0; i < 2; ++i)
-        if (ext_registered(eng[i])) MATCH_TRY(eng[i], ext_search_begin(eng[i], &cur[i], false));
-    while (!cur[0].done || !cur[1].done)
-        for (int i = 0; i < 2; ++i)
-            if (!cur[i].done) MATCH_TRY(eng[i], ext_search_resume(eng[i], &cur[i]));
-    for (azx_engine *e : eng)
-        if (ext_registered(e)) azx_launch_choose(e->d, e->stream);
+    HIPCHECK(hipEventRecord(L.t1, s0));
+    return AZX_OK;
+}
+
+static void fill_match_stats(const unsigned long long *ctr, float ms, azx_match_stats *st) {
+    st->games = (int64_t)ctr[MCTR_DECIDED];
+    st->wins[0] = (int64_t)ctr[MCTR_WINS0];
+    st->wins[1] = (int64_t)ctr[MCTR_WINS1];
+    st->first_player_wins = (int64_t)ctr[MCTR_FIRST_WINS];
+    st->voided = (int64_t)ctr[MCTR_VOIDED];
+    st->plies = (int64_t)ctr[MCTR_PLIES];
+    st->seconds = ms * 1e-3;
+}
+
+// the device side of a finished play call's results: P counter blocks (one per pair; a match has one) and the records
+struct LoopResults {
+    const unsigned long long *ctr;
+    const int8_t *outcome;
+    const int16_t *length;
+    const int16_t *moves;
+};
+
+// What a play call does after its ply loop: the results to the caller's arrays, every engine left as azx_reset leaves
+// it (fresh games, all active, its own uid numbering), the stats of the P blocks, and the checks that come last.
+static int loop_finish(PlyLoop &L, const LoopResults &dev, int P, int64_t n_games, int8_t *outcome, int16_t *length,
+                       int16_t *moves, azx_match_stats *stats) {
+    azx_engine *sink = L.sink >= 0 ? L.eng[(size_t)L.sink] : nullptr;
+    const hipStream_t s0 = L.eng[0]->stream;
+    const size_t ncells = (size_t)L.eng[0]->d.ncells;
+    std::vector<unsigned long long> ctr((size_t)P * MCTR_COUNT);
+    unsigned long long rows = 0, lost = 0;
+    HIPCHECK(hipMemcpyAsync(ctr.data(), dev.ctr, sizeof(unsigned long long) * ctr.size(), hipMemcpyDeviceToHost, s0));
+    if (sink) HIPCHECK(hipMemcpyAsync(&rows, sink->d.q_count, sizeof rows, hipMemcpyDeviceToHost, s0));
+    if (outcome) HIPCHECK(hipMemcpyAsync(outcome, dev.outcome, (size_t)n_games, hipMemcpyDeviceToHost, s0));
+    if (length) HIPCHECK(hipMemcpyAsync(length, dev.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, s0));
+    if (moves) HIPCHECK(hipMemcpyAsync(moves, dev.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, s0));
+    for (azx_engine *e : L.eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 1, s0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s0));
+    if (stats) {
+        float ms = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms, L.t0, L.t1));
+        for (int s = 0; s < P; ++s) fill_match_stats(ctr.data() + (size_t)s * MCTR_COUNT, ms, stats + s);
+    }
+    for (int s = 0; s < P; ++s) lost += ctr[(size_t)s * MCTR_COUNT + MCTR_ROWS_LOST];
+    if (lost)
+        return fail(AZX_ESTATE, "%s: %llu replay rows of finished games did not fit the harvest queue of %lld rows "
+                    "or did not add up to their games (internal error)", L.noun, lost, (long long)(sink ? sink->d.q_cap : 0));
+    if (sink) {                                          // the rows stay readable until the sink's next play call
+        L.rows_last = (int64_t)rows;
+        sink->q_rows_valid = (int64_t)rows;
+    }
+    for (azx_engine *e : L.eng) TRY(check_net_range(e));
     return AZX_OK;
 }
 
@@ -2882,32 +3031,21 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
                               int16_t *moves, azx_match_stats *stats) {
     if (!m) return fail(AZX_EINVAL, "null match");
     if (first_game < 0 || n_games < 1) return fail(AZX_EINVAL, "first_game must be >= 0 and n_games >= 1");
-    azx_engine *a = m->a, *b = m->b;
-    azx_engine *const both[2] = {a, b};
-    TRY(refuse_selfplay_options(both, 2, "match", "ab"));
+    PlyLoop &L = m->loop;
+    azx_engine *a = L.eng[0], *b = L.eng[1];
     ENGINE_GUARD(a);
-    if (const char *why = match_engine_problem(a)) return fail(AZX_ESTATE, "engine a %s", why);
-    if (const char *why = match_engine_problem(b)) return fail(AZX_ESTATE, "engine b %s", why);
-    TRY(ext_refuse(a));
-    TRY(ext_refuse(b));
-    if (stats) memset(stats, 0, sizeof *stats);
+    TRY(loop_begin(L, n_games, stats, 1));
     const int G = a->d.G, ncells = a->d.ncells;
-    const hipStream_t sa = a->stream, sb = b->stream;
-    // the move draw records a replay row per draw (choose_body): the row area must exist; a game draws at most
-    // ceil(cells / 2) times per engine and n_rows restarts with every game
-    m->rows_last = 0;
-    for (azx_engine *e : {a, b}) {
-        if (m->harvest && e == a) TRY(harvest_setup(e, n_games));
-        else TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
-        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
-    }
-    TRY(match_reserve(m, n_games, moves != nullptr));
+    const hipStream_t sa = a->stream;
+    TRY(loop_grow(L, &m->m.outcome, &m->out_cap, n_games, "outcomes"));
+    TRY(loop_grow(L, &m->m.length, &m->len_cap, n_games, "lengths"));
+    if (moves) TRY(loop_grow(L, &m->moves_buf, &m->moves_cap, n_games * ncells, "move records"));
     MatchDev M = m->m;
     M.first_game = first_game;
     M.n_games = n_games;
-    M.harvest = m->harvest ? 1 : 0;
-    M.first_mode = m->first_mode;
-    M.book = m->book;
+    M.harvest = L.sink >= 0 ? 1 : 0;
+    M.first_mode = L.first_mode;
+    M.book = L.book;
     M.moves = moves ? m->moves_buf : nullptr;
     if (M.moves) HIPCHECK(hipMemsetAsync(M.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, sa));
     unsigned long long ctr0[MCTR_COUNT] = {0};
@@ -2920,65 +3058,12 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
     if (M.book.n > 0) azx_launch_match_open(a->d, b->d, M, sa);      // the slots' first games from their openings
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(sa));                  // (ctr0 is on this frame)
-    HIPCHECK(hipEventRecord(m->t0, sa));
 
     // every game ends within `cells` plies and a slot plays its games back to back
     const int64_t max_plies = ((n_games + G - 1) / G + 1) * (int64_t)(ncells + 1);
-    int64_t plies = 0;
-    for (;; ++plies) {
-        if (plies > max_plies)
-            return fail(AZX_ESTATE, "match: %lld plies without deciding all %lld games (internal error)",
-                        (long long)plies, (long long)n_games);
-        azx_launch_match_turn(a->d, b->d, M, sa);
-        HIPCHECK(hipEventRecord(m->ev_fork, sa));
-        HIPCHECK(hipStreamWaitEvent(sb, m->ev_fork, 0));
-        TRY(match_ply_searches(m));
-        HIPCHECK(hipEventRecord(m->ev_join, sb));
-        HIPCHECK(hipStreamWaitEvent(sa, m->ev_join, 0));
-        azx_launch_match_step(a->d, b->d, M, sa);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(m->host_word, M.ctr + MCTR_DECIDED, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa));
-        // the error word of each external search's last import rides on the same read-back (a's stream has joined b's)
-        for (azx_engine *e : {a, b})
-            if (ext_registered(e)) TRY(ext_info_enqueue(e, sa));
-        HIPCHECK(hipStreamSynchronize(sa));
-        for (azx_engine *e : {a, b})
-            if (ext_registered(e)) MATCH_TRY(e, ext_info_take(e));
-        if (*m->host_word >= (unsigned long long)n_games) break;
-    }
-    HIPCHECK(hipEventRecord(m->t1, sa));
-
-    unsigned long long ctr[MCTR_COUNT], rows = 0;
-    HIPCHECK(hipMemcpyAsync(ctr, M.ctr, sizeof ctr, hipMemcpyDeviceToHost, sa));
-    if (m->harvest) HIPCHECK(hipMemcpyAsync(&rows, a->d.q_count, sizeof rows, hipMemcpyDeviceToHost, sa));
-    if (outcome) HIPCHECK(hipMemcpyAsync(outcome, M.outcome, (size_t)n_games, hipMemcpyDeviceToHost, sa));
-    if (length) HIPCHECK(hipMemcpyAsync(length, M.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, sa));
-    if (moves) HIPCHECK(hipMemcpyAsync(moves, M.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, sa));
-    // leave both engines as azx_reset leaves them: fresh games, all active, their own uid numbering
-    azx_launch_reset(a->d, nullptr, G, nullptr, nullptr, 0, 1, sa);
-    azx_launch_reset(b->d, nullptr, G, nullptr, nullptr, 0, 1, sa);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(sa));
-    if (stats) {
-        float ms = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms, m->t0, m->t1));
-        stats->games = (int64_t)ctr[MCTR_DECIDED];
-        stats->wins[0] = (int64_t)ctr[MCTR_WINS0];
-        stats->wins[1] = (int64_t)ctr[MCTR_WINS1];
-        stats->first_player_wins = (int64_t)ctr[MCTR_FIRST_WINS];
-        stats->voided = (int64_t)ctr[MCTR_VOIDED];
-        stats->plies = (int64_t)ctr[MCTR_PLIES];
-        stats->seconds = ms * 1e-3;
-    }
-    if (ctr[MCTR_ROWS_LOST])
-        return fail(AZX_ESTATE, "match: %llu replay rows of finished games did not fit the harvest queue of %lld rows "
-                    "or did not add up to their games (internal error)", ctr[MCTR_ROWS_LOST], (long long)a->d.q_cap);
-    if (m->harvest) {                                    // the rows stay readable until a's next play call
-        m->rows_last = (int64_t)rows;
-        a->q_rows_valid = (int64_t)rows;
-    }
-    TRY(check_net_range(a));
-    return check_net_range(b);
+    TRY(loop_play(L, M.ctr + MCTR_DECIDED, n_games, max_plies, [&] { azx_launch_match_turn(a->d, b->d, M, sa); },
+                  [&] { azx_launch_match_step(a->d, b->d, M, sa); }));
+    return loop_finish(L, LoopResults{M.ctr, M.outcome, M.length, M.moves}, 1, n_games, outcome, length, moves, stats);
 }
 
 // ---- tournaments: P matches side by side in one ply loop, sharing K engines (match_kernels.hip) ----------------
@@ -2992,32 +3077,17 @@ extern "C" int azx_match_play(azx_match *m, int64_t first_game, int64_t n_games,
 // game first_game + s * rounds + r, with that uid in both engines, so a pair plays exactly the games of
 // azx_match_play(first_game + s * rounds, rounds) between its two engines.
 struct azx_tournament {
-    std::vector<azx_engine *> eng;
+    PlyLoop loop;
     TourDev t = {};
     DevEngine *eng_dev = nullptr;                // [K]
     TourTable *tab_dev = nullptr;
     int64_t tab_cap = 0, game_cap = 0, ctr_cap = 0, out_cap = 0, len_cap = 0, moves_cap = 0;   // elements held
-    unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
-    hipEvent_t ev_fork = nullptr, t0 = nullptr, t1 = nullptr;
-    std::vector<hipEvent_t> ev_join;             // [K - 1]: engine k's stream back into engine 0's
-    int sink = -1;                               // azx_tournament_set_harvest: the engine whose queue takes the rows
-    int first_mode = -1;                         // azx_tournament_set_first_mover
-    int64_t rows_last = 0;                       // rows the last azx_tournament_play harvested
-    MatchBook book = {nullptr, nullptr, 0, 0};   // azx_tournament_set_openings: as azx_match's
 };
 
 extern "C" void azx_tournament_destroy(azx_tournament *t) {
     if (!t) return;
-    DevGuard guard(t->eng[0]->cfg.device);
-    for (void *p : {(void *)t->eng_dev, (void *)t->tab_dev, (void *)t->t.tab_game, (void *)t->t.ctr,
-                    (void *)t->t.outcome, (void *)t->t.length, (void *)t->t.moves, (void *)t->book.moves,
-                    (void *)t->book.len})
-        if (p) (void)hipFree(p);
-    if (t->host_word) (void)hipHostFree(t->host_word);
-    for (hipEvent_t ev : {t->ev_fork, t->t0, t->t1})
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : t->ev_join)
-        if (ev) (void)hipEventDestroy(ev);
+    DevGuard guard(t->loop.eng[0]->cfg.device);
+    loop_destroy(t->loop, {t->eng_dev, t->tab_dev, t->t.tab_game, t->t.ctr, t->t.outcome, t->t.length, t->t.moves});
     delete t;
 }
 
@@ -3039,15 +3109,8 @@ extern "C" int azx_tournament_create(azx_engine *const *engines, int n_engines, 
     }
     DevGuard guard(engines[0]->cfg.device);
     azx_tournament *t = new azx_tournament();
-    t->eng.assign(engines, engines + n_engines);
-    t->ev_join.assign((size_t)n_engines - 1, nullptr);
     hipError_t err = hipMalloc((void **)&t->eng_dev, sizeof(DevEngine) * (size_t)n_engines);
-    if (err == hipSuccess) err = hipHostMalloc((void **)&t->host_word, sizeof(unsigned long long), hipHostMallocDefault);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming);
-    for (hipEvent_t &ev : t->ev_join)
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreate(&t->t0);
-    if (err == hipSuccess) err = hipEventCreate(&t->t1);
+    err = loop_create(t->loop, err, engines, n_engines, "tournament", nullptr);
     if (err != hipSuccess) {
         azx_tournament_destroy(t);
         return fail(AZX_ENOMEM, "allocating the tournament state failed: %s", hipGetErrorString(err));
@@ -3058,83 +3121,21 @@ extern "C" int azx_tournament_create(azx_engine *const *engines, int n_engines, 
 
 extern "C" int azx_tournament_set_harvest(azx_tournament *t, int sink_engine) {
     if (!t) return fail(AZX_EINVAL, "null tournament");
-    if (sink_engine < -1 || sink_engine >= (int)t->eng.size())
-        return fail(AZX_EINVAL, "sink engine %d: -1 (off) or an engine index below %d", sink_engine, (int)t->eng.size());
-    t->sink = sink_engine;
+    const int K = (int)t->loop.eng.size();
+    if (sink_engine < -1 || sink_engine >= K)
+        return fail(AZX_EINVAL, "sink engine %d: -1 (off) or an engine index below %d", sink_engine, K);
+    t->loop.sink = sink_engine;
     return AZX_OK;
 }
 
 extern "C" int azx_tournament_set_first_mover(azx_tournament *t, int mode) {
-    if (mode < -1 || mode > 1) return fail(AZX_EINVAL, "first mover mode %d: -1 (agent u & 1), 0 or 1", mode);
-    if (!t) return fail(AZX_EINVAL, "null tournament");
-    t->first_mode = mode;
-    return AZX_OK;
+    return loop_set_first_mover(t ? &t->loop : nullptr, "tournament", mode);
 }
-
 extern "C" int azx_tournament_set_openings(azx_tournament *t, int n_openings, int stride, const int16_t *moves,
                                            const int32_t *lengths) {
-    if (!t) return fail(AZX_EINVAL, "null tournament");
-    TRY(openings_args(n_openings, stride, moves, lengths));
-    ENGINE_GUARD(t->eng[0]);
-    return book_set(&t->book, t->eng[0]->d.N, n_openings, stride, moves, lengths);
+    return loop_set_openings(t ? &t->loop : nullptr, "tournament", n_openings, stride, moves, lengths);
 }
-
-extern "C" int azx_tournament_rows(azx_tournament *t, int64_t *rows_out) {
-    if (!t || !rows_out) return fail(AZX_EINVAL, "null argument");
-    *rows_out = t->rows_last;
-    return AZX_OK;
-}
-
-// a device buffer of at least `count` elements (grown, never shrunk; the contents are not kept)
-template <typename T>
-static int tour_grow(T **p, int64_t *cap, int64_t count, const char *what) {
-    if (count <= *cap) return AZX_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc((void **)p, sizeof(T) * (size_t)count) != hipSuccess)
-        return fail(AZX_ENOMEM, "hipMalloc of the tournament's %s (%lld) failed", what, (long long)count);
-    *cap = count;
-    return AZX_OK;
-}
-
-// a failure inside a ply: nothing any engine has queued is left running, and the message says whose engine it was
-static int tour_fail(azx_tournament *t, int k, int rc) {
-    for (azx_engine *e : t->eng) (void)hipStreamSynchronize(e->stream);
-    if (rc == AZX_EEXTERNAL) g_err = "engine " + std::to_string(k) + ": " + g_err;
-    return rc;
-}
-#define TOUR_TRY(k, expr)                           \
-    do {                                            \
-        int _rc = (expr);                           \
-        if (_rc) return tour_fail(t, (k), _rc);     \
-    } while (0)
-
-// match_ply_searches for K engines, each on its own stream (all forked from engine 0's): first what needs no host
-// -- the whole search and draw of every device-evaluated engine -- then the external engines' cursors in turn, so
-// that each one's next tree phase is on its stream before the host waits for another's evaluation point.
-static int tour_ply_searches(azx_tournament *t) {
-    const int K = (int)t->eng.size();
-    std::vector<ExtCursor> cur((size_t)K);
-    for (int k = 0; k < K; ++k)
-        if (!ext_registered(t->eng[k])) {
-            TOUR_TRY(k, enqueue_search(t->eng[k], false));
-            azx_launch_choose(t->eng[k]->d, t->eng[k]->stream);
-        }
-    for (int k = 0; k < K; ++k)
-        if (ext_registered(t->eng[k])) TOUR_TRY(k, ext_search_begin(t->eng[k], &cur[k], false));
-    for (bool busy = true; busy;) {
-        busy = false;
-        for (int k = 0; k < K; ++k)
-            if (!cur[k].done) {
-                TOUR_TRY(k, ext_search_resume(t->eng[k], &cur[k]));
-                busy = true;
-            }
-    }
-    for (int k = 0; k < K; ++k)
-        if (ext_registered(t->eng[k])) azx_launch_choose(t->eng[k]->d, t->eng[k]->stream);
-    return AZX_OK;
-}
+extern "C" int azx_tournament_rows(azx_tournament *t, int64_t *rows_out) { return loop_rows(t ? &t->loop : nullptr, rows_out); }
 
 extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                                    int64_t first_game, int64_t rounds, int32_t tables_per_pair, int8_t *outcome,
@@ -3143,8 +3144,8 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     if (!pair_a || !pair_b || n_pairs < 1) return fail(AZX_EINVAL, "a tournament needs at least one pair (pair_a, pair_b, n_pairs)");
     if (first_game < 0 || rounds < 1 || tables_per_pair < 1)
         return fail(AZX_EINVAL, "first_game must be >= 0, rounds >= 1 and tables_per_pair >= 1");
-    const int K = (int)t->eng.size(), P = n_pairs, T = tables_per_pair;
-    TRY(refuse_selfplay_options(t->eng.data(), K, "tournament", nullptr));
+    PlyLoop &L = t->loop;
+    const int K = (int)L.eng.size(), P = n_pairs, T = tables_per_pair;
     // ---- the static slot layout: engine i's pool is partitioned among its opponents, in pair order ----
     std::vector<int> deg((size_t)K, 0);
     std::vector<TourTable> tab((size_t)P * T);
@@ -3163,40 +3164,24 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     }
     int max_g = 0;
     for (int k = 0; k < K; ++k) {
-        if ((int64_t)deg[k] * T > t->eng[k]->d.G)
+        if ((int64_t)deg[k] * T > L.eng[k]->d.G)
             return fail(AZX_EINVAL, "engine %d has n_games = %d slots, its %d pairs at %d tables each need %lld", k,
-                        t->eng[k]->d.G, deg[k], T, (long long)deg[k] * T);
-        max_g = std::max(max_g, t->eng[k]->d.G);
+                        L.eng[k]->d.G, deg[k], T, (long long)deg[k] * T);
+        max_g = std::max(max_g, L.eng[k]->d.G);
     }
     const int64_t n_games = (int64_t)P * rounds, n_tables = (int64_t)P * T;
     if (n_tables > (1 << 24)) return fail(AZX_EINVAL, "%lld tables are more than a tournament takes", (long long)n_tables);
-    azx_engine *e0 = t->eng[0];
+    azx_engine *e0 = L.eng[0];
     ENGINE_GUARD(e0);
-    for (int k = 0; k < K; ++k) {
-        if (const char *why = match_engine_problem(t->eng[k])) return fail(AZX_ESTATE, "engine %d %s", k, why);
-        TRY(ext_refuse(t->eng[k]));
-    }
-    if (stats) memset(stats, 0, sizeof *stats * (size_t)P);
+    TRY(loop_begin(L, n_games, stats, P));
     const int ncells = e0->d.ncells;
     const hipStream_t s0 = e0->stream;
-    // the move draw records a replay row per draw (choose_body): the row area must exist (as in azx_match_play)
-    t->rows_last = 0;
-    azx_engine *sink = t->sink >= 0 ? t->eng[(size_t)t->sink] : nullptr;
-    for (azx_engine *e : t->eng) {
-        if (e == sink) TRY(harvest_setup(e, n_games));
-        else TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 10), 1));
-        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
-    }
-    TRY(tour_grow(&t->tab_dev, &t->tab_cap, n_tables, "tables"));
-    TRY(tour_grow(&t->t.tab_game, &t->game_cap, n_tables, "table games"));
-    TRY(tour_grow(&t->t.ctr, &t->ctr_cap, (int64_t)(P + 1) * MCTR_COUNT, "counters"));
-    TRY(tour_grow(&t->t.outcome, &t->out_cap, n_games, "outcomes"));
-    TRY(tour_grow(&t->t.length, &t->len_cap, n_games, "lengths"));
-    int16_t *moves_dev = nullptr;
-    if (moves) {
-        TRY(tour_grow(&t->t.moves, &t->moves_cap, n_games * ncells, "move records"));
-        moves_dev = t->t.moves;
-    }
+    TRY(loop_grow(L, &t->tab_dev, &t->tab_cap, n_tables, "tables"));
+    TRY(loop_grow(L, &t->t.tab_game, &t->game_cap, n_tables, "table games"));
+    TRY(loop_grow(L, &t->t.ctr, &t->ctr_cap, (int64_t)(P + 1) * MCTR_COUNT, "counters"));
+    TRY(loop_grow(L, &t->t.outcome, &t->out_cap, n_games, "outcomes"));
+    TRY(loop_grow(L, &t->t.length, &t->len_cap, n_games, "lengths"));
+    if (moves) TRY(loop_grow(L, &t->t.moves, &t->moves_cap, n_games * ncells, "move records"));
     TourDev D = t->t;
     D.eng = t->eng_dev;
     D.tab = t->tab_dev;
@@ -3206,12 +3191,12 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     D.max_g = max_g;
     D.first_game = first_game;
     D.rounds = rounds;
-    D.moves = moves_dev;
-    D.sink = t->sink;
-    D.first_mode = t->first_mode;
-    D.book = t->book;
+    D.moves = moves ? t->t.moves : nullptr;
+    D.sink = L.sink;
+    D.first_mode = L.first_mode;
+    D.book = L.book;
     std::vector<DevEngine> devs;
-    for (azx_engine *e : t->eng) devs.push_back(e->d);
+    for (azx_engine *e : L.eng) devs.push_back(e->d);
     std::vector<unsigned long long> ctr0((size_t)(P + 1) * MCTR_COUNT, 0ull);
     for (int s = 0; s < P; ++s) ctr0[(size_t)s * MCTR_COUNT + MCTR_NEXT] = (unsigned long long)std::min<int64_t>(T, rounds);
     HIPCHECK(hipMemcpyAsync(t->eng_dev, devs.data(), sizeof(DevEngine) * (size_t)K, hipMemcpyHostToDevice, s0));
@@ -3219,77 +3204,18 @@ extern "C" int azx_tournament_play(azx_tournament *t, int n_pairs, const int32_t
     HIPCHECK(hipMemcpyAsync(D.ctr, ctr0.data(), sizeof(unsigned long long) * ctr0.size(), hipMemcpyHostToDevice, s0));
     if (D.moves) HIPCHECK(hipMemsetAsync(D.moves, 0, sizeof(int16_t) * (size_t)n_games * ncells, s0));
     // fresh games in every slot of every engine (no generation is used up: the uids are the tournament's)
-    for (azx_engine *e : t->eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 0, s0);
+    for (azx_engine *e : L.eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 0, s0);
     azx_launch_tour_init(D, s0);
     if (D.book.n > 0) azx_launch_tour_open(D, e0->d.slots, s0);      // the tables' first games from their openings
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s0));                  // (the uploads are from this frame)
-    HIPCHECK(hipEventRecord(t->t0, s0));
 
-    // every game ends within `cells` plies and a table plays its pair's games back to back
+    // every game ends within `cells` plies and a table plays its pair's games back to back; the block after the
+    // pairs' counts the games decided over all pairs
     const int64_t max_plies = ((rounds + T - 1) / T + 1) * (int64_t)(ncells + 1);
-    int64_t plies = 0;
-    for (;; ++plies) {
-        if (plies > max_plies)
-            return fail(AZX_ESTATE, "tournament: %lld plies without deciding all %lld games (internal error)",
-                        (long long)plies, (long long)n_games);
-        azx_launch_tour_turn(D, s0);
-        HIPCHECK(hipEventRecord(t->ev_fork, s0));
-        for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(t->eng[k]->stream, t->ev_fork, 0));
-        TRY(tour_ply_searches(t));
-        for (int k = 1; k < K; ++k) {
-            HIPCHECK(hipEventRecord(t->ev_join[k - 1], t->eng[k]->stream));
-            HIPCHECK(hipStreamWaitEvent(s0, t->ev_join[k - 1], 0));
-        }
-        azx_launch_tour_step(D, e0->d.slots, s0);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(t->host_word, D.ctr + (size_t)P * MCTR_COUNT + MCTR_DECIDED, sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost, s0));
-        // the error word of each external search's last import rides on the same read-back (every stream has joined)
-        for (azx_engine *e : t->eng)
-            if (ext_registered(e)) TRY(ext_info_enqueue(e, s0));
-        HIPCHECK(hipStreamSynchronize(s0));
-        for (int k = 0; k < K; ++k)
-            if (ext_registered(t->eng[k])) TOUR_TRY(k, ext_info_take(t->eng[k]));
-        if (*t->host_word >= (unsigned long long)n_games) break;
-    }
-    HIPCHECK(hipEventRecord(t->t1, s0));
-
-    std::vector<unsigned long long> ctr((size_t)P * MCTR_COUNT);
-    unsigned long long rows = 0, lost = 0;
-    HIPCHECK(hipMemcpyAsync(ctr.data(), D.ctr, sizeof(unsigned long long) * ctr.size(), hipMemcpyDeviceToHost, s0));
-    if (sink) HIPCHECK(hipMemcpyAsync(&rows, sink->d.q_count, sizeof rows, hipMemcpyDeviceToHost, s0));
-    if (outcome) HIPCHECK(hipMemcpyAsync(outcome, D.outcome, (size_t)n_games, hipMemcpyDeviceToHost, s0));
-    if (length) HIPCHECK(hipMemcpyAsync(length, D.length, sizeof(int16_t) * (size_t)n_games, hipMemcpyDeviceToHost, s0));
-    if (moves) HIPCHECK(hipMemcpyAsync(moves, D.moves, sizeof(int16_t) * (size_t)n_games * ncells, hipMemcpyDeviceToHost, s0));
-    // leave every engine as azx_reset leaves it: fresh games, all active, its own uid numbering
-    for (azx_engine *e : t->eng) azx_launch_reset(e->d, nullptr, e->d.G, nullptr, nullptr, 0, 1, s0);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(s0));
-    if (stats) {
-        float ms = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms, t->t0, t->t1));
-        for (int s = 0; s < P; ++s) {
-            const unsigned long long *c = ctr.data() + (size_t)s * MCTR_COUNT;
-            stats[s].games = (int64_t)c[MCTR_DECIDED];
-            stats[s].wins[0] = (int64_t)c[MCTR_WINS0];
-            stats[s].wins[1] = (int64_t)c[MCTR_WINS1];
-            stats[s].first_player_wins = (int64_t)c[MCTR_FIRST_WINS];
-            stats[s].voided = (int64_t)c[MCTR_VOIDED];
-            stats[s].plies = (int64_t)c[MCTR_PLIES];
-            stats[s].seconds = ms * 1e-3;
-        }
-    }
-    for (int s = 0; s < P; ++s) lost += ctr[(size_t)s * MCTR_COUNT + MCTR_ROWS_LOST];
-    if (lost)
-        return fail(AZX_ESTATE, "tournament: %llu replay rows of finished games did not fit the harvest queue of %lld "
-                    "rows or did not add up to their games (internal error)", lost, (long long)(sink ? sink->d.q_cap : 0));
-    if (sink) {                                          // the rows stay readable until the sink's next play call
-        t->rows_last = (int64_t)rows;
-        sink->q_rows_valid = (int64_t)rows;
-    }
-    for (azx_engine *e : t->eng) TRY(check_net_range(e));
-    return AZX_OK;
+    TRY(loop_play(L, D.ctr + (size_t)P * MCTR_COUNT + MCTR_DECIDED, n_games, max_plies, [&] { azx_launch_tour_turn(D, s0); },
+                  [&] { azx_launch_tour_step(D, e0->d.slots, s0); }));
+    return loop_finish(L, LoopResults{D.ctr, D.outcome, D.length, D.moves}, P, n_games, outcome, length, moves, stats);
 }
 
 // ---- native training step (train_kernels.hip) ----------------------------------------------------------------

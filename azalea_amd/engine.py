@@ -910,7 +910,80 @@ def _refuse_train_targets(engines, what):
                              "the outcome (clear_train_targets() first)" % (i, e.train_targets(), what))
 
 
-class Match:
+class _DeviceGames:
+    """What Match and Tournament share: a library handle behind the entry points `_PREFIX`* (include/azx.h gives both
+    families the same setters), the engines it plays with, and what the library was last told."""
+    _PREFIX = None
+
+    def __init__(self, engines, harvest_off):
+        self.L = _lib.lib()
+        self.engines = list(engines)
+        self.h = C.c_void_p()
+        self._mode = (harvest_off, -1)    # (harvest / sink, first mover) as set in the library
+        self._book = ()                   # the opening book as set in the library (a tuple of move tuples; () = none)
+
+    def _fn(self, name):
+        return getattr(self.L, self._PREFIX + name)
+
+    def set_openings(self, openings):
+        n, stride, mv, ln = _book_arrays(openings)
+        _book_error(self._fn("set_openings")(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32)))
+        self._book = _book_key(openings)
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _set_modes(self, harvest, first_mover):
+        """Harvest (a match: 0 / 1; a tournament: the sink, -1 = off) and first mover, each set only when it changes:
+        a plain play touches none of the later entry points of the library."""
+        want = (harvest, -1 if first_mover is None else int(first_mover))
+        if want[0] != self._mode[0]:
+            check(self._fn("set_harvest")(self.h, want[0]))
+            self._mode = (want[0], self._mode[1])
+        if want[1] != self._mode[1]:
+            check(self._fn("set_first_mover")(self.h, want[1]))
+        self._mode = want
+
+    def _call(self, fn, *args):
+        """check(fn(*args)) for the play calls: what an engine's evaluator raised inside the call surfaces itself,
+        chained to the AzxError (Engine._check)."""
+        for e in self.engines:
+            e._ext_exc = None
+        rc = fn(*args)
+        exc = next((e._ext_exc for e in self.engines if e._ext_exc is not None), None)
+        for e in self.engines:
+            e._ext_exc = None
+        if rc != 0 and exc is not None:
+            try:
+                check(rc)
+            except AzxError as err:
+                raise exc from err
+        check(rc)
+
+    def _game_dict(self, outcome, length, mv, stats, first_game, n, first_mover):
+        """One pair's result: games first_game .. first_game + n - 1 (`mv`: their records, or None)."""
+        out = dict(outcome=outcome, length=length, stats=stats.as_dict())
+        if mv is not None:
+            out["moves"] = mv
+        if self._book:
+            out["opening"] = _opening_index(first_game, n, len(self._book), first_mover)
+        return out
+
+    def _collect(self, out, sink, collect):
+        rows = C.c_int64(0)
+        check(self._fn("rows")(self.h, C.byref(rows)))
+        _collected(out, sink, rows.value, collect)
+
+
+class Match(_DeviceGames):
     """azx_match_*: evaluation games between two engines, played entirely on the device.  Agent 0 is `engine_a`,
     agent 1 `engine_b`; game u is first moved by agent u & 1 and both engines draw from their stream seed + u, so
     the games of a call do not depend on the pool size.  The engines stay the caller's (and must stay open while
@@ -918,14 +991,13 @@ class Match:
     registered (Engine.set_external_evaluator): it is called at every evaluation point with the rows of the slots in
     which its engine is the mover, and an exception it raises is re-raised from play()."""
 
+    _PREFIX = "azx_match_"
+
     def __init__(self, engine_a, engine_b):
-        self.L = _lib.lib()
+        super().__init__((engine_a, engine_b), 0)
         self.a, self.b = engine_a, engine_b
         self.cells = engine_a.cells
-        self.h = C.c_void_p()
         check(self.L.azx_match_create(engine_a.h, engine_b.h, C.byref(self.h)))
-        self._mode = (0, -1)          # (harvest, first mover) as set in the library
-        self._book = ()               # the opening book as set in the library (a tuple of move tuples; () = none)
 
     def set_openings(self, openings):
         """azx_match_set_openings: the following play() calls start game u from opening (u >> 1) % n -- games 2j and
@@ -934,20 +1006,7 @@ class Match:
         ValueError with the library's message for a book it refuses (openings_check for this board size); the book
         set before stays in place then.  Not in the reference, whose evaluation games all start from the empty
         board; use an even first_game and an even number of games for colour-balanced results."""
-        n, stride, mv, ln = _book_arrays(openings)
-        _book_error(self.L.azx_match_set_openings(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32)))
-        self._book = _book_key(openings)
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h:
-            self.L.azx_match_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_openings(openings)
 
     def play(self, n_games, first_game=0, moves=False, collect=False, first_mover=None, openings=_KEEP):
         """Games first_game .. first_game + n_games - 1, each to its end.  Returns outcome int8[n] (+1 agent 0 won,
@@ -969,44 +1028,21 @@ class Match:
         _refuse_train_targets((self.a, self.b), "match")
         if openings is not _KEEP and _book_key(openings) != self._book:
             self.set_openings(openings)
-        # (set only when they change: a plain play touches none of the later entry points of the library)
-        want = (1 if collect else 0, -1 if first_mover is None else int(first_mover))
-        if want[0] != self._mode[0]:
-            check(self.L.azx_match_set_harvest(self.h, want[0]))
-            self._mode = (want[0], self._mode[1])
-        if want[1] != self._mode[1]:
-            check(self.L.azx_match_set_first_mover(self.h, want[1]))
-        self._mode = want
+        self._set_modes(1 if collect else 0, first_mover)
         n = int(n_games)
         outcome = np.zeros(n, np.int8)
         length = np.zeros(n, np.int16)
         mv = np.zeros((n, self.cells), np.int16) if moves else None
         st = MatchStats()
-        self.a._ext_exc = self.b._ext_exc = None
-        rc = self.L.azx_match_play(self.h, int(first_game), n, _p(outcome, C.c_int8), _p(length, C.c_int16),
-                                   _p(mv, C.c_int16), C.byref(st))
-        # what an engine's evaluator raised inside the call surfaces itself, chained to the AzxError (Engine._check)
-        exc = self.a._ext_exc if self.a._ext_exc is not None else self.b._ext_exc
-        self.a._ext_exc = self.b._ext_exc = None
-        if rc != 0 and exc is not None:
-            try:
-                check(rc)
-            except AzxError as err:
-                raise exc from err
-        check(rc)
-        out = dict(outcome=outcome, length=length, stats=st.as_dict())
-        if moves:
-            out["moves"] = mv
-        if self._book:
-            out["opening"] = _opening_index(first_game, n, len(self._book), first_mover)
+        self._call(self.L.azx_match_play, self.h, int(first_game), n, _p(outcome, C.c_int8), _p(length, C.c_int16),
+                   _p(mv, C.c_int16), C.byref(st))
+        out = self._game_dict(outcome, length, mv, st, first_game, n, first_mover)
         if collect:
-            rows = C.c_int64(0)
-            check(self.L.azx_match_rows(self.h, C.byref(rows)))
-            _collected(out, self.a, rows.value, collect)
+            self._collect(out, self.a, collect)
         return out
 
 
-class Tournament:
+class Tournament(_DeviceGames):
     """azx_tournament_*: several matches side by side in ONE ply loop on the device, sharing engines.  `pairs` names
     engines by their index in `engines`; pair s = (i, j) plays, bit for bit, the games of
     Match(engines[i], engines[j]).play(rounds, first_game=first_game + s * rounds) -- engine i is its agent 0 -- while
@@ -1014,34 +1050,19 @@ class Tournament:
     flight); an engine that is in d pairs needs n_games >= d * tables_per_pair slots.  The engines stay the caller's,
     as with Match; an exception raised by an engine's external evaluator is re-raised from play()."""
 
+    _PREFIX = "azx_tournament_"
+
     def __init__(self, engines):
-        self.L = _lib.lib()
-        self.engines = list(engines)
-        self.h = C.c_void_p()
+        super().__init__(engines, -1)
         arr = (C.c_void_p * max(len(self.engines), 1))(*[e.h for e in self.engines])
         check(self.L.azx_tournament_create(arr, len(self.engines), C.byref(self.h)))
         self.cells = self.engines[0].cells
-        self._mode = (-1, -1)         # (sink, first mover) as set in the library
-        self._book = ()               # the opening book as set in the library (as Match's)
 
     def set_openings(self, openings):
         """azx_tournament_set_openings: as Match.set_openings, for the games of every pair.  The rule is keyed on the
         game index u = first_game + s * rounds + r, so pair s still plays the games of its Match over that range; an
         even first_game and even `rounds` keep every pair colour-balanced."""
-        n, stride, mv, ln = _book_arrays(openings)
-        _book_error(self.L.azx_tournament_set_openings(self.h, n, stride, _p(mv, C.c_int16), _p(ln, C.c_int32)))
-        self._book = _book_key(openings)
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h:
-            self.L.azx_tournament_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().set_openings(openings)
 
     def play(self, pairs, rounds, first_game=0, tables_per_pair=None, moves=False, collect=False, sink=0,
              first_mover=None, openings=_KEEP):
@@ -1058,13 +1079,7 @@ class Tournament:
         _refuse_train_targets(self.engines, "tournament")
         if openings is not _KEEP and _book_key(openings) != self._book:
             self.set_openings(openings)
-        want = (int(sink) if collect else -1, -1 if first_mover is None else int(first_mover))
-        if want[0] != self._mode[0]:
-            check(self.L.azx_tournament_set_harvest(self.h, want[0]))
-            self._mode = (want[0], self._mode[1])
-        if want[1] != self._mode[1]:
-            check(self.L.azx_tournament_set_first_mover(self.h, want[1]))
-        self._mode = want
+        self._set_modes(int(sink) if collect else -1, first_mover)
         pairs = [(int(i), int(j)) for i, j in pairs]
         P, rounds = len(pairs), int(rounds)
         if tables_per_pair is None:
@@ -1078,33 +1093,15 @@ class Tournament:
         st = (MatchStats * max(P, 1))()
         pa = np.array([p[0] for p in pairs], np.int32)
         pb = np.array([p[1] for p in pairs], np.int32)
-        for e in self.engines:
-            e._ext_exc = None
-        rc = self.L.azx_tournament_play(self.h, P, _p(pa, C.c_int32), _p(pb, C.c_int32), int(first_game), rounds,
-                                        int(tables_per_pair), _p(outcome, C.c_int8), _p(length, C.c_int16),
-                                        _p(mv, C.c_int16), st)
-        # what an engine's evaluator raised inside the call surfaces itself, chained to the AzxError (as Match.play)
-        exc = next((e._ext_exc for e in self.engines if e._ext_exc is not None), None)
-        for e in self.engines:
-            e._ext_exc = None
-        if rc != 0 and exc is not None:
-            try:
-                check(rc)
-            except AzxError as err:
-                raise exc from err
-        check(rc)
+        self._call(self.L.azx_tournament_play, self.h, P, _p(pa, C.c_int32), _p(pb, C.c_int32), int(first_game), rounds,
+                   int(tables_per_pair), _p(outcome, C.c_int8), _p(length, C.c_int16), _p(mv, C.c_int16), st)
         out = {}
         for s, pair in enumerate(pairs):
             sl = slice(s * rounds, (s + 1) * rounds)
-            out[pair] = dict(outcome=outcome[sl], length=length[sl], stats=st[s].as_dict())
-            if moves:
-                out[pair]["moves"] = mv[sl]
-            if self._book:
-                out[pair]["opening"] = _opening_index(int(first_game) + s * rounds, rounds, len(self._book), first_mover)
+            out[pair] = self._game_dict(outcome[sl], length[sl], mv[sl] if moves else None, st[s],
+                                        int(first_game) + s * rounds, rounds, first_mover)
         if collect:
-            rows = C.c_int64(0)
-            check(self.L.azx_tournament_rows(self.h, C.byref(rows)))
-            _collected(out, self.engines[int(sink)], rows.value, collect)
+            self._collect(out, self.engines[int(sink)], collect)
         return out
 
 
