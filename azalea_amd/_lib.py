@@ -195,6 +195,12 @@ SYMBOLS = {
     "azx_selftest_rollout": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_uint64, _i32p, _f32p, _f32p,
                                        C.POINTER(C.c_uint8)]),
     "azx_rollout_stats": (C.c_int, [_vp, _i64p]),
+    # first-play urgency of the PUCT search (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_fpu": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "azx_get_fpu": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "azx_fpu_stats": (C.c_int, [_vp, _i64p]),
+    "azx_fpu_score": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float,
+                                _f32p, _f32p, _f32p, C.c_float, _i32p]),
 }
 
 class TrainConfig(C.Structure):

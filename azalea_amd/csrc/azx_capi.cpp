@@ -25,6 +25,7 @@
 #include "match_kernels.h"
 #include "playout_cap.h"
 #include "gumbel.h"
+#include "fpu.h"
 #include "resign.h"
 #include "rollout_kernels.h"
 #include "selfplay_openings.h"
@@ -316,6 +317,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.tt_ctr, G * TT_COUNT);
     A(d.fp_ctr, G * FP_COUNT);
     A(d.gm_ctr, G * GM_COUNT);
+    A(d.fpu_ctr, G * FPU_COUNT);
     A(d.gm_state, G * GM_STATE_WORDS);
     A(d.gm_g, G * 2 * AZX_CELL_STRIDE);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
@@ -461,6 +463,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.tt_ctr += b * TT_COUNT;
     v.fp_ctr += b * FP_COUNT;
     v.gm_ctr += b * GM_COUNT;
+    v.fpu_ctr += b * FPU_COUNT;
     v.gm_state += b * GM_STATE_WORDS;
     v.gm_g += b * 2 * AZX_CELL_STRIDE;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
@@ -2469,6 +2472,84 @@ extern "C" int azx_selftest_gumbel(int device, int n, const uint32_t *words, flo
     if (err == hipSuccess) err = hipMemcpy(g_out, dg, (size_t)n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(dw); (void)hipFree(dg);                       // (on every path)
     if (err != hipSuccess) return fail(AZX_EHIP, "azx_selftest_gumbel: %s", hipGetErrorString(err));
+    return AZX_OK;
+}
+
+// ---- first-play urgency (include/azx.h; NOT the reference's behaviour) ------
+// A property of the engine's search: it lives in e->d, in every launch, and is not one of SELFPLAY_OPTIONS.
+static int fpu_check(int mode, float value, float reduction, float root_reduction) {
+    if (mode != AZX_FPU_OFF && mode != AZX_FPU_ABSOLUTE && mode != AZX_FPU_REDUCTION)
+        return fail(AZX_EINVAL, "fpu: mode must be AZX_FPU_OFF (0), AZX_FPU_ABSOLUTE (1) or AZX_FPU_REDUCTION (2), got %d", mode);
+    if (mode == AZX_FPU_OFF) return AZX_OK;
+    if (!(value >= -1.0f && value <= 1.0f))                 // NaN fails both comparisons
+        return fail(AZX_EINVAL, "fpu: value must be in [-1, 1], got %g", (double)value);
+    if (!(reduction >= 0.0f && reduction <= 3.0e38f))
+        return fail(AZX_EINVAL, "fpu: reduction must be finite and >= 0, got %g", (double)reduction);
+    if (!(root_reduction >= 0.0f && root_reduction <= 3.0e38f))
+        return fail(AZX_EINVAL, "fpu: root_reduction must be finite and >= 0, got %g", (double)root_reduction);
+    return AZX_OK;
+}
+
+extern "C" int azx_set_fpu(azx_engine *e, int mode, float value, float reduction, float root_reduction) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    TRY(fpu_check(mode, value, reduction, root_reduction));
+    if (e->ext_active)
+        return fail(AZX_ESTATE, "fpu: a phase-API search is in flight (finish it with azx_search_step first)");
+    ENGINE_GUARD(e);
+    TRY(zero_game_counters(e, e->d.fpu_ctr, FPU_COUNT));
+    const bool on = mode != AZX_FPU_OFF;
+    e->d.fpu_mode = mode;
+    e->d.fpu_value = on ? value + 0.0f : 0.0f;
+    e->d.fpu_red = on ? reduction + 0.0f : 0.0f;
+    e->d.fpu_root_red = on ? root_reduction + 0.0f : 0.0f;
+    return AZX_OK;
+}
+
+extern "C" int azx_get_fpu(azx_engine *e, int *mode, float *value, float *reduction, float *root_reduction) {
+    if (!e || !mode || !value || !reduction || !root_reduction) return fail(AZX_EINVAL, "null argument");
+    *mode = e->d.fpu_mode;
+    *value = e->d.fpu_value;
+    *reduction = e->d.fpu_red;
+    *root_reduction = e->d.fpu_root_red;
+    return AZX_OK;
+}
+
+extern "C" int azx_fpu_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    TRY(sum_game_counters(e, e->d.fpu_ctr, FPU_COUNT, out4, 4));
+    out4[3] = 0;                        // (not computed: include/azx.h)
+    return AZX_OK;
+}
+
+// the definition on the host for one node: score_actions + np.argmax (mcts.py:119-136, :112) op by op in float32, the
+// unvisited children's Q from fpu.h
+extern "C" int azx_fpu_score(int mode, float value, float reduction, float root_reduction, int is_root, int k, float nv_p,
+                             float tv_p, const float *nv, const float *tv, const float *prior, float c_puct,
+                             int32_t *child_out) {
+#pragma clang fp contract(off)
+    if (k < 1 || !nv || !tv || !prior || !child_out) return fail(AZX_EINVAL, "fpu score: bad argument");
+    TRY(fpu_check(mode, value, reduction, root_reduction));
+    double sum = 0.0;                                       // integers: exact in any order
+    uint32_t M = 0u;
+    for (int j = 0; j < k; ++j) {
+        sum += (double)nv[j];
+        if (nv[j] > 0.0f) M += azx_fpu_mass_word(prior[j]);
+    }
+    const float sq = sqrtf((float)sum);
+    float fpu = 0.0f;
+    if (mode != AZX_FPU_OFF) fpu = azx_fpu_q(mode, value, is_root ? root_reduction : reduction, nv_p, tv_p, M);
+    int best = 0;
+    float best_score = 0.0f;
+    for (int j = 0; j < k; ++j) {
+        const float gap = sq / (1.0f + nv[j]);
+        const float U = (c_puct * prior[j]) * gap;
+        float Q = (-tv[j]) / fmaxf(nv[j], 1.0f);
+        if (mode != AZX_FPU_OFF && nv[j] == 0.0f) Q = fpu;
+        const float score = Q + U;
+        if (j == 0 || score > best_score) { best = j; best_score = score; }
+    }
+    *child_out = best;
     return AZX_OK;
 }
 

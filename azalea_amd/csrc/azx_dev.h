@@ -192,7 +192,16 @@ struct DevEngine {
     const int32_t *bk_len;      // [bk_n]
     const uint64_t *bk_ub;      // [bk_n] game uid starts from the least o with azx_book_word(seed, uid) < bk_ub[o]
     unsigned long long *bk_ctr; // [bk_n][BK_COUNT] per OPENING (several slots share one: atomics), azx_selfplay_openings_stats' array
+    // first-play urgency (azx_set_fpu; NOT the reference's behaviour).  A property of the engine's search, not a self-play
+    // option: like the book it is in every launch -- azx_search, the phase API, self-play, matches and tournaments -- and
+    // AZX_FPU_OFF (0) is the reference's rule (fpu.h has the rule, include/azx.h the definition)
+    int32_t fpu_mode;           // AZX_FPU_OFF / AZX_FPU_ABSOLUTE / AZX_FPU_REDUCTION
+    float fpu_value;            // ABSOLUTE: Q of an unvisited child
+    float fpu_red, fpu_root_red;   // REDUCTION: r below the root, r at the root
+    unsigned long long *fpu_ctr;   // [G][FPU_COUNT] per game (no atomics), azx_fpu_stats' array; the host sums
 };
+// selects made under the option, node levels scored under it with an unvisited child, selects that ended on an unvisited child
+enum { FPU_SELECTS = 0, FPU_LEVELS, FPU_UNVISITED, FPU_RESERVED, FPU_COUNT = 4 };
 // games started, games finished, finished games won by colour 1, plies of finished games counted from the empty board
 enum { BK_STARTED = 0, BK_FINISHED, BK_WON1, BK_PLIES, BK_COUNT = 4 };
 // plies chosen under the option, halvings performed, root selects made under the option, rows recorded as the improved policy

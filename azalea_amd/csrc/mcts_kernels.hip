@@ -22,6 +22,7 @@
 #include "mcts_kernels.h"
 #include "playout_cap.h"
 #include "gumbel.h"
+#include "fpu.h"
 #include "resign.h"
 #include "selfplay_openings.h"
 
@@ -495,7 +496,7 @@ __device__ __forceinline__ void gumbel_top(const float *key, const uint64_t *fro
     }
 }
 
-template <int SLOTS, bool FAST>
+template <int SLOTS, bool FAST, bool FPU = false>
 __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int num_batches, bool stage_tables = true) {
     const int mode = FAST ? (MODE_BEGIN | MODE_INLINE) : mode_arg;
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -574,6 +575,16 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) gsurv[s] = 0ull;
     if (gm_m != 0 && (mode & MODE_BEGIN)) gumbel_fill(E, g, gh->uid, ply, lane);
+    // First-play urgency (azx_set_fpu; NOT the reference's behaviour; fpu.h has the rule): where a node's children are
+    // scored, a child with num_visits == 0 takes Q = fpu.  The wave-uniform branch on the mode is taken by the HOST: an
+    // engine with the option set launches the FPU instantiations of the tree kernels (k_mcts_fpu, k_play<S, true>), every
+    // other launch the instantiations in which fpu_mode is the constant 0 and all of the option's work -- the parent's
+    // Q, the integer reduction of the visited children's prior mass, the three tallies -- folds away: those are the
+    // kernels of before the option, instruction for instruction.  (Tested at run time inside one kernel, any single
+    // part of the option's work made k_mcts<3, FAST>, which fills the 128 registers of its four waves, spill 18 to 23
+    // of them across the whole launch: profiles/fpu_resources.txt.)
+    const int fpu_mode = FPU ? __builtin_amdgcn_readfirstlane(E.fpu_mode) : AZX_FPU_OFF;
+    uint32_t c_fpu_lvl = 0, c_fpu_unv = 0;
     if (!FAST && gm_m != 0 && !(mode & MODE_BEGIN)) {
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) gsurv[s] = E.gm_state[(size_t)g * GM_STATE_WORDS + GM_SURV + s];
@@ -1055,8 +1066,9 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         // score_actions (mcts.py:119-136) op by op in float32 over RS register slots + np.argmax
         // (highest score, lowest index on ties, mcts.py:112): returns the winning lane-slot index.
         // Branch-free: every lane computes, lanes outside `mm` are masked out of the maximum.
+        // First-play urgency: `fpu` is the Q of the children with num_visits == 0 (read only while fpu_mode != 0).
         auto score_argmax = [&](auto rs_tag, const float4 *st, const float *Pn, const uint64_t *mm,
-                                float sq) __attribute__((always_inline)) -> int {
+                                float sq, float fpu) __attribute__((always_inline)) -> int {
             constexpr int RS = decltype(rs_tag)::value;
             uint32_t key[SLOTS], lkey = 0u;
             auto score_slots = [&](auto exact_tag) {
@@ -1074,7 +1086,13 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     f2 dq;                                                             // clip(min=1)
                     dq.x = __builtin_amdgcn_fmed3f(nvj.x, 1.0f, 3.0e38f);
                     dq.y = __builtin_amdgcn_fmed3f(nvj.y, 1.0f, 3.0e38f);
-                    const f2 W = -tvj;                                                 // search_tree.py:203
+                    f2 W = -tvj;                                                       // search_tree.py:203
+                    // azx_set_fpu, the one changed term: an unvisited child's numerator is fpu and its divisor the
+                    // clip's 1, so its Q is fpu itself (n / 1 is n in both divides), chosen where nvj is live anyway
+                    if (fpu_mode != 0) {
+                        W.x = nvj.x == 0.0f ? fpu : W.x;
+                        W.y = nvj.y == 0.0f ? fpu : W.y;
+                    }
                     const f2 Q = kIeee ? div2_ieee(W, dq) : div2_unscaled(W, dq);     // mcts.py:134
                     const f2 score = (Q + U) + zero;                    // mcts.py:135; -0.0 -> +0.0
                     // order-preserving map float -> u32 (np.argmax compares values; equal
@@ -1098,6 +1116,28 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             }
             return best_idx;
         };
+        // First-play urgency of one node (only called with fpu_mode != 0): RS register slots of its children, `mm` their
+        // lane masks, (nv_p, tv_p) the node's own num_visits and total_value as this select sees them, r the reduction
+        // that holds at it.  One integer wave reduction in mode REDUCTION; counts the level if it has an unvisited child.
+        auto fpu_of = [&](auto rs_tag, const float4 *st, const uint64_t *mm, float nv_p, float tv_p,
+                          float r) __attribute__((always_inline)) -> float {
+            constexpr int RS = decltype(rs_tag)::value;
+            uint32_t m = 0u;
+            bool unv = false;
+#pragma unroll
+            for (int s = 0; s < RS; ++s) {
+                const bool in = lane_bit(mm[s]);
+                unv = unv || (in && st[s].x == 0.0f);
+                if (fpu_mode == AZX_FPU_REDUCTION && in && st[s].x > 0.0f) m += azx_fpu_mass_word(st[s].z);
+            }
+            if (__ballot(unv)) c_fpu_lvl += 1;
+            uint32_t M = 0u;
+            if (fpu_mode == AZX_FPU_REDUCTION) M = (uint32_t)wave_sum_i((int)m);
+            // (a scalar from here on, and nothing of the above left to interleave with the scoring)
+            const float q = readlane_f(azx_fpu_q(fpu_mode, E.fpu_value, r, nv_p, tv_p, M), 0);
+            __builtin_amdgcn_sched_barrier(0);
+            return q;
+        };
         auto sqrt_of = [&](float sq_tab, int sumn) __attribute__((always_inline)) -> float {
             float sq = late_vgpr(sq_tab);
             if (sumn >= AZX_SQRT_TAB) {                // beyond the table (rare): a real branch
@@ -1112,7 +1152,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         // block is on its way from HBM (its only input from descent i, the virtual loss on i's root
         // child, is applied as soon as that child is known).
         int pk_rank = 0, pk_cell = 0, pk_link = 0;
-        float pk_nv = 0.0f;
+        float pk_nv = 0.0f, pk_tv = 0.0f;   // (pk_tv: read only in mode AZX_FPU_REDUCTION, the root child's Q is needed below it)
         // Gumbel root search, the top of batch b = NBt - batches_left (the earlier batches are backed up, their virtual
         // losses undone): at b == 0 the m0 = min(m, k) candidates with the largest g + ln P become the survivors; the
         // survivors are halved -- the ceil(|S| / 2) largest g + ln P + sigma stay -- once for every r in 1..R-1 with
@@ -1257,7 +1297,9 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     }
                     if (forced_idx >= 0) c_forced += 1;
                 }
-                const int argmax_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq);
+                float fpu = 0.0f;
+                if (fpu_mode != 0) fpu = fpu_of(rs_tag, rst, rootrm, root_nv, root_tv, E.fpu_root_red);
+                const int argmax_idx = score_argmax(rs_tag, rst, Pn, rootrm, sq, fpu);
                 best_idx = forced_idx >= 0 ? forced_idx : argmax_idx;
             }
             const int bl = best_idx & 63, bsl = best_idx >> 6;
@@ -1267,6 +1309,13 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                 const int l_ = __builtin_amdgcn_readlane(__float_as_int(rst[s].w), bl);
                 const float n_ = readlane_f(rst[s].x, bl);
                 if (s == bsl) { pk_cell = c_; pk_link = l_; pk_nv = n_; }
+            }
+            if (fpu_mode == AZX_FPU_REDUCTION) {
+#pragma unroll
+                for (int s = 0; s < RS; ++s) {
+                    const float t_ = readlane_f(rst[s].y, bl);
+                    if (s == bsl) pk_tv = t_;
+                }
             }
             pk_rank = best_idx;
             T_MARK(0)
@@ -1295,7 +1344,9 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             int link = root_link, node = root_link + pk_rank, child_link = pk_link, depth = 1;
             int mover = 3 - root.color;                       // colour placing the next stone
             float cur_nv = 0.0f;               // num_visits (incl. virtual) of the node being scored
+            float cur_tv = 0.0f;               // its total_value (followed only in mode AZX_FPU_REDUCTION)
             float cnv = pk_nv, ctv = 0.f;
+            if (fpu_mode == AZX_FPU_REDUCTION) ctv = pk_tv;
             float sq_next_pend = 0.0f;
             int slot1 = -1;                                    // cache entry of the depth-2 node, once known
             {
@@ -1328,6 +1379,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             auto deeper_issue = [&]() __attribute__((always_inline)) {
                 link = child_link;
                 cur_nv = cnv;
+                if (fpu_mode == AZX_FPU_REDUCTION) cur_tv = ctv;
                 // sqrt(visits - 1) of this node: requested here, consumed after the children arrive
                 const int sn = (int)cur_nv - 1;
                 sq_next_pend = c_sqrt[sn < 0 ? 0 : (sn < AZX_SQRT_TAB ? sn : AZX_SQRT_TAB - 1)];
@@ -1357,6 +1409,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     for (int s = SLOTS - 1; s >= 0; --s)
                         if (mk.m[s]) best_cell = s * 64 + (int)__ffsll((long long)mk.m[s]) - 1;
                     child_link = AZX_LINK_UNEVAL;
+                    if (fpu_mode != 0) c_fpu_lvl += 1;   // (every child takes fpu + 0: child 0 still)
                 } else {
                     // sqrt(sum of the children's visits), mcts.py:132: every evaluated node has been
                     // visited once more than its children together (its own expansion), virtual
@@ -1377,7 +1430,10 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
 #pragma unroll
                     for (int s = 0; s < SLOTS; ++s) Pn[s] = pst[s].z;
                     const float sq = sqrt_of(sq_next_pend, sumn);
-                    const int best_idx = score_argmax(std::integral_constant<int, SLOTS>{}, pst, Pn, mk.m, sq);
+                    float fpu = 0.0f;
+                    if (fpu_mode != 0)
+                        fpu = fpu_of(std::integral_constant<int, SLOTS>{}, pst, mk.m, cur_nv, cur_tv, E.fpu_red);
+                    const int best_idx = score_argmax(std::integral_constant<int, SLOTS>{}, pst, Pn, mk.m, sq, fpu);
                     const int bl = best_idx & 63, bsl = best_idx >> 6;
 #pragma unroll
                     for (int s = 0; s < SLOTS; ++s) {
@@ -1433,6 +1489,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             }
             select_count += 1;
             c_selects += 1;
+            if (fpu_mode != 0) c_fpu_unv += cnv == 0.0f ? 1u : 0u;   // the chosen leaf had no visit
             // ---- the leaf position: winner (hex.py:204-231) and legal moves ---------------------
             const int last = 3 - mover;                       // colour of the stone just placed
             int winner = last;                                // a terminal link: the last mover won
@@ -1657,6 +1714,13 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         if (c_forced) E.fp_ctr[(size_t)g * FP_COUNT + FP_FORCED] += c_forced;
         // azx_gumbel_stats: every select of a search under the option makes its root level under it
         if (gm_m != 0 && c_selects) E.gm_ctr[(size_t)g * GM_COUNT + GM_SELECTS] += c_selects;
+        // azx_fpu_stats: every select of a launch under the option
+        if (fpu_mode != 0 && c_selects) {
+            unsigned long long *fc = E.fpu_ctr + (size_t)g * FPU_COUNT;
+            fc[FPU_SELECTS] += c_selects;
+            fc[FPU_LEVELS] += c_fpu_lvl;
+            fc[FPU_UNVISITED] += c_fpu_unv;
+        }
     }
     // the six per-game tallies, one lane each (as six scalar read-modify-writes the compiler waited
     // for each load in turn: six memory round trips at the end of every launch)
@@ -1672,6 +1736,11 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
 template <int SLOTS, bool FAST>
 __global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, FAST) void k_mcts(DevEngine E, int mode_arg, int num_batches) {
     mcts_body<SLOTS, FAST>(E, mode_arg, num_batches);
+}
+// the same search for an engine with first-play urgency set (azx_set_fpu), under the same occupancy bounds
+template <int SLOTS, bool FAST>
+__global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, FAST) void k_mcts_fpu(DevEngine E, int mode_arg, int num_batches) {
+    mcts_body<SLOTS, FAST, true>(E, mode_arg, num_batches);
 }
 
 // ============================================================================================
@@ -2472,7 +2541,7 @@ __global__ __launch_bounds__(64) void k_choose(DevEngine E) {
 // k_play<2> now sits exactly ON the 128-VGPR limit of 4 waves: with the bound stated, anything further added to the
 // play loop -- here, in choose_body or in advance_body -- spills VGPRs to scratch instead of losing occupancy.  Check
 // the compiler's resource remarks (VGPRs Spill, ScratchSize) after any such change, and make room first.)
-template <int SLOTS>
+template <int SLOTS, bool FPU = false>
 __global__ __launch_bounds__(64) AZX_PLAY_ATTR(SLOTS) void k_play(DevEngine E, int num_batches, int steps) {
 #ifdef AZX_STAMP_PLAY     // diagnostic build: per-wave cycles in the search, the move draw and the game step (slots 10-12)
     unsigned long long tp_[3] = {0, 0, 0};
@@ -2481,7 +2550,7 @@ __global__ __launch_bounds__(64) AZX_PLAY_ATTR(SLOTS) void k_play(DevEngine E, i
 #define TP(i, stmt) stmt;
 #endif
     for (int s = 0; s < steps; ++s) {
-        TP(0, (mcts_body<SLOTS, true>(E, MODE_BEGIN | MODE_INLINE, num_batches, s == 0)))
+        TP(0, (mcts_body<SLOTS, true, FPU>(E, MODE_BEGIN | MODE_INLINE, num_batches, s == 0)))
         wave_mem_sync();
         // The move draw and the game step read their engine fields (queue, row and statistics pointers: ~50
         // scalar registers) from the kernel-argument segment again, through a pointer the compiler cannot see
@@ -2506,7 +2575,6 @@ __global__ __launch_bounds__(64) AZX_PLAY_ATTR(SLOTS) void k_play(DevEngine E, i
 #endif
 #undef TP
 }
-
 template <int SLOTS>
 __global__ __launch_bounds__(64) void k_hex_replay(int N, int n_games, const int32_t *moves,
                                                    const int32_t *length, int stride,
@@ -2688,8 +2756,22 @@ bool azx_mcts_fast_path(const DevEngine &E, int mode, bool force_generic) {
            E.prior_default && (E.noise_scale == 0.0 || E.device_noise);
 }
 
+// An engine with first-play urgency set (azx_set_fpu) runs the FPU instantiations of the tree kernels; every other
+// launch runs the kernels in which the option does not exist.
 void azx_launch_mcts(const DevEngine &E, int mode, int num_batches, hipStream_t st, bool force_generic) {
     const size_t lds = azx_mcts_lds_bytes(E.ncells, E.bs);
+    if (E.fpu_mode != AZX_FPU_OFF) {
+        if (azx_mcts_fast_path(E, mode, force_generic)) {
+#define CALL(S) hipLaunchKernelGGL((k_mcts_fpu<S, true>), dim3(E.G), dim3(64), lds, st, E, mode, num_batches)
+            DISPATCH_SLOTS(E.slots, CALL);
+#undef CALL
+            return;
+        }
+#define CALL(S) hipLaunchKernelGGL((k_mcts_fpu<S, false>), dim3(E.G), dim3(64), lds, st, E, mode, num_batches)
+        DISPATCH_SLOTS(E.slots, CALL);
+#undef CALL
+        return;
+    }
     if (azx_mcts_fast_path(E, mode, force_generic)) {
 #define CALL(S) hipLaunchKernelGGL((k_mcts<S, true>), dim3(E.G), dim3(64), lds, st, E, mode, num_batches)
         DISPATCH_SLOTS(E.slots, CALL);
@@ -2706,7 +2788,13 @@ bool azx_launch_play(const DevEngine &E, int num_batches, int steps, hipStream_t
     if (!allowed) return false;
     if (!(E.evaluator == AZX_EVAL_UNIFORM && E.prior_default && (E.noise_scale == 0.0 || E.device_noise))) return false;
     const size_t lds = azx_mcts_lds_bytes(E.ncells, E.bs);
-#define CALL(S) hipLaunchKernelGGL((k_play<S>), dim3(E.G), dim3(64), lds, st, E, num_batches, steps)
+    if (E.fpu_mode != AZX_FPU_OFF) {
+#define CALL(S) hipLaunchKernelGGL((k_play<S, true>), dim3(E.G), dim3(64), lds, st, E, num_batches, steps)
+        DISPATCH_SLOTS(E.slots, CALL);
+#undef CALL
+        return true;
+    }
+#define CALL(S) hipLaunchKernelGGL((k_play<S, false>), dim3(E.G), dim3(64), lds, st, E, num_batches, steps)
     DISPATCH_SLOTS(E.slots, CALL);
 #undef CALL
     return true;

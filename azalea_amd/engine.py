@@ -827,6 +827,55 @@ class Engine:
         check(self.L.azx_gumbel_state(self.h, _p(cand, C.c_uint64), _p(surv, C.c_uint64)))
         return cand, surv
 
+    # ---- first-play urgency of the PUCT search (azx_set_fpu; NOT the reference's behaviour) ----
+    FPU_MODES = {"off": 0, "absolute": 1, "reduction": 2}
+
+    def set_fpu(self, mode="reduction", value=0.0, reduction=0.25, root_reduction=0.0):
+        """azx_set_fpu: first-play urgency.  In EVERY search this engine runs from now on -- search(), the phase API,
+        play / play_device / replay_fill / play_steps, and as a side of a Match or Tournament (each engine keeps its own
+        setting; they are not refused) -- a child with no visit is scored with Q = fpu instead of Q = 0:
+        mode="absolute": fpu = value, in [-1, 1]; mode="reduction": fpu = Qp - r * sqrt(mass), Qp the node's own mean
+        value in its mover's view, mass the prior mass of its visited children, r = root_reduction at the search's root
+        and reduction below it (include/azx.h has the definition bit for bit, DESIGN 7.20 the interactions).
+        mode="off" (or clear_fpu()) is the reference's rule: the same kernels, the same bytes as before.  Forced playouts
+        override an argmax computed with FPU; under the Gumbel root search FPU acts below the root only.  The defaults
+        (reduction 0.25 below the root, 0 at it) are lc0's / KataGo's customary values as the author recalls them and are
+        not checked here.  NOT the reference's behaviour; off by default; outside every parity claim.  Refused
+        (AzxError, AZX_ESTATE) between search_begin and the last search_step.  Zeroes fpu_stats().  Its effect on
+        playing strength is NOT measured unless profiles/fpu_strength.json says otherwise."""
+        if mode not in self.FPU_MODES:
+            raise ValueError("fpu: mode must be one of %s, got %r" % (sorted(self.FPU_MODES), mode))
+        value, reduction, root_reduction = float(value), float(reduction), float(root_reduction)
+        if mode != "off":
+            if not -1.0 <= value <= 1.0:                # NaN fails both comparisons
+                raise ValueError("fpu: value must be in [-1, 1], got %r" % (value,))
+            if not 0.0 <= reduction < float("inf"):
+                raise ValueError("fpu: reduction must be finite and >= 0, got %r" % (reduction,))
+            if not 0.0 <= root_reduction < float("inf"):
+                raise ValueError("fpu: root_reduction must be finite and >= 0, got %r" % (root_reduction,))
+        check(self.L.azx_set_fpu(self.h, self.FPU_MODES[mode], value, reduction, root_reduction))
+
+    def clear_fpu(self):
+        """set_fpu("off"): an unvisited child scores with Q = 0 again, as in the reference."""
+        check(self.L.azx_set_fpu(self.h, 0, 0.0, 0.0, 0.0))
+
+    def fpu(self):
+        """azx_get_fpu: dict(mode, value, reduction, root_reduction) in force; mode "off" with zeros when off."""
+        if getattr(self.L, "azx_get_fpu", None) is None:        # an older build (tools/lib_bench.py): never set
+            return dict(mode="off", value=0.0, reduction=0.0, root_reduction=0.0)
+        m, v, r, rr = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        check(self.L.azx_get_fpu(self.h, C.byref(m), C.byref(v), C.byref(r), C.byref(rr)))
+        name = {n: k for k, n in self.FPU_MODES.items()}[int(m.value)]
+        return dict(mode=name, value=float(v.value), reduction=float(r.value), root_reduction=float(rr.value))
+
+    FPU_STATS = ("selects", "levels_with_unvisited", "ended_unvisited", "differs_from_off")
+
+    def fpu_stats(self):
+        """azx_fpu_stats since the last set_fpu: dict(selects, levels_with_unvisited, ended_unvisited, differs_from_off)
+        -- the selects made under the option, the node levels scored under it that had an unvisited child, the selects
+        that ended on a child with no visit; differs_from_off is not computed and always 0 (include/azx.h)."""
+        return self._stats(self.L.azx_fpu_stats, self.FPU_STATS)
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""
@@ -1179,6 +1228,22 @@ def selftest_gumbel(words, device=0):
     out = np.zeros(words.shape, np.float32)
     check(_lib.lib().azx_selftest_gumbel(device, words.size, _p(words, C.c_uint32), _p(out, C.c_float)))
     return out
+
+
+def fpu_score(mode, nv, tv, prior, nv_p, tv_p, c_puct, is_root=False, value=0.0, reduction=0.25, root_reduction=0.0):
+    """azx_fpu_score: the child PUCT takes at ONE node under first-play urgency, on the host (no GPU, no root noise):
+    nv, tv, prior are the float32 arrays of its children, (nv_p, tv_p) the node's own visits and total value.  mode
+    "off" gives the reference's choice.  The counterpart of Engine.set_fpu for tests and tools."""
+    nv, tv, prior = (np.ascontiguousarray(a, np.float32) for a in (nv, tv, prior))
+    if not (nv.ndim == 1 and nv.shape == tv.shape == prior.shape):
+        raise ValueError("fpu_score: nv, tv and prior must be 1-d arrays of one length")
+    if mode not in Engine.FPU_MODES:
+        raise ValueError("fpu: mode must be one of %s, got %r" % (sorted(Engine.FPU_MODES), mode))
+    out = C.c_int32(-1)
+    check(_lib.lib().azx_fpu_score(Engine.FPU_MODES[mode], float(value), float(reduction), float(root_reduction),
+                                   1 if is_root else 0, int(nv.size), float(nv_p), float(tv_p), _p(nv, C.c_float),
+                                   _p(tv, C.c_float), _p(prior, C.c_float), float(c_puct), C.byref(out)))
+    return int(out.value)
 
 
 def rollout_value(seed, board, rollouts):

@@ -24,6 +24,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from . import fpu as _fpu
 from .play_game import play_game
 
 Pair = Tuple[int, int]
@@ -117,6 +118,7 @@ def evaluate_batched(agents, num_rounds: int, *, game_max_length: int = 300) -> 
                           noise_scale=pol.exploration_noise_scale, temperature=pol.exploration_temperature,
                           evaluator=_eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                           device=(dev.index or 0) if dev.type == "cuda" else 0)
+        _fpu.apply(eng, _fpu.policy_fpu(pol))                  # first-play urgency, if the policy carries it
         pol.net.eval()
         sd = {k: v for k, v in pol.net.state_dict().items() if v.dtype == torch.float32}
         if dev.type == "cuda":
@@ -257,6 +259,10 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     games are the same; `games[pair]` gains "opening", the opening index of each game.  NOT the reference's
     behaviour, whose evaluation games all start from the empty board; off by default.  A ValueError with the
     library's message, before any engine is made, for a book the rules refuse (engine.openings_check).
+    A policy attribute `fpu` (Policy.set_fpu, config["fpu"]; first-play urgency, Engine.set_fpu: NOT the reference's
+    behaviour, off by default, OUTSIDE every parity claim) is honoured per agent, pooled or not: it is a property of an
+    engine's search, not a self-play option, so a match between the same weights with and without it is two agents that
+    differ in that attribute.
     `gumbel`: refused.  The Gumbel root search (Engine.set_gumbel, Player(gumbel=...)) is a self-play option; device
     matches and tournaments search and draw every ply as the reference does.  Anything but None / False / 0 is a
     ValueError, before any engine is made."""
@@ -314,6 +320,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                               nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),   # 0: the engine's default
                               flags=flags[a], seed=((int(seed) << 8) + a) << 32)
             engines.append(eng)
+            _fpu.apply(eng, _fpu.policy_fpu(pol))              # first-play urgency, per agent, if its policy carries it
             if hasattr(pol.net, "eval"):
                 pol.net.eval()
             if external:

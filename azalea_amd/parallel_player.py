@@ -29,6 +29,7 @@ import torch
 
 from . import distributed as azdist
 from . import engine as _eng
+from . import fpu as _fpu
 from .game.hex import HexGameState
 from .play_game import play_game
 from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags  # noqa: F401
@@ -81,7 +82,7 @@ class Player:
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
                  openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None,
-                 forced_playouts=None, gumbel=None, selfplay_openings=None, selfplay_opening_weights=None):
+                 forced_playouts=None, gumbel=None, selfplay_openings=None, selfplay_opening_weights=None, fpu=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -168,7 +169,16 @@ class Player:
         a device match.)  A ValueError -- here, before any engine is made -- with device_match=True (a match has its
         own book: use openings=), with two agents, when the games would run through the host loop, or for anything
         normalize_selfplay_openings or the rules refuse.  opening_stats() has the per-opening tallies.  Its effect on
-        playing strength and training efficiency is NOT measured."""
+        playing strength and training efficiency is NOT measured.
+        `fpu` (NOT the reference's behaviour, which scores an unvisited child with Q = 0; off by default): first-play
+        urgency, anything azalea_amd.fpu.normalize_fpu takes -- True (reduction 0.25 below the root, 0 at it; lc0's /
+        KataGo's customary values as the author recalls them, not checked here), "absolute" / "reduction", a (mode,
+        value, reduction, root_reduction) tuple or a dict with those keys.  Unlike the options above it is a property
+        of the SEARCH, not a self-play option: it is put on every agent's Policy (Policy.set_fpu) and from there on every
+        engine built for it -- device self-play, external_batch, BOTH engines of device_match, and the host loop's
+        single-game engines.  None leaves each policy's own setting (config["fpu"], Policy.set_fpu) as it is.  A
+        ValueError for anything normalize_fpu refuses.  DESIGN 7.20 has what was and was not measured."""
+        self.fpu = _fpu.normalize_fpu(fpu)
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -176,6 +186,10 @@ class Player:
             raise ValueError("openings are a device_match option: only the device match starts its games from an "
                              "opening book (self-play and the host loop start from the empty board)")
         self.agents = agents
+        if self.fpu is not None:
+            for a in agents:
+                if hasattr(getattr(a, "policy", None), "set_fpu"):
+                    a.policy.set_fpu(self.fpu)
         self.running = True
         self.gather = gather
         self.external_batch = bool(external_batch)
@@ -522,6 +536,7 @@ class Player:
             for opt in OPTIONS:          # (the book first, before any play: generation 0 follows it too)
                 opt.apply(self._engine, getattr(self, opt.name))
             self._engine_key = key
+        _fpu.apply(self._engine, _fpu.policy_fpu(pol))          # a property of the search, not one of OPTIONS
         return self._engine
 
     def _produce_on_device(self, pol: Policy, want: int) -> None:
@@ -562,7 +577,7 @@ class Player:
         external = not pol._uses_device_net()
         dev = _net_device(pol.net)
         # game_rng keys on seed + uid: the two agents' streams are disjoint ranges of 2^32 games
-        return _eng.Engine(board_size=n, n_games=self.n_games, simulations=pol.simulations,
+        eng = _eng.Engine(board_size=n, n_games=self.n_games, simulations=pol.simulations,
                            search_batch_size=pol.search_batch_size, exploration_coef=pol.exploration_coef,
                            exploration_depth=pol.exploration_depth, noise_alpha=pol.exploration_noise_alpha,
                            noise_scale=noise_scale, temperature=temperature,
@@ -572,6 +587,8 @@ class Player:
                            device=(dev.index or 0) if dev.type == "cuda" else 0, nodes_per_game=int(getattr(pol, "nodes_per_game", 0) or 0),
                            flags=self._engine_flags | tower_flags(pol),
                            seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
+        _fpu.apply(eng, _fpu.policy_fpu(pol))
+        return eng
 
     def _produce_match(self, pols) -> None:
         """One chunk of MATCH_CHUNK * n_games games between the two agents' engines, harvested on the device."""

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import engine as _eng
+from . import fpu as _fpu
 from .utils import import_and_get
 
 
@@ -117,6 +118,7 @@ class Policy:
         self._engine_moves = None     # moves applied to the engine slot since its last reset
         self._weights_version = None
         self.keep_reference_arena = True   # never-free arena + moving root, like the reference
+        self.fpu = None               # first-play urgency (set_fpu): None = off, the reference's rule
 
     # ---- construction / persistence (policy.py:36-63, :85-130, :181-208) ------------------
     def initialize(self, config):
@@ -132,6 +134,19 @@ class Policy:
             setattr(self, k, config[k])
         if "seed" in config:
             self.seed(config["seed"])
+        self.set_fpu(config.get("fpu"))
+
+    def set_fpu(self, fpu=True):
+        """First-play urgency for every search made for this policy (Engine.set_fpu; include/azx.h has the definition):
+        an unvisited child is scored with Q = fpu instead of Q = 0.  `fpu`: anything azalea_amd.fpu.normalize_fpu takes --
+        True (reduction 0.25 below the root, 0 at it), "absolute" / "reduction", a (mode, value, reduction,
+        root_reduction) tuple, a dict with those keys, or None / False / "off".  Also set by config["fpu"] and by
+        Player(fpu=...).  It is honoured wherever an engine is built for the policy: choose_action (the single-game
+        path behind play_game and evaluate), Player's engines, evaluate_throughput's matches and tournaments.  It is a
+        setting of the search, not of the network: checkpoints do not carry it.  The defaults are lc0's / KataGo's
+        customary values as the author recalls them and are not checked here.  NOT the reference's behaviour; off by
+        default; outside every parity claim."""
+        self.fpu = _fpu.normalize_fpu(fpu)
 
     @property
     def net(self):
@@ -227,6 +242,7 @@ class Policy:
             self._engine_key = key
             self._engine_moves = None
             self._weights_version = None
+        _fpu.apply(self._engine, _fpu.policy_fpu(self))
         return self._engine
 
     def _sync_weights(self, eng):

@@ -397,9 +397,29 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     engines: the draw is keyed on the global uid, so N ranks play the one-rank set of games.  The random-mover player
     that fills the first buffer does NOT get it.  One log line says whether it is on.  A ValueError, before anything is
     built, for anything normalize_selfplay_openings or the rules refuse; Player refuses it where the games would run
-    through the host loop.  Its effect on playing strength and on training efficiency is NOT measured."""
+    through the host loop.  Its effect on playing strength and on training efficiency is NOT measured.
+
+    config["fpu"] = true, "absolute" / "reduction", (mode, value, reduction, root_reduction) or a dict with those keys
+    (default absent; NOT the reference's behaviour, and outside every parity claim): first-play urgency -- every search
+    made for the trained policy scores an unvisited child with Q = fpu instead of Q = 0 (Engine.set_fpu, include/azx.h
+    has the definition).  It is a property of the search, not one of the self-play options above: it is put on the
+    policy (Policy.set_fpu), so the self-play Player's engines and every later evaluation of that policy object play
+    with it; an absent key leaves the policy's own setting alone.  The defaults are lc0's / KataGo's customary values
+    as the author recalls them and are not checked here.  One log line says whether it is on.  A ValueError, before
+    anything is built, for anything azalea_amd.fpu.normalize_fpu refuses.  DESIGN 7.20 has what was and was not
+    measured."""
     from .selfplay_options import from_config
+    from . import fpu as _fpu
     option_keywords, option_lines = from_config(config, policy)
+    if "fpu" in config:
+        try:
+            policy.fpu = _fpu.normalize_fpu(config["fpu"])
+        except ValueError as exc:
+            raise ValueError("config['fpu']: %s" % exc) from None
+    policy_fpu = _fpu.policy_fpu(policy)
+    option_lines = list(option_lines) + [
+        "first-play urgency (config['fpu']): %s" % ("off" if policy_fpu is None else
+            "on -- NOT the reference's behaviour: mode %s, value %g, reduction %g, root reduction %g" % policy_fpu)]
     apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])

@@ -1097,6 +1097,61 @@ int azx_selftest_rollout(int device, int board_size, int n, const int32_t *board
                          int32_t *wins, float *value, float *prior, uint8_t *fills /* NULL or [n][min(rollouts,64)][cells] */);
 int azx_rollout_stats(azx_engine *e, int64_t out4[4]);
 
+/* ---- First-play urgency (FPU) for the PUCT search -----------------------------------------------------------------
+ * NOT the reference's behaviour (an unvisited child scores with Q = 0 there: mcts.py:119-136, oracle/mcts.c:101-113,
+ * and that stays the default); additive, off unless asked for, and outside every parity claim.  A property of the
+ * ENGINE'S SEARCH, not a self-play option: it holds in every search the engine runs -- azx_search, the phase API,
+ * throughput self-play, matches and tournaments (each engine with its own setting; they are not refused).
+ *
+ * THE DEFINITION (the tree kernels, azx_fpu_score and the tests' restatement are held to it bit for bit; csrc/fpu.h is
+ * the one text the kernels and the host compile).  Every place that computes PUCT scores over a node's children
+ * changes in exactly one term: a child with nv_j == 0.0f takes Q_j = fpu in place of -tv_j / max(nv_j, 1).  nv and tv
+ * are the arrays as they stand at that select, virtual losses included; they are integer-valued, so the test is exact.
+ * Everything else is untouched: U, the noise mix at the root, visited children, the first-maximum argmax, virtual
+ * loss, dedup, expand, backup.
+ *   AZX_FPU_ABSOLUTE:  fpu = value, in [-1, 1].
+ *   AZX_FPU_REDUCTION: fpu = Qp - (r * sqrtf(mass)), every operation a separate float32 operation (no contraction,
+ *     IEEE divide and square root), where
+ *       Qp   = tv_p / max(nv_p, 1.0f), the node's own mean value in its mover's view (the root's evaluation is not
+ *              backed up and the root takes no virtual loss, so a fresh root has Qp = 0);
+ *       r    = root_reduction at the search's root, reduction at every other node;
+ *       mass = (float)M * (1.0f / 16777216.0f);
+ *       M    = the sum, over the node's children with nv_j > 0, of (uint32_t)(prior_prob_j * 16777216.0f) -- the
+ *              STORED prior, not the noise-mixed one; an integer sum, so neither lane order nor the shape of the
+ *              reduction can change a bit.  (Priors are taken to lie in [0, 1]; others are not defined here.)
+ *   No clamp is applied.
+ * Interactions: forced playouts still override the root argmax, and the argmax they override is computed with FPU;
+ * the Gumbel root search replaces the root's selection, so root_reduction is unused there and FPU acts below the root;
+ * playout cap, resignation, early stop, training targets, opening books and the random reflection are orthogonal.
+ * With the option never set, or set and then set back to AZX_FPU_OFF, every output of the library is the same bytes
+ * as before this addition.  Not part of this: AlphaZero's visit-dependent c(s), a root policy temperature, any change
+ * of default.
+ *
+ * azx_set_fpu: mode AZX_FPU_OFF ignores the three parameters (they are stored as 0).  AZX_EINVAL, leaving the setting
+ *   in place, for an unknown mode, a NaN parameter, |value| > 1 or a negative reduction; AZX_ESTATE while a phase-API
+ *   search is in flight (between azx_search_begin and the last azx_search_step).  Zeroes azx_fpu_stats.
+ * azx_fpu_stats: since the last azx_set_fpu, summed over the engine's games:
+ *   [0] selects made under the option (a select that ends on a leaf already in flight in its batch counts too, so this
+ *       equals the search counters' select count of the same searches);
+ *   [1] node levels scored under the option at which at least one unvisited child existed;
+ *   [2] selects that ended on a child with no visit (virtual losses count as visits);
+ *   [3] selects whose choice differs from the OFF rule's: NOT computed -- it needs a second scoring pass at every level
+ *       -- and always 0.
+ * azx_fpu_score: the definition on the host for ONE node without root noise, no GPU: child_out = the index PUCT takes
+ *   among k children with (nv[j], tv[j], prior[j]) at a node with (nv_p, tv_p), c_puct as a float32; is_root chooses
+ *   root_reduction.  mode AZX_FPU_OFF gives the reference's choice.  AZX_EINVAL for k < 1, null pointers or parameters
+ *   azx_set_fpu would refuse.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_fpu). */
+#define AZX_FPU_OFF       0
+#define AZX_FPU_ABSOLUTE  1
+#define AZX_FPU_REDUCTION 2
+int azx_set_fpu(azx_engine *e, int mode, float value, float reduction, float root_reduction);
+int azx_get_fpu(azx_engine *e, int *mode, float *value, float *reduction, float *root_reduction);
+int azx_fpu_stats(azx_engine *e, int64_t out4[4]);
+int azx_fpu_score(int mode, float value, float reduction, float root_reduction, int is_root, int k, float nv_p, float tv_p,
+                  const float *nv, const float *tv, const float *prior, float c_puct, int32_t *child_out);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

@@ -58,7 +58,7 @@ def is_wide_any(kn):
 
 
 def is_play2(kn):
-    return "k_playILi2" in kn or "k_play<2>" in kn
+    return "k_playILi2" in kn or "k_play<2" in kn        # k_play<2> before first-play urgency, k_play<2, false> since
 
 
 def dur_ms(r):
