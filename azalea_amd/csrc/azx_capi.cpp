@@ -89,6 +89,31 @@ struct SelfplayOptions {
     }
 };
 
+// ---- the launch schedule of one search ---------------------------------------------------------------------
+// With nb = num_batches, a search of an engine whose evaluations are launches of their own (the network, a registered
+// evaluator, the phase API's caller) is the phases
+//   0          k_mcts MODE_BEGIN                then an evaluation
+//   1 .. nb    k_mcts MODE_APPLY | MODE_SELECT  then an evaluation
+//   nb + 1     k_mcts MODE_APPLY                ends the search
+// on one stream.  Every driver issues them through enqueue_tree_phase, and all but the pipelined play loop walk them
+// with a SearchCursor (search_advance, further down).
+struct PhaseMode { int bits; bool then_eval; };     // a tree launch's MODE_* bits; an evaluation of the leaves it queued follows
+static PhaseMode phase_mode(int ph, int nb) {
+    if (ph == 0) return {MODE_BEGIN, true};
+    if (ph <= nb) return {MODE_APPLY | MODE_SELECT, true};
+    return {MODE_APPLY, false};
+}
+
+// Where a search stands: the next phase to issue.  A cursor not yet begun is done.
+struct SearchCursor {
+    int next = 0, last = -1;
+    bool timed = false;             // its launches go into the timing pool (the throughput calls)
+    bool by_caller = false;         // the phase API's: on an AZX_EVAL_EXTERNAL engine the caller evaluates between the phases
+    SearchCursor() {}
+    SearchCursor(int nb, bool timed_, bool by_caller_) : last(nb + 1), timed(timed_), by_caller(by_caller_) {}
+    bool done() const { return next > last; }
+};
+
 struct azx_engine {
     azx_config cfg;
     DevEngine d;
@@ -108,10 +133,9 @@ struct azx_engine {
     int32_t *moveids_dev = nullptr;
     int32_t *slots_dev = nullptr, *moves_dev = nullptr, *nmoves_dev = nullptr;
     size_t moves_cap = 0;
+    SearchCursor phase_api;                     // azx_search_begin / azx_search_step: their search, in flight while !done()
     // external evaluator bookkeeping
-    bool ext_active = false;
-    int ext_batches_done = 0;
-    std::vector<int> ext_order;                 // eval indices sorted by (slot, leaf)
+    std::vector<int> ext_order;                // eval indices sorted by (slot, leaf)
     std::vector<std::vector<int>> ext_cells;    // original legal cells per sorted entry
     // registered device evaluator (azx_set_external_evaluator): the hand-over buffers, the last host read of
     // ext.info, and the slots a failed evaluation left with half-done searches (refused until azx_reset)
@@ -706,7 +730,7 @@ extern "C" int azx_reset(azx_engine *e, const int32_t *slots, int n_slots, const
                      moves ? e->nmoves_dev : nullptr, stride, 1, e->stream);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(e->stream));
-    e->ext_active = false;
+    e->phase_api = SearchCursor();
     if (e->ext_failed) {
         for (int i = 0; i < n_slots; ++i) e->ext_dirty[slots ? slots[i] : i] = 0;
         e->ext_failed = std::find(e->ext_dirty.begin(), e->ext_dirty.end(), 1) != e->ext_dirty.end();
@@ -840,7 +864,7 @@ static int ext_fail(azx_engine *e, const char *fmt, ...) {
     (void)hipMemcpyAsync(e->ext.info + 2, &clear, sizeof clear, hipMemcpyHostToDevice, e->stream);
     (void)hipStreamSynchronize(e->stream);
     e->ext_info[2] = clear;
-    e->ext_active = false;
+    e->phase_api = SearchCursor();
     e->ev_used = 0;                       // the timed launches of the failed call are not booked
     e->ev_groups = 0;
     e->ext_failed = true;
@@ -915,43 +939,54 @@ static int ext_point_finish(azx_engine *e, bool timed) {
     return AZX_OK;
 }
 
-// The search of an engine with a registered evaluator as a cursor over its num_batches + 1 evaluation points.
-// begin: the first tree phase and its point's first half are on the stream.  resume: the point's second half (host
-// sync, callback), then the next tree phase with its point's first half -- or, after the last point, the final
-// APPLY, which ends the search.  enqueue_search runs the cursor to its end on the one stream; azx_match_play
-// advances two engines' cursors in turn.
-struct ExtCursor {
-    int points = 0;         // evaluation points after the first whose tree phase has been enqueued
-    bool done = true;
-    bool timed = false;
+// Where the launches of one phase of a search (the schedule: phase_mode, above azx_engine) go: the pool or half-pool they cover, its stream, and how they are timed -- `group` and `ref`
+// as time_begin takes them.  The defaults are the whole pool on the engine stream, each launch timed on its own.
+struct PhaseWhere {
+    const DevEngine *view;
+    hipStream_t stream;
+    bool timed;
+    int group = 0, ref = -1;
 };
+static PhaseWhere whole_pool(azx_engine *e, bool timed) { return {&e->d, e->stream, timed}; }
 
-static int ext_search_begin(azx_engine *e, ExtCursor *c, bool timed) {
-    c->points = 0;
-    c->done = false;
-    c->timed = timed;
-    HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
-    if (timed) time_begin(e);
-    azx_launch_mcts(e->d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
-    if (timed) time_end(e);
-    return ext_point_enqueue(e, timed);
+// a tree launch with its timing pair: every k_mcts launch of a search, and the uniform evaluators' fused one
+static void launch_tree(azx_engine *e, const PhaseWhere &w, int mode) {
+    if (w.timed) time_begin(e, 0, w.stream, w.group, w.ref);
+    azx_launch_mcts(*w.view, mode, e->num_batches, w.stream, e->force_generic);
+    if (w.timed) time_end(e, 1, w.stream);
 }
 
-static int ext_search_resume(azx_engine *e, ExtCursor *c) {
-    TRY(ext_point_finish(e, c->timed));
-    if (c->points < e->num_batches) {
-        HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
-        if (c->timed) time_begin(e);
-        azx_launch_mcts(e->d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
-        if (c->timed) time_end(e);
-        c->points += 1;
-        return ext_point_enqueue(e, c->timed);
-    }
-    if (c->timed) time_begin(e);
-    azx_launch_mcts(e->d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
-    if (c->timed) time_end(e);
-    c->done = true;
+// the tree launch of phase `ph`; a phase that queues leaves for an evaluation starts from an empty queue
+static int enqueue_tree_phase(azx_engine *e, const PhaseWhere &w, int ph) {
+    const PhaseMode m = phase_mode(ph, e->num_batches);
+    if (m.then_eval) HIPCHECK(hipMemsetAsync(w.view->n_eval, 0, sizeof(int32_t), w.stream));
+    launch_tree(e, w, m.bits);
     return AZX_OK;
+}
+
+// the network's evaluation of the leaves a phase queued
+static void enqueue_net_eval(azx_engine *e, const PhaseWhere &w) {
+    if (w.timed) time_begin(e, 1, w.stream);
+    azx_net_eval(e->net, *w.view, w.stream);
+    if (w.timed) time_end(e, 1, w.stream);
+}
+
+// Issues the cursor's next phase on the engine stream: the tree launch and, after phases 0 .. nb, what evaluates the
+// leaves it queued -- the network's launches, the first half of a registered evaluator's point, or nothing, where
+// the phase API's caller evaluates.  A registered evaluator's point is finished (host sync, callback: its second half)
+// at the start of the next call, so that all the host can enqueue without waiting is on the stream before it waits.
+// enqueue_search runs a cursor to its end; ply_searches advances several engines' cursors in turn; the phase API
+// advances the engine's own by one phase per call.
+static int search_advance(azx_engine *e, SearchCursor *c) {
+    const bool net = e->d.evaluator == AZX_EVAL_RESNET, point = !net && !c->by_caller;
+    const PhaseWhere w = whole_pool(e, c->timed);
+    if (point && c->next > 0) TRY(ext_point_finish(e, c->timed));
+    const int ph = c->next++;
+    if (ph == 0 && net && !azx_net_ready(e->net)) return fail(AZX_ESTATE, "azx_set_weights has not been called");
+    TRY(enqueue_tree_phase(e, w, ph));
+    if (!phase_mode(ph, e->num_batches).then_eval) return AZX_OK;
+    if (net) enqueue_net_eval(e, w);
+    return point ? ext_point_enqueue(e, c->timed) : AZX_OK;
 }
 
 // the hand-over buffers of a registered evaluator, made at the first registration and kept
@@ -1094,45 +1129,23 @@ extern "C" int azx_selftest_rollout(int device, int board_size, int n, const int
 }
 
 // one whole search on the stream (no host sync) for the device-side evaluators; with a registered external
-// evaluator the host takes part at every evaluation point (the ExtCursor run to its end) and the call returns after the last one
+// evaluator the host takes part at every evaluation point and the call returns after the last one
 static int enqueue_search(azx_engine *e, bool timed) {
-    DevEngine &d = e->d;
-    if (ext_registered(e)) {
-        ExtCursor c;
-        TRY(ext_search_begin(e, &c, timed));
-        while (!c.done) TRY(ext_search_resume(e, &c));
+    const int ev = e->d.evaluator;
+    if (ev == AZX_EVAL_UNIFORM || ev == AZX_EVAL_UNIFORM_HASH) {
+        launch_tree(e, whole_pool(e, timed), MODE_BEGIN | MODE_INLINE);     // evaluated inside the kernel: all phases in one launch
         return AZX_OK;
     }
-    if (d.evaluator == AZX_EVAL_UNIFORM || d.evaluator == AZX_EVAL_UNIFORM_HASH) {
-        if (timed) time_begin(e);
-        azx_launch_mcts(d, MODE_BEGIN | MODE_INLINE, e->num_batches, e->stream, e->force_generic);
-        if (timed) time_end(e);
-        return AZX_OK;
-    }
-    if (d.evaluator == AZX_EVAL_RESNET) {
-        if (!azx_net_ready(e->net)) return fail(AZX_ESTATE, "azx_set_weights has not been called");
-        HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
-        if (timed) time_begin(e);
-        azx_launch_mcts(d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
-        if (timed) time_end(e);
-        if (timed) time_begin(e, 1);
-        azx_net_eval(e->net, d, e->stream);
-        if (timed) time_end(e);
-        for (int b = 0; b < e->num_batches; ++b) {
-            HIPCHECK(hipMemsetAsync(d.n_eval, 0, sizeof(int32_t), e->stream));
-            if (timed) time_begin(e);
-            azx_launch_mcts(d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
-            if (timed) time_end(e);
-            if (timed) time_begin(e, 1);
-            azx_net_eval(e->net, d, e->stream);
-            if (timed) time_end(e);
-        }
-        if (timed) time_begin(e);
-        azx_launch_mcts(d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
-        if (timed) time_end(e);
-        return AZX_OK;
-    }
-    return fail(AZX_ESTATE, "evaluator %d has no device pipeline", d.evaluator);
+    if (ev != AZX_EVAL_RESNET && !ext_registered(e)) return fail(AZX_ESTATE, "evaluator %d has no device pipeline", ev);
+    SearchCursor c(e->num_batches, timed, false);
+    while (!c.done()) TRY(search_advance(e, &c));
+    return AZX_OK;
+}
+
+// how a call that searched ends: the last import's checks, or the network's range check
+static int search_outcome(azx_engine *e) {
+    if (ext_registered(e)) return ext_read_info(e);
+    return check_net_range(e);
 }
 
 extern "C" int azx_search(azx_engine *e, const double *noise, int n_select, int noise_stride,
@@ -1146,8 +1159,7 @@ extern "C" int azx_search(azx_engine *e, const double *noise, int n_select, int 
     TRY(enqueue_search(e, false));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(e->stream));
-    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
-    return check_net_range(e);
+    return search_outcome(e);
 }
 
 static int read_pending(azx_engine *e, int *n_pending) {
@@ -1166,32 +1178,23 @@ extern "C" int azx_search_begin(azx_engine *e, const double *noise, int n_select
     if (e->d.evaluator != AZX_EVAL_EXTERNAL && e->d.evaluator != AZX_EVAL_RESNET)
         return fail(AZX_ESTATE, "phase API needs AZX_EVAL_EXTERNAL (or RESNET)");
     TRY(upload_noise(e, noise, n_select, noise_stride, noise_scale));
-    HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
-    if (e->d.evaluator == AZX_EVAL_RESNET && !azx_net_ready(e->net))
-        return fail(AZX_ESTATE, "azx_set_weights has not been called");
-    azx_launch_mcts(e->d, MODE_BEGIN, e->num_batches, e->stream, e->force_generic);
-    if (e->d.evaluator == AZX_EVAL_RESNET) azx_net_eval(e->net, e->d, e->stream);
+    SearchCursor c(e->num_batches, false, true);
+    TRY(search_advance(e, &c));
     HIPCHECK(hipGetLastError());
-    e->ext_active = true;
-    e->ext_batches_done = 0;
+    e->phase_api = c;                   // in flight from here on
     return read_pending(e, n_pending);
 }
 
 extern "C" int azx_search_step(azx_engine *e, int *n_pending, int *done) {
     if (!e || !n_pending || !done) return fail(AZX_EINVAL, "null argument");
     ENGINE_GUARD(e);
-    if (!e->ext_active) return fail(AZX_ESTATE, "azx_search_step without azx_search_begin");
-    HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
-    if (e->ext_batches_done < e->num_batches) {
-        azx_launch_mcts(e->d, MODE_APPLY | MODE_SELECT, e->num_batches, e->stream, e->force_generic);
-        if (e->d.evaluator == AZX_EVAL_RESNET) azx_net_eval(e->net, e->d, e->stream);
-        e->ext_batches_done += 1;
-        *done = 0;
-    } else {
-        azx_launch_mcts(e->d, MODE_APPLY, e->num_batches, e->stream, e->force_generic);
-        e->ext_active = false;
-        *done = 1;
-    }
+    SearchCursor &c = e->phase_api;
+    if (c.done()) return fail(AZX_ESTATE, "azx_search_step without azx_search_begin");
+    // the host reads n_eval back after every phase, the last included: that one queues nothing and so leaves the
+    // count alone, which is zeroed here
+    if (!phase_mode(c.next, e->num_batches).then_eval) HIPCHECK(hipMemsetAsync(e->d.n_eval, 0, sizeof(int32_t), e->stream));
+    TRY(search_advance(e, &c));
+    *done = c.done() ? 1 : 0;
     HIPCHECK(hipGetLastError());
     return read_pending(e, n_pending);
 }
@@ -1387,7 +1390,7 @@ extern "C" int azx_advance(azx_engine *e, const int32_t *move_ids) {
     azx_launch_advance(d, e->moveids_dev, 0, e->stream);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(e->stream));
-    e->ext_active = false;
+    e->phase_api = SearchCursor();
     return AZX_OK;
 }
 
@@ -1576,13 +1579,6 @@ static void fill_stats(const CounterSnap &a, const CounterSnap &b, azx_play_stat
     st->sum_game_length = b.s[4] - a.s[4];
 }
 
-static int enqueue_ply(azx_engine *e) {
-    TRY(enqueue_search(e, true));
-    azx_launch_choose(e->d, e->stream);
-    azx_launch_advance(e->d, nullptr, 1, e->stream);
-    return AZX_OK;
-}
-
 // `plies` moves of the resnet play loop as two half-pools (use_pipeline): half A on the engine stream, half B on
 // stream_b.  Each half's phases follow each other on its own stream only; the host issues them phase by phase,
 // alternating the halves, so that one half's tower is queued while the other half runs its search phases.  Half B
@@ -1610,14 +1606,17 @@ static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
     // the launch statistics count one phase's two half-pool launches as one launch of the whole pool
     const int ref = time_mark(e, hs[0]);
     for (int64_t p = 0; p < plies; ++p) {
-        // phase 0: BEGIN; phases 1..nb: APPLY|SELECT; each followed by the half's network evaluation
-        for (int ph = 0; ph <= nb; ++ph) {
-            const int g_tree = ++e->ev_groups, g_net = ++e->ev_groups;
+        // every phase's tree launch, followed by the half's network evaluation or, after the last, by the move
+        for (int ph = 0; ph <= nb + 1; ++ph) {
+            const bool then_eval = phase_mode(ph, nb).then_eval;
+            const int g_tree = ++e->ev_groups, g_net = then_eval ? ++e->ev_groups : 0;
             for (int h = 0; h < 2; ++h) {
-                HIPCHECK(hipMemsetAsync(hv[h].n_eval, 0, sizeof(int32_t), hs[h]));
-                time_begin(e, 0, hs[h], g_tree, ref);
-                azx_launch_mcts(hv[h], ph ? MODE_APPLY | MODE_SELECT : MODE_BEGIN, nb, hs[h], e->force_generic);
-                time_end(e, 1, hs[h]);
+                TRY(enqueue_tree_phase(e, {&hv[h], hs[h], true, g_tree, ref}, ph));
+                if (!then_eval) {
+                    azx_launch_choose(hv[h], hs[h]);
+                    azx_launch_advance(hv[h], nullptr, 1, hs[h]);
+                    continue;
+                }
                 if (p == 0 && ph == 0 && h == 0) {
                     HIPCHECK(hipEventRecord(e->ev_fork, hs[0]));
                     HIPCHECK(hipStreamWaitEvent(hs[1], e->ev_fork, 0));
@@ -1635,19 +1634,78 @@ static int enqueue_plies_pipelined(azx_engine *e, int64_t plies) {
                 }
             }
         }
-        const int g_tree = ++e->ev_groups;
-        for (int h = 0; h < 2; ++h) {
-            time_begin(e, 0, hs[h], g_tree, ref);
-            azx_launch_mcts(hv[h], MODE_APPLY, nb, hs[h], e->force_generic);
-            time_end(e, 1, hs[h]);
-            azx_launch_choose(hv[h], hs[h]);
-            azx_launch_advance(hv[h], nullptr, 1, hs[h]);
-        }
     }
     HIPCHECK(hipEventRecord(e->ev_join, hs[1]));
     HIPCHECK(hipStreamWaitEvent(hs[0], e->ev_join, 0));
     return AZX_OK;
 }
+
+// `want` plies on the engine's stream(s), by the first way of three that applies.  The uniform-evaluator path plays
+// the moves in persistent launches (k_play), at most `chunk_cap` moves each; its time is booked per move like the
+// per-move launches'.  Otherwise the two half-pools or per-move launches play the rest, at most `else_plies` of it.
+// *enqueued: how many plies are on the stream.
+static int enqueue_plies(azx_engine *e, int64_t want, int chunk_cap, int64_t else_plies, int64_t *enqueued) {
+    int64_t p = 0;
+    while (p < want) {
+        const int n = (int)std::min<int64_t>(chunk_cap, want - p);
+        time_begin(e);
+        if (!azx_launch_play(e->d, e->num_batches, n, e->stream, !e->force_generic && !e->no_persistent)) break;
+        time_end(e, n);                     // (a begin event without its end is simply overwritten by the next one)
+        p += n;
+    }
+    if (p < want) {
+        const int64_t rest = std::min(else_plies, want - p);
+        if (use_pipeline(e)) TRY(enqueue_plies_pipelined(e, rest));
+        else for (int64_t i = 0; i < rest; ++i) {
+            TRY(enqueue_search(e, true));
+            azx_launch_choose(e->d, e->stream);
+            azx_launch_advance(e->d, nullptr, 1, e->stream);
+        }
+        p += rest;
+    }
+    *enqueued = p;
+    return AZX_OK;
+}
+
+// One throughput self-play call from the first thing it puts on the device to its stats.  The scope hands the launches
+// the engine's self-play options; the two events take the call's wall time on the engine stream and are released on
+// every way out, an early error return included.  The caller sets the harvest queue up (play_setup) between the
+// construction and begin().
+struct PlayRun {
+    azx_engine *e;
+    SelfplayScope scope;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    CounterSnap before;
+    explicit PlayRun(azx_engine *e_) : e(e_), scope(e_) {}
+    ~PlayRun() { for (hipEvent_t ev : {t0, t1}) if (ev) (void)hipEventDestroy(ev); }
+
+    int begin() {
+        TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
+        TRY(snap_counters(e, &before));
+        HIPCHECK(hipEventCreate(&t0));
+        HIPCHECK(hipEventCreate(&t1));
+        HIPCHECK(hipEventRecord(t0, e->stream));
+        // slots parked by an earlier azx_play* call rejoin: games that finished while the queue was full hand their
+        // rows over first (a ring queue always has room)
+        azx_launch_advance(e->d, nullptr, 2, e->stream);
+        return AZX_OK;
+    }
+
+    // `positions`: the rows the caller counted, or -1 for the rows the games' counters saw
+    int finish(azx_play_stats *stats, int64_t positions) {
+        HIPCHECK(hipEventRecord(t1, e->stream));
+        HIPCHECK(hipStreamSynchronize(e->stream));
+        float ms = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms, t0, t1));
+        CounterSnap after;
+        TRY(snap_counters(e, &after));
+        fill_stats(before, after, stats);
+        stats->positions = positions >= 0 ? positions : (int64_t)(after.c[CTR_ROWS] - before.c[CTR_ROWS]);
+        stats->seconds = ms * 1e-3;
+        time_collect(e, stats);
+        return search_outcome(e);
+    }
+};
 
 extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stats) {
     if (!e || !stats) return fail(AZX_EINVAL, "null argument");
@@ -1656,46 +1714,14 @@ extern "C" int azx_play_steps(azx_engine *e, int64_t plies, azx_play_stats *stat
     if (e->d.evaluator == AZX_EVAL_EXTERNAL && !ext_registered(e))
         return fail(AZX_ESTATE, "play mode needs a device evaluator");
     memset(stats, 0, sizeof *stats);
-    SelfplayScope selfplay_scope(e);
+    PlayRun run(e);
     TRY(play_setup(e, std::max<int64_t>(e->q_alloc, 1 << 16), 1));
-    TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
-    CounterSnap a, b;
-    TRY(snap_counters(e, &a));
-    hipEvent_t t0, t1;
-    HIPCHECK(hipEventCreate(&t0));
-    HIPCHECK(hipEventCreate(&t1));
-    HIPCHECK(hipEventRecord(t0, e->stream));
-    azx_launch_advance(e->d, nullptr, 2, e->stream);     // slots parked by an earlier azx_play* call rejoin (ring queue: always room)
-    {
-        // the uniform-evaluator path plays the moves in persistent launches (k_play), at most
-        // PLAY_CHUNK moves each; its time is booked per move like the per-move launches'
-        const int PLAY_CHUNK = 256;
-        int64_t p = 0;
-        while (p < plies) {
-            const int n = (int)std::min<int64_t>(PLAY_CHUNK, plies - p);
-            time_begin(e);
-            const bool ok = azx_launch_play(e->d, e->num_batches, n, e->stream, !e->force_generic && !e->no_persistent);
-            if (!ok) break;                 // (the begin event is simply overwritten by the next one)
-            time_end(e, n);
-            p += n;
-        }
-        if (p < plies && use_pipeline(e)) TRY(enqueue_plies_pipelined(e, plies - p));
-        else for (; p < plies; ++p) TRY(enqueue_ply(e));
-    }
-    HIPCHECK(hipEventRecord(t1, e->stream));
+    TRY(run.begin());
+    const int PLAY_CHUNK = 256;
+    int64_t done = 0;
+    TRY(enqueue_plies(e, plies, PLAY_CHUNK, plies, &done));
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHECK(hipEventElapsedTime(&ms, t0, t1));
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    TRY(snap_counters(e, &b));
-    fill_stats(a, b, stats);
-    stats->positions = (int64_t)(b.c[CTR_ROWS] - a.c[CTR_ROWS]);
-    stats->seconds = ms * 1e-3;
-    time_collect(e, stats);
-    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
-    return check_net_range(e);
+    return run.finish(stats, -1);
 }
 
 // play whole games into the harvest queue until it holds >= min_positions rows
@@ -1703,37 +1729,23 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
                       unsigned long long *rows_out) {
     DevEngine &d = e->d;
     memset(stats, 0, sizeof *stats);
-    SelfplayScope selfplay_scope(e);
+    PlayRun run(e);
     const int64_t worst = min_positions + (int64_t)d.G * d.ncells;
     TRY(play_setup(e, worst, 0));
     if (e->dbg_qcap > 0)                                // tests (azx_debug_set_queue_cap): a queue too small, so that slots get parked
         d.q_cap = std::max<int64_t>(1, std::min<int64_t>(d.q_cap, e->dbg_qcap));
-    TRY(upload_noise(e, nullptr, 0, 0, e->cfg.noise_scale));
-    CounterSnap a, b;
-    TRY(snap_counters(e, &a));
-    hipEvent_t t0, t1;
-    HIPCHECK(hipEventCreate(&t0));
-    HIPCHECK(hipEventCreate(&t1));
-    HIPCHECK(hipEventRecord(t0, e->stream));
-    // games that finished while the queue was full (parked slots) hand their rows over first
-    azx_launch_advance(d, nullptr, 2, e->stream);
+    TRY(run.begin());
     unsigned long long rows = 0;
     for (int64_t p = 0; (max_plies <= 0 || p < max_plies) && (int64_t)rows < min_positions;) {
         // with the uniform evaluator a few moves per persistent launch (k_play) between looks at the
         // queue; Player.read may return more than it was asked for anyway (whole games only)
         // (at most 2N - 1 moves, the shortest possible game: a slot then finishes at most one game
-        // per launch and the queue bound min_positions + n_games * cells still holds)
+        // per launch and the queue bound min_positions + n_games * cells still holds); else one move per look
         const int64_t most = std::min<int64_t>(8, 2 * d.N - 1);
         const int chunk = (int)std::min<int64_t>(most, max_plies > 0 ? max_plies - p : most);
-        time_begin(e);
-        if (azx_launch_play(d, e->num_batches, chunk, e->stream, !e->force_generic && !e->no_persistent)) {
-            time_end(e, chunk);
-            p += chunk;
-        } else {
-            if (use_pipeline(e)) TRY(enqueue_plies_pipelined(e, 1));
-            else TRY(enqueue_ply(e));
-            p += 1;
-        }
+        int64_t done = 0;
+        TRY(enqueue_plies(e, chunk, chunk, 1, &done));
+        p += done;
         HIPCHECK(hipMemcpyAsync(&rows, d.q_count, sizeof rows, hipMemcpyDeviceToHost, e->stream));
         HIPCHECK(hipStreamSynchronize(e->stream));
         // a bounded queue (azx_debug_set_queue_cap) below min_positions parks every slot sooner or later: with
@@ -1747,20 +1759,10 @@ static int play_until(azx_engine *e, int64_t min_positions, int64_t max_plies, a
             if (!any) break;
         }
     }
-    HIPCHECK(hipEventRecord(t1, e->stream));
-    HIPCHECK(hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHECK(hipEventElapsedTime(&ms, t0, t1));
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    TRY(snap_counters(e, &b));
-    fill_stats(a, b, stats);
-    stats->positions = (int64_t)rows;
-    stats->seconds = ms * 1e-3;
-    time_collect(e, stats);
+    TRY(run.finish(stats, (int64_t)rows));
     *rows_out = rows;
-    if (ext_registered(e)) return ext_read_info(e);   // the last import's checks
-    return check_net_range(e);
+    e->q_rows_valid = (int64_t)rows;
+    return AZX_OK;
 }
 
 // rows [first, first + n) of the harvest queue to the host in azx_play's layout (any pointer may be null): widen /
@@ -1811,7 +1813,6 @@ extern "C" int azx_play(azx_engine *e, int64_t min_positions, int64_t max_plies,
                     (long long)cap, (long long)worst);
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
-    e->q_rows_valid = (int64_t)rows;
     return rows_read(e, 0, (int64_t)rows, board, color, nlegal, moves_prob, reward, game_uid);
 }
 
@@ -1824,7 +1825,6 @@ extern "C" int azx_play_device(azx_engine *e, int64_t min_positions, int64_t max
         return fail(AZX_ESTATE, "play mode needs a device evaluator");
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
-    e->q_rows_valid = (int64_t)rows;
     *rows_out = (int64_t)rows;
     return AZX_OK;
 }
@@ -1993,7 +1993,6 @@ extern "C" int azx_replay_fill(azx_engine *e, int64_t min_positions, int64_t max
         return fail(AZX_ESTATE, "play mode needs a device evaluator");
     unsigned long long rows = 0;
     TRY(play_until(e, min_positions, max_plies, stats, &rows));
-    e->q_rows_valid = (int64_t)rows;
     DevEngine &d = e->d;
     const ReplayRows src = {d.q_board, d.q_prob, d.q_color, d.q_k, d.q_reward};
     if (rows) TRY(ring_put(e, src, (int64_t)rows));
@@ -2493,7 +2492,7 @@ static int fpu_check(int mode, float value, float reduction, float root_reductio
 extern "C" int azx_set_fpu(azx_engine *e, int mode, float value, float reduction, float root_reduction) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     TRY(fpu_check(mode, value, reduction, root_reduction));
-    if (e->ext_active)
+    if (!e->phase_api.done())
         return fail(AZX_ESTATE, "fpu: a phase-API search is in flight (finish it with azx_search_step first)");
     ENGINE_GUARD(e);
     TRY(zero_game_counters(e, e->d.fpu_ctr, FPU_COUNT));
@@ -2784,7 +2783,7 @@ extern "C" int azx_selfplay_openings_stats(azx_engine *e, int64_t cap, int64_t *
 //   a's search + move draw            (a's stream)  |  b's search + move draw  (b's stream, forked / joined by events)
 //   k_match_step                      (a's stream)  hand-over, game step in both engines, settle, refill
 // and reads back ONE word, the number of games decided.  An engine with a registered external evaluator cannot be
-// enqueued whole: the host takes part at each of its evaluation points.  Its search is then a cursor (ExtCursor)
+// enqueued whole: the host takes part at each of its evaluation points.  Its search is then a cursor (SearchCursor)
 // that the ply advances point by point, after everything that needs no host is on the streams and in turn with the
 // other engine's cursor when both are external (ply_searches).
 //
@@ -2800,7 +2799,7 @@ struct PlyLoop {
     unsigned long long *host_word = nullptr;     // pinned: the per-ply read-back
     hipEvent_t ev_fork = nullptr, t0 = nullptr, t1 = nullptr;
     std::vector<hipEvent_t> ev_join;             // [K - 1]: engine k's stream back into engine 0's
-    std::vector<ExtCursor> cur;                  // [K]: the external engines' searches of the current ply
+    std::vector<SearchCursor> cur;                 // [K]: the external engines' searches of the current ply
     int sink = -1;                               // *_set_harvest: the engine whose harvest queue takes the won games' rows
     int first_mode = -1;                         // *_set_first_mover
     int64_t rows_last = 0;                       // rows the last play call harvested
@@ -2824,7 +2823,7 @@ static hipError_t loop_create(PlyLoop &L, hipError_t err, azx_engine *const *eng
     L.noun = noun;
     L.letters = letters;
     L.ev_join.assign((size_t)K - 1, nullptr);
-    L.cur.assign((size_t)K, ExtCursor());
+    L.cur.assign((size_t)K, SearchCursor());
     if (err == hipSuccess) err = hipHostMalloc((void **)&L.host_word, sizeof(unsigned long long), hipHostMallocDefault);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming);
     for (hipEvent_t &ev : L.ev_join)
@@ -2970,27 +2969,21 @@ static int loop_fail(const PlyLoop &L, int k, int rc) {
 // and so the games, are the same either way.
 static int ply_searches(PlyLoop &L) {
     const int K = (int)L.eng.size();
-    if (!L.interleave) {
-        for (int k = 0; k < K; ++k) {
-            LOOP_TRY(k, enqueue_search(L.eng[k], false));
-            azx_launch_choose(L.eng[k]->d, L.eng[k]->stream);
-        }
-        return AZX_OK;
-    }
     for (int k = 0; k < K; ++k)
-        if (!ext_registered(L.eng[k])) {
+        if (!L.interleave || !ext_registered(L.eng[k])) {
             LOOP_TRY(k, enqueue_search(L.eng[k], false));
             azx_launch_choose(L.eng[k]->d, L.eng[k]->stream);
         }
+    if (!L.interleave) return AZX_OK;
     for (int k = 0; k < K; ++k) {
-        L.cur[k] = ExtCursor();
-        if (ext_registered(L.eng[k])) LOOP_TRY(k, ext_search_begin(L.eng[k], &L.cur[k], false));
+        L.cur[k] = ext_registered(L.eng[k]) ? SearchCursor(L.eng[k]->num_batches, false, false) : SearchCursor();
+        if (!L.cur[k].done()) LOOP_TRY(k, search_advance(L.eng[k], &L.cur[k]));
     }
     for (bool busy = true; busy;) {
         busy = false;
         for (int k = 0; k < K; ++k)
-            if (!L.cur[k].done) {
-                LOOP_TRY(k, ext_search_resume(L.eng[k], &L.cur[k]));
+            if (!L.cur[k].done()) {
+                LOOP_TRY(k, search_advance(L.eng[k], &L.cur[k]));
                 busy = true;
             }
     }

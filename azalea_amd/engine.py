@@ -211,23 +211,24 @@ class Engine:
         assert m.shape == (self.G,)
         check(self.L.azx_set_active(self.h, _p(m, C.c_int32)))
 
+    def _noise_args(self, noise):
+        """(rows pointer, n_select, stride) of azx_search / azx_search_begin for float64 [G, n_select, stride] host
+        Dirichlet rows, or for None; the array is returned with them to be kept alive over the call."""
+        if noise is None:
+            return (None, 0, 0), None
+        nz = np.ascontiguousarray(noise, np.float64)
+        assert nz.ndim == 3 and nz.shape[0] == self.G
+        return (_p(nz, C.c_double), nz.shape[1], nz.shape[2]), nz
+
     def search(self, noise=None, noise_scale=0.0):
         """noise: float64 [G, n_select, stride] host Dirichlet rows, or None."""
-        if noise is not None:
-            nz = np.ascontiguousarray(noise, np.float64)
-            assert nz.ndim == 3 and nz.shape[0] == self.G
-            self._check(self.L.azx_search(self.h, _p(nz, C.c_double), nz.shape[1], nz.shape[2], noise_scale))
-        else:
-            self._check(self.L.azx_search(self.h, None, 0, 0, noise_scale))
+        args, _keep = self._noise_args(noise)
+        self._check(self.L.azx_search(self.h, *args, noise_scale))
 
     def search_begin(self, noise=None, noise_scale=0.0):
         n = C.c_int(0)
-        if noise is not None:
-            nz = np.ascontiguousarray(noise, np.float64)
-            check(self.L.azx_search_begin(self.h, _p(nz, C.c_double), nz.shape[1], nz.shape[2],
-                                          noise_scale, C.byref(n)))
-        else:
-            check(self.L.azx_search_begin(self.h, None, 0, 0, noise_scale, C.byref(n)))
+        args, _keep = self._noise_args(noise)
+        check(self.L.azx_search_begin(self.h, *args, noise_scale, C.byref(n)))
         return n.value
 
     def search_step(self):
@@ -264,34 +265,31 @@ class Engine:
         check(self.L.azx_get_evals(self.h, cap, _p(v, C.c_float), _p(p, C.c_float), C.byref(n)))
         return v[:n.value], p[:n.value]
 
+    def _search_phases(self, on_leaves, noise, noise_scale):
+        """One search driven phase by phase: on_leaves(boards, legal_moves, slot, k) after every phase that left
+        leaves pending, in mcts.sample_paths' call order."""
+        n = self.search_begin(noise, noise_scale)
+        done = False
+        while not done:
+            if n:
+                on_leaves(*self.get_leaves())
+            n, done = self.search_step()
+
     def search_recorded(self, noise=None, noise_scale=0.0):
         """EVAL_RESNET search driven phase by phase, returning the evaluation tape
         [(slot, k, value, prior[:k])] in mcts.evaluate_batch order."""
         tape = []
-        n = self.search_begin(noise, noise_scale)
-        while True:
-            if n:
-                b, lm, slot, k = self.get_leaves()
-                v, p = self.get_evals()
-                for i in range(len(k)):
-                    tape.append((int(slot[i]), int(k[i]), np.float32(v[i]), p[i, :k[i]].copy()))
-            n, done = self.search_step()
-            if done:
-                break
+
+        def record(b, lm, slot, k):
+            v, p = self.get_evals()
+            tape.extend((int(slot[i]), int(k[i]), np.float32(v[i]), p[i, :k[i]].copy()) for i in range(len(k)))
+        self._search_phases(record, noise, noise_scale)
         return tape
 
     def search_external(self, evaluate, noise=None, noise_scale=0.0):
         """Drive one search with a host evaluator: evaluate(boards, legal_moves, slot, k) ->
         (value[n], prior[n, >=max k]).  Mirrors mcts.sample_paths' call order."""
-        n = self.search_begin(noise, noise_scale)
-        while True:
-            if n:
-                b, lm, slot, k = self.get_leaves()
-                v, p = evaluate(b, lm, slot, k)
-                self.put_evals(v, p)
-            n, done = self.search_step()
-            if done:
-                break
+        self._search_phases(lambda *leaves: self.put_evals(*evaluate(*leaves)), noise, noise_scale)
 
     # ---- results ------------------------------------------------------------------------
     def get_root(self):
