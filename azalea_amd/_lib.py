@@ -201,6 +201,11 @@ SYMBOLS = {
     "azx_fpu_stats": (C.c_int, [_vp, _i64p]),
     "azx_fpu_score": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float,
                                 _f32p, _f32p, _f32p, C.c_float, _i32p]),
+    # policy temperature of the search's priors (additions within revision 7; NOT the reference's behaviour)
+    "azx_set_policy_temp": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "azx_get_policy_temp": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "azx_policy_temp_stats": (C.c_int, [_vp, _i64p]),
+    "azx_policy_temp_row": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, C.POINTER(C.c_int)]),
 }
 
 class TrainConfig(C.Structure):

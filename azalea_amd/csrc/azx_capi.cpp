@@ -26,6 +26,7 @@
 #include "playout_cap.h"
 #include "gumbel.h"
 #include "fpu.h"
+#include "policy_temp.h"
 #include "resign.h"
 #include "rollout_kernels.h"
 #include "selfplay_openings.h"
@@ -148,6 +149,8 @@ struct azx_engine {
     bool ext_failed = false;
     // rollout evaluator (azx_set_rollout_evaluator): takes ext_fn's place at the evaluation points while ro_R > 0
     int ro_R = 0;
+    // policy temperature as azx_set_policy_temp left it (d.pt_* are the values in force: pt_refresh)
+    int pt_eighths = 8, pt_root_eighths = 8;
     uint64_t ro_seed = 0;
     int64_t ro_handovers = 0, ro_rows = 0;
     unsigned long long *ro_won = nullptr;       // device: rollouts won by the mover (one add per row)
@@ -312,6 +315,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     d.noise_scale = 0.0;
     d.exploration_depth = cfg->exploration_depth;
     d.temperature = (float)cfg->temperature;
+    d.pt_eighths = d.pt_root_eighths = 8;
     e->num_batches = cfg->simulations / cfg->search_batch_size + 1;   // mcts.py:268
     e->selects_per_search = e->num_batches * cfg->search_batch_size;
     d.selects_per_search = e->selects_per_search;
@@ -342,6 +346,7 @@ extern "C" int azx_create(const azx_config *cfg, azx_engine **out) {
     A(d.fp_ctr, G * FP_COUNT);
     A(d.gm_ctr, G * GM_COUNT);
     A(d.fpu_ctr, G * FPU_COUNT);
+    A(d.pt_ctr, G * PT_COUNT);
     A(d.gm_state, G * GM_STATE_WORDS);
     A(d.gm_g, G * 2 * AZX_CELL_STRIDE);
     A(e->g_k, G); A(e->g_legal, G * d.ncells); A(e->g_nn, G);
@@ -488,6 +493,7 @@ static DevEngine pool_view(const DevEngine &d, int base, int n, int32_t *n_eval)
     v.fp_ctr += b * FP_COUNT;
     v.gm_ctr += b * GM_COUNT;
     v.fpu_ctr += b * FPU_COUNT;
+    v.pt_ctr += b * PT_COUNT;
     v.gm_state += b * GM_STATE_WORDS;
     v.gm_g += b * 2 * AZX_CELL_STRIDE;
     if (v.row_board) v.row_board += b * nc * AZX_CELL_STRIDE;
@@ -596,7 +602,11 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
         snprintf(play, sizeof play, "%s", fast && !e->no_persistent ? (S == 2 ? "k_play<2> (persistent)" : "k_play<3> (persistent)")
                                                                        : "k_mcts + k_choose + k_advance per move");
     } else {
-        snprintf(tree, sizeof tree, "k_mcts<%d,generic> (BEGIN / APPLY|SELECT / APPLY phases)", S);
+        // (a policy temperature in force takes the phase launches to its own instantiation: azx_launch_mcts)
+        if (d.pt_eighths != 8 || d.pt_root_eighths != 8)
+            snprintf(tree, sizeof tree, "k_mcts_pt<%d> (BEGIN / APPLY|SELECT / APPLY phases)", S);
+        else
+            snprintf(tree, sizeof tree, "k_mcts<%d,generic> (BEGIN / APPLY|SELECT / APPLY phases)", S);
         snprintf(play, sizeof play, "%s", !use_pipeline(e) ? "phases + k_choose + k_advance per move, one stream"
                                           : e->stagger     ? "phases + k_choose + k_advance per move, two half-pools on two streams half an evaluation apart (any tower)"
                                                            : "phases + k_choose + k_advance per move, two half-pools on two streams");
@@ -611,7 +621,9 @@ extern "C" int azx_kernel_info(azx_engine *e, char *buf, int cap) {
                        " reflect=" + ((d.flags & AZX_FLAG_RANDOM_REFLECT) ? "on" : "off") +
                        selfplay_option_fields(e) +
                        (e->ro_R > 0 ? " eval=rollout(" + std::to_string(e->ro_R) + ")" : std::string()) +
-                       "; src=" AZX_SRC_SHA;       // sha256 (16 hex digits) over the kernel sources this library was built from
+                       "; src=" AZX_SRC_SHA +      // sha256 (16 hex digits) over the kernel sources this library was built from
+                       "; temp=" + (e->pt_eighths == 8 && e->pt_root_eighths == 8 ? std::string("off")     // azx_set_policy_temp
+                                    : std::to_string(e->pt_eighths) + "/8," + std::to_string(e->pt_root_eighths) + "/8");
     snprintf(buf, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
 }
@@ -1015,6 +1027,14 @@ static int ext_alloc(azx_engine *e) {
     return AZX_OK;
 }
 
+// The policy temperature in force (azx_set_policy_temp): the rollout evaluator hands every child one table prior, and
+// such rows are untouched by the rule (include/azx.h), so while it is set the launches see (8, 8).
+static void pt_refresh(azx_engine *e) {
+    const bool table = e->ro_R > 0;
+    e->d.pt_eighths = table ? 8 : e->pt_eighths;
+    e->d.pt_root_eighths = table ? 8 : e->pt_root_eighths;
+}
+
 extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *user) {
     if (!e) return fail(AZX_EINVAL, "null engine");
     ENGINE_GUARD(e);
@@ -1025,6 +1045,7 @@ extern "C" int azx_set_external_evaluator(azx_engine *e, azx_eval_fn fn, void *u
     e->ext_fn = fn;
     e->ext_user = fn ? user : nullptr;
     if (fn) e->ro_R = 0;                 // it and azx_set_rollout_evaluator replace each other: the last call wins
+    pt_refresh(e);
     return AZX_OK;
 }
 
@@ -1042,6 +1063,7 @@ extern "C" int azx_set_rollout_evaluator(azx_engine *e, int rollouts, uint64_t s
                                 "with AZX_FLAG_RANDOM_REFLECT");
     if (rollouts == 0) {
         e->ro_R = 0;
+        pt_refresh(e);
         return AZX_OK;
     }
     TRY(ext_alloc(e));
@@ -1053,6 +1075,7 @@ extern "C" int azx_set_rollout_evaluator(azx_engine *e, int rollouts, uint64_t s
     e->ro_handovers = e->ro_rows = 0;
     e->ext_fn = nullptr;
     e->ext_user = nullptr;
+    pt_refresh(e);
     return AZX_OK;
 }
 
@@ -2549,6 +2572,70 @@ extern "C" int azx_fpu_score(int mode, float value, float reduction, float root_
         if (j == 0 || score > best_score) { best = j; best_score = score; }
     }
     *child_out = best;
+    return AZX_OK;
+}
+
+// ---- policy temperature of the search's priors (include/azx.h; NOT the reference's behaviour) ------
+// Like first-play urgency a property of the engine's search: it lives in e->d, in every launch, and is not one of
+// SELFPLAY_OPTIONS.
+static int pt_check(int eighths, int root_eighths) {
+    if (eighths < 1 || eighths > 8)
+        return fail(AZX_EINVAL, "policy temperature: eighths must be in 1..8 (8 is off), got %d", eighths);
+    if (root_eighths < 1 || root_eighths > 8)
+        return fail(AZX_EINVAL, "policy temperature: root_eighths must be in 1..8 (8 is off), got %d", root_eighths);
+    return AZX_OK;
+}
+
+extern "C" int azx_set_policy_temp(azx_engine *e, int eighths, int root_eighths) {
+    if (!e) return fail(AZX_EINVAL, "null engine");
+    TRY(pt_check(eighths, root_eighths));
+    if (!e->phase_api.done())
+        return fail(AZX_ESTATE, "policy temperature: a phase-API search is in flight (finish it with azx_search_step first)");
+    ENGINE_GUARD(e);
+    TRY(zero_game_counters(e, e->d.pt_ctr, PT_COUNT));
+    e->pt_eighths = eighths;
+    e->pt_root_eighths = root_eighths;
+    pt_refresh(e);
+    return AZX_OK;
+}
+
+extern "C" int azx_get_policy_temp(azx_engine *e, int *eighths, int *root_eighths) {
+    if (!e || !eighths || !root_eighths) return fail(AZX_EINVAL, "null argument");
+    *eighths = e->pt_eighths;
+    *root_eighths = e->pt_root_eighths;
+    return AZX_OK;
+}
+
+extern "C" int azx_policy_temp_stats(azx_engine *e, int64_t out4[4]) {
+    if (!e || !out4) return fail(AZX_EINVAL, "null argument");
+    ENGINE_GUARD(e);
+    TRY(sum_game_counters(e, e->d.pt_ctr, PT_COUNT, out4, 4));
+    out4[3] = 0;
+    return AZX_OK;
+}
+
+// the definition on the host for one row, from the text the kernels compile (policy_temp.h)
+extern "C" int azx_policy_temp_row(int eighths, int k, const float *p_in, float *p_out, int *tempered) {
+#pragma clang fp contract(off)
+    if (k < 1 || k > AZX_CELL_STRIDE || !p_in || !p_out || !tempered)
+        return fail(AZX_EINVAL, "policy temperature row: k must be in 1..%d and the pointers non-null", AZX_CELL_STRIDE);
+    if (eighths < 1 || eighths > 8)
+        return fail(AZX_EINVAL, "policy temperature: eighths must be in 1..8 (8 is off), got %d", eighths);
+    *tempered = 0;
+    bool bad = eighths == 8;
+    for (int j = 0; j < k && !bad; ++j) bad = azx_pt_bad(p_in[j]);
+    uint32_t Z = 0u;
+    if (!bad) {
+        for (int j = 0; j < k; ++j) Z += azx_pt_word(azx_pt_q(p_in[j], eighths));
+        bad = Z == 0u;
+    }
+    if (bad) {
+        if (p_out != p_in) memmove(p_out, p_in, sizeof(float) * (size_t)k);
+        return AZX_OK;
+    }
+    const float Zf = azx_pt_zf(Z);
+    for (int j = 0; j < k; ++j) p_out[j] = azx_pt_q(p_in[j], eighths) / Zf;
+    *tempered = 1;
     return AZX_OK;
 }
 

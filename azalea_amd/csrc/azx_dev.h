@@ -199,7 +199,15 @@ struct DevEngine {
     float fpu_value;            // ABSOLUTE: Q of an unvisited child
     float fpu_red, fpu_root_red;   // REDUCTION: r below the root, r at the root
     unsigned long long *fpu_ctr;   // [G][FPU_COUNT] per game (no atomics), azx_fpu_stats' array; the host sums
+    // policy temperature of the priors (azx_set_policy_temp; NOT the reference's behaviour).  Like first-play urgency a
+    // property of the engine's search, in every launch; (8, 8) is off, the reference's rule (policy_temp.h has the
+    // rule, include/azx.h the definition).  These are the values IN FORCE: (8, 8) while the rollout evaluator is set
+    int32_t pt_eighths;         // exponent, in eighths, of the prior rows an expansion stores
+    int32_t pt_root_eighths;    // exponent, in eighths, of the priors the root select scores with
+    unsigned long long *pt_ctr; // [G][PT_COUNT] per game (no atomics), azx_policy_temp_stats' array; the host sums
 };
+// expansions tempered, rows left as delivered by the guard (expansion or root), searches begun with root_eighths != 8
+enum { PT_TEMPERED = 0, PT_GUARDED, PT_ROOT_SEARCHES, PT_RESERVED, PT_COUNT = 4 };
 // selects made under the option, node levels scored under it with an unvisited child, selects that ended on an unvisited child
 enum { FPU_SELECTS = 0, FPU_LEVELS, FPU_UNVISITED, FPU_RESERVED, FPU_COUNT = 4 };
 // games started, games finished, finished games won by colour 1, plies of finished games counted from the empty board
@@ -239,6 +247,16 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     v += AZX_DPP(0, v, 0x142, 0xa);
     v += AZX_DPP(0, v, 0x143, 0xc);
     return __builtin_amdgcn_readlane(v, 63);
+}
+// the same sum over unsigned words (wraps modulo 2^32 by definition: the policy temperature's Z may pass 2^31)
+__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x111, 0xf);
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x112, 0xf);
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x114, 0xf);
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x118, 0xf);
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x142, 0xa);
+    v += (uint32_t)AZX_DPP(0, (int)v, 0x143, 0xc);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 // unsigned max: 0 is the identity, so bound_ctrl DPP reads need no 'old' operand
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {

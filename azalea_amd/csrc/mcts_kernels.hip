@@ -23,6 +23,7 @@
 #include "playout_cap.h"
 #include "gumbel.h"
 #include "fpu.h"
+#include "policy_temp.h"
 #include "resign.h"
 #include "selfplay_openings.h"
 
@@ -496,7 +497,7 @@ __device__ __forceinline__ void gumbel_top(const float *key, const uint64_t *fro
     }
 }
 
-template <int SLOTS, bool FAST, bool FPU = false>
+template <int SLOTS, bool FAST, bool FPU = false, bool PT = false>
 __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int num_batches, bool stage_tables = true) {
     const int mode = FAST ? (MODE_BEGIN | MODE_INLINE) : mode_arg;
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -585,6 +586,19 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     // of them across the whole launch: profiles/fpu_resources.txt.)
     const int fpu_mode = FPU ? __builtin_amdgcn_readfirstlane(E.fpu_mode) : AZX_FPU_OFF;
     uint32_t c_fpu_lvl = 0, c_fpu_unv = 0;
+    // Policy temperature (azx_set_policy_temp; NOT the reference's behaviour; policy_temp.h has the rule): an expansion
+    // from a prior row stores temper(row, pt_e), the root select scores with R = temper(stored priors, pt_r) (rR, in
+    // registers of its own: rst[].z is written back at the end of the launch and stays the stored prior).  Decided by
+    // the HOST as first-play urgency is: an engine with the option in force launches k_mcts_pt for its phase launches
+    // (the only ones that expand from a row), in which first-play urgency is the wave-uniform branch it is in
+    // k_mcts_fpu; in every other instantiation PT is false, both exponents are the constant 8 and all of this folds
+    // away (profiles/policy_temp_resources.txt).  Under the Gumbel root search the root select reads no prior: pt_r is 8.
+    const int pt_e = PT ? __builtin_amdgcn_readfirstlane(E.pt_eighths) : 8;
+    const int pt_r = (PT && gm_m == 0) ? __builtin_amdgcn_readfirstlane(E.pt_root_eighths) : 8;
+    uint32_t c_pt_exp = 0, c_pt_guard = 0, c_pt_root = 0;
+    float rR[SLOTS];
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) rR[s] = 0.0f;
     if (!FAST && gm_m != 0 && !(mode & MODE_BEGIN)) {
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) gsurv[s] = E.gm_state[(size_t)g * GM_STATE_WORDS + GM_SURV + s];
@@ -807,6 +821,24 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         if (num_nodes + k > E.cap) { status = 1; return false; }   // SearchTreeFull
         const int fc = num_nodes;
         num_nodes += k;
+        // azx_set_policy_temp: the row over the legal cells is tempered as one row (one integer wave reduction); the
+        // guard and Z == 0 leave it as delivered (Z <= 169 * 2^24 < 2^32: an unsigned sum)
+        float pt_zf = 0.0f;
+        if (PT && pt_e != 8 && prior_row && k > 0) {
+            bool bad = false;
+            uint32_t w = 0u;
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s)
+                if (lane_bit(lm[s])) {
+                    const float p = prior_row[s * 64 + lane];
+                    if (azx_pt_bad(p)) bad = true;
+                    else w += azx_pt_word(azx_pt_q(p, pt_e));
+                }
+            const uint32_t Z = wave_sum_u(w);
+            if (__ballot(bad) == 0ull && Z != 0u) { pt_zf = azx_pt_zf(Z); c_pt_exp += 1; }
+            else c_pt_guard += 1;
+        }
+        const bool pt_on = PT && pt_zf != 0.0f;
         if (k > 0) {
             if (!prior_row) {
                 Node nd;
@@ -827,6 +859,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     nd.nv = 0.0f;
                     nd.tv = 0.0f;
                     nd.pp = prior_row ? prior_row[cell] : prior_const;
+                    if (pt_on) nd.pp = azx_pt_q(nd.pp, pt_e) / pt_zf;
                     nd.link = AZX_LINK_UNEVAL;
                     arena[fc + rk] = nd;
                 }
@@ -837,6 +870,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                     if (rempty[s]) {
                         rst[s] = make_float4(0.f, 0.f, prior_row ? prior_row[rcell[s]] : prior_const,
                                              __int_as_float(AZX_LINK_UNEVAL));
+                        if (pt_on) rst[s].z = azx_pt_q(rst[s].z, pt_e) / pt_zf;
                         rkp[s] = keep32 * rst[s].z;
                     }
             }
@@ -953,7 +987,9 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
     }
 
     // =================================== APPLY: expand + backup pending leaves ============
+    bool pt_root_applied = false;      // this launch applied the evaluation of the search's root
     if (!FAST && (mode & MODE_APPLY) && pending > 0 && status == 0) {
+        pt_root_applied = pending_root != 0;
         const size_t lb = (size_t)g * bs;
         for (int i = 0; i < pending; ++i) {
             const int node = E.leaf_node[lb + i];
@@ -983,6 +1019,34 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
         if (!pending_root && status == 0) search_value += np_sum_vals(pending);   // mcts.py:287
         pending = 0;
         pending_root = 0;
+    }
+
+    // azx_set_policy_temp at the root: R = temper(stored priors of the root's children, pt_r), once per launch (the
+    // stored priors of an expanded root do not change inside one).  The search's first launch with an expanded root --
+    // the one that begins it on a carried subtree, else the one that applies the root's evaluation -- counts it.
+    const bool pt_root_first = PT && ((mode & MODE_BEGIN) ? root_link >= 0 : pt_root_applied);
+    if (PT && (mode & MODE_BEGIN) && pt_r != 8) c_pt_root = 1;
+    if (PT && pt_r != 8 && root_link >= 0 && k_root > 0) {
+        bool bad = false;
+        uint32_t w = 0u;
+        float q[SLOTS];
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            q[s] = 0.0f;
+            if (lane_bit(rootrm[s])) {
+                if (azx_pt_bad(rst[s].z)) bad = true;
+                else { q[s] = azx_pt_q(rst[s].z, pt_r); w += azx_pt_word(q[s]); }
+            }
+        }
+        const uint32_t Z = wave_sum_u(w);
+        const bool ok = __ballot(bad) == 0ull && Z != 0u;
+        const float zf = ok ? azx_pt_zf(Z) : 1.0f;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            rR[s] = (ok && lane_bit(rootrm[s])) ? q[s] / zf : rst[s].z;
+            rkp[s] = keep32 * rR[s];
+        }
+        if (!ok && pt_root_first) c_pt_guard += 1;
     }
 
     // =================================== SELECT (+ inline evaluate/expand/backup) =========
@@ -1263,7 +1327,7 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
                 const bool noisy = E.noise_scale != 0.0 && cap_full;
                 float Pn[SLOTS];
 #pragma unroll
-                for (int s = 0; s < RS; ++s) Pn[s] = rst[s].z;
+                for (int s = 0; s < RS; ++s) Pn[s] = (PT && pt_r != 8) ? rR[s] : rst[s].z;
                 if (noisy) {
                     if (FAST || E.device_noise) {
                         // one stream word per (game, move, select): a Weyl sequence from the per-move
@@ -1721,6 +1785,13 @@ __device__ __forceinline__ void mcts_body(const DevEngine &E, int mode_arg, int 
             fc[FPU_LEVELS] += c_fpu_lvl;
             fc[FPU_UNVISITED] += c_fpu_unv;
         }
+        // azx_policy_temp_stats
+        if (PT && (c_pt_exp | c_pt_guard | c_pt_root)) {
+            unsigned long long *pc = E.pt_ctr + (size_t)g * PT_COUNT;
+            pc[PT_TEMPERED] += c_pt_exp;
+            pc[PT_GUARDED] += c_pt_guard;
+            pc[PT_ROOT_SEARCHES] += c_pt_root;
+        }
     }
     // the six per-game tallies, one lane each (as six scalar read-modify-writes the compiler waited
     // for each load in turn: six memory round trips at the end of every launch)
@@ -1741,6 +1812,12 @@ __global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, FAST) void k_mcts(DevEngine
 template <int SLOTS, bool FAST>
 __global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, FAST) void k_mcts_fpu(DevEngine E, int mode_arg, int num_batches) {
     mcts_body<SLOTS, FAST, true>(E, mode_arg, num_batches);
+}
+// the generic search for an engine with a policy temperature in force (azx_set_policy_temp): its phase launches, the
+// ones that expand from prior rows.  First-play urgency is read at run time here, as in k_mcts_fpu.
+template <int SLOTS>
+__global__ __launch_bounds__(64) AZX_MCTS_WPE(SLOTS, false) void k_mcts_pt(DevEngine E, int mode_arg, int num_batches) {
+    mcts_body<SLOTS, false, true, true>(E, mode_arg, num_batches);
 }
 
 // ============================================================================================
@@ -2758,8 +2835,17 @@ bool azx_mcts_fast_path(const DevEngine &E, int mode, bool force_generic) {
 
 // An engine with first-play urgency set (azx_set_fpu) runs the FPU instantiations of the tree kernels; every other
 // launch runs the kernels in which the option does not exist.
+// A policy temperature in force (azx_set_policy_temp) acts where a node is expanded from a prior row and where the root
+// of such a search is scored: the phase launches.  Those run k_mcts_pt; a launch that evaluates inside the kernel
+// (MODE_INLINE: one table prior for all children, which the rule leaves untouched) runs what it ran before.
 void azx_launch_mcts(const DevEngine &E, int mode, int num_batches, hipStream_t st, bool force_generic) {
     const size_t lds = azx_mcts_lds_bytes(E.ncells, E.bs);
+    if ((E.pt_eighths != 8 || E.pt_root_eighths != 8) && !(mode & MODE_INLINE)) {
+#define CALL(S) hipLaunchKernelGGL((k_mcts_pt<S>), dim3(E.G), dim3(64), lds, st, E, mode, num_batches)
+        DISPATCH_SLOTS(E.slots, CALL);
+#undef CALL
+        return;
+    }
     if (E.fpu_mode != AZX_FPU_OFF) {
         if (azx_mcts_fast_path(E, mode, force_generic)) {
 #define CALL(S) hipLaunchKernelGGL((k_mcts_fpu<S, true>), dim3(E.G), dim3(64), lds, st, E, mode, num_batches)

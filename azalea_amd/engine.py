@@ -874,6 +874,46 @@ class Engine:
         that ended on a child with no visit; differs_from_off is not computed and always 0 (include/azx.h)."""
         return self._stats(self.L.azx_fpu_stats, self.FPU_STATS)
 
+    # ---- policy temperature of the search's priors (azx_set_policy_temp; NOT the reference's behaviour) ----
+    def set_policy_temp(self, eighths, root_eighths):
+        """azx_set_policy_temp: a policy temperature of 8 / eighths for the prior rows this engine's searches expand
+        from, and of 8 / root_eighths for the priors the root select scores with; both in 1..8, (8, 8) is off.  It holds
+        in EVERY search this engine runs from now on -- search(), the phase API, play / play_device / replay_fill /
+        play_steps, and as a side of a Match or Tournament (each engine keeps its own setting).  At expansion the
+        children's stored prior is temper(row over the legal cells, eighths); at the root PUCT, the noise mix and forced
+        playouts read temper(stored priors, root_eighths) while the stored priors stay (include/azx.h has the
+        definition bit for bit, DESIGN 7.22 the interactions).  Engines whose evaluator gives one table prior to all
+        children (uniform, hash, rollout) are untouched.  (8, 8), or clear_policy_temp(), is the reference's rule: the
+        same kernels, the same bytes as before.  NOT the reference's behaviour; off by default; outside every parity
+        claim.  Refused (AzxError, AZX_ESTATE) between search_begin and the last search_step.  Zeroes
+        policy_temp_stats().  The option has no default setting: both values are given.  (A setting made here directly
+        is not known to azalea_amd.policy_temp.apply, which remembers what IT last put on the engine -- as fpu.apply
+        does: an engine handed to the policy layers is set through them.)"""
+        for name, v in (("eighths", eighths), ("root_eighths", root_eighths)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 8:
+                raise ValueError("policy_temp: %s must be an integer in 1..8 (8 is off), got %r" % (name, v))
+        check(self.L.azx_set_policy_temp(self.h, int(eighths), int(root_eighths)))
+
+    def clear_policy_temp(self):
+        """set_policy_temp(8, 8): the search reads the evaluator's rows as delivered again, as in the reference."""
+        check(self.L.azx_set_policy_temp(self.h, 8, 8))
+
+    def policy_temp(self):
+        """azx_get_policy_temp: (eighths, root_eighths) as set; (8, 8) when off."""
+        if getattr(self.L, "azx_get_policy_temp", None) is None:        # an older build (tools/lib_bench.py): never set
+            return (8, 8)
+        m, r = C.c_int(8), C.c_int(8)
+        check(self.L.azx_get_policy_temp(self.h, C.byref(m), C.byref(r)))
+        return int(m.value), int(r.value)
+
+    POLICY_TEMP_STATS = ("tempered", "left_as_delivered", "root_searches", "reserved")
+
+    def policy_temp_stats(self):
+        """azx_policy_temp_stats since the last set_policy_temp: dict(tempered, left_as_delivered, root_searches,
+        reserved) -- expansions whose row was tempered, rows the guard (or Z == 0) left as delivered at an expansion or
+        at a root, searches begun whose root select scores with the tempered priors; reserved is 0 (include/azx.h)."""
+        return self._stats(self.L.azx_policy_temp_stats, self.POLICY_TEMP_STATS)
+
     def resign_values(self):
         """azx_resign_value: float32[n_games], the resign statistic of every slot's current root (NaN where the root
         is unevaluated or unvisited), by the device function the move draw uses."""
@@ -1242,6 +1282,20 @@ def fpu_score(mode, nv, tv, prior, nv_p, tv_p, c_puct, is_root=False, value=0.0,
                                    1 if is_root else 0, int(nv.size), float(nv_p), float(tv_p), _p(nv, C.c_float),
                                    _p(tv, C.c_float), _p(prior, C.c_float), float(c_puct), C.byref(out)))
     return int(out.value)
+
+
+def policy_temp_row(eighths, row):
+    """azx_policy_temp_row: temper(row, eighths) by the definition (include/azx.h) on the host, no GPU.  row: a 1-d
+    float32 array of 1..192 priors.  Returns (out, tempered): the float32 row and whether it was changed (False: eighths
+    8, the guard, or Z == 0 -- the row comes back as delivered)."""
+    row = np.ascontiguousarray(row, np.float32)
+    if row.ndim != 1:
+        raise ValueError("policy_temp_row: row must be a 1-d array")
+    out = np.empty_like(row)
+    flag = C.c_int(0)
+    check(_lib.lib().azx_policy_temp_row(int(eighths), int(row.size), _p(row, C.c_float), _p(out, C.c_float),
+                                         C.byref(flag)))
+    return out, bool(flag.value)
 
 
 def rollout_value(seed, board, rollouts):

@@ -25,6 +25,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 from . import fpu as _fpu
+from . import policy_temp as _ptemp
 from .play_game import play_game
 
 Pair = Tuple[int, int]
@@ -119,6 +120,7 @@ def evaluate_batched(agents, num_rounds: int, *, game_max_length: int = 300) -> 
                           evaluator=_eng.EVAL_RESNET, num_blocks=pol.num_blocks, base_chans=pol.base_chans,
                           device=(dev.index or 0) if dev.type == "cuda" else 0)
         _fpu.apply(eng, _fpu.policy_fpu(pol))                  # first-play urgency, if the policy carries it
+        _ptemp.apply(eng, _ptemp.policy_policy_temp(pol))      # and its policy temperature
         pol.net.eval()
         sd = {k: v for k, v in pol.net.state_dict().items() if v.dtype == torch.float32}
         if dev.type == "cuda":
@@ -262,7 +264,9 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
     A policy attribute `fpu` (Policy.set_fpu, config["fpu"]; first-play urgency, Engine.set_fpu: NOT the reference's
     behaviour, off by default, OUTSIDE every parity claim) is honoured per agent, pooled or not: it is a property of an
     engine's search, not a self-play option, so a match between the same weights with and without it is two agents that
-    differ in that attribute.
+    differ in that attribute.  A policy attribute `policy_temp` (Policy.set_policy_temp, config["policy_temp"]; the
+    policy temperature of the search's priors, Engine.set_policy_temp: NOT the reference's behaviour, off by default,
+    OUTSIDE every parity claim) is honoured per agent in the same way.
     `gumbel`: refused.  The Gumbel root search (Engine.set_gumbel, Player(gumbel=...)) is a self-play option; device
     matches and tournaments search and draw every ply as the reference does.  Anything but None / False / 0 is a
     ValueError, before any engine is made."""
@@ -321,6 +325,7 @@ def evaluate_throughput(agents, num_rounds: int, *, n_slots=None, seed: int = 0,
                               flags=flags[a], seed=((int(seed) << 8) + a) << 32)
             engines.append(eng)
             _fpu.apply(eng, _fpu.policy_fpu(pol))              # first-play urgency, per agent, if its policy carries it
+            _ptemp.apply(eng, _ptemp.policy_policy_temp(pol))  # and its policy temperature
             if hasattr(pol.net, "eval"):
                 pol.net.eval()
             if external:

@@ -30,6 +30,7 @@ import torch
 from . import distributed as azdist
 from . import engine as _eng
 from . import fpu as _fpu
+from . import policy_temp as _ptemp
 from .game.hex import HexGameState
 from .play_game import play_game
 from .policy import Policy, SearchTreeFull, external_evaluator, tower_flags  # noqa: F401
@@ -82,7 +83,8 @@ class Player:
     def __init__(self, pool, agents: Sequence, *, n_games: int = None, gather: bool = True, role: str = None,
                  external_batch: bool = False, device_match: bool = False, random_reflect: bool = False,
                  openings=None, playout_cap=None, resign=None, early_stop=False, train_targets=None,
-                 forced_playouts=None, gumbel=None, selfplay_openings=None, selfplay_opening_weights=None, fpu=None):
+                 forced_playouts=None, gumbel=None, selfplay_openings=None, selfplay_opening_weights=None, fpu=None,
+                 policy_temp=None):
         """`gather`: under torch.distributed every rank plays its share of a read and all ranks get all rows.
         `role`: None -- every rank calls read() itself, in lock-step (symmetric); "leader" / "follower" -- the
         training-time topology (azalea_amd/distributed.py: rank 0 announces each shared production and broadcasts
@@ -177,8 +179,16 @@ class Player:
         of the SEARCH, not a self-play option: it is put on every agent's Policy (Policy.set_fpu) and from there on every
         engine built for it -- device self-play, external_batch, BOTH engines of device_match, and the host loop's
         single-game engines.  None leaves each policy's own setting (config["fpu"], Policy.set_fpu) as it is.  A
-        ValueError for anything normalize_fpu refuses.  DESIGN 7.20 has what was and was not measured."""
+        ValueError for anything normalize_fpu refuses.  DESIGN 7.20 has what was and was not measured.
+        `policy_temp` (NOT the reference's behaviour, which searches with the evaluator's prior rows as delivered; off
+        by default): a policy temperature for the search's priors, anything
+        azalea_amd.policy_temp.normalize_policy_temp takes -- an int m (the rows a search expands from at temperature
+        8 / m), an (eighths, root_eighths) tuple or a dict with those keys.  Like `fpu` it is a property of the SEARCH,
+        not a self-play option: it is put on every agent's Policy (Policy.set_policy_temp) and from there on every
+        engine built for it.  None leaves each policy's own setting as it is.  A ValueError for anything
+        normalize_policy_temp refuses.  DESIGN 7.22 has what was and was not measured."""
         self.fpu = _fpu.normalize_fpu(fpu)
+        self.policy_temp = _ptemp.normalize_policy_temp(policy_temp)
         if role not in (None, "leader", "follower"):
             raise ValueError("Player role must be None, 'leader' or 'follower'")
         self.openings = [[int(m) for m in o] for o in ([] if openings is None else openings)]
@@ -190,6 +200,10 @@ class Player:
             for a in agents:
                 if hasattr(getattr(a, "policy", None), "set_fpu"):
                     a.policy.set_fpu(self.fpu)
+        if self.policy_temp is not None:
+            for a in agents:
+                if hasattr(getattr(a, "policy", None), "set_policy_temp"):
+                    a.policy.set_policy_temp(self.policy_temp)
         self.running = True
         self.gather = gather
         self.external_batch = bool(external_batch)
@@ -537,6 +551,7 @@ class Player:
                 opt.apply(self._engine, getattr(self, opt.name))
             self._engine_key = key
         _fpu.apply(self._engine, _fpu.policy_fpu(pol))          # a property of the search, not one of OPTIONS
+        _ptemp.apply(self._engine, _ptemp.policy_policy_temp(pol))   # likewise
         return self._engine
 
     def _produce_on_device(self, pol: Policy, want: int) -> None:
@@ -588,6 +603,7 @@ class Player:
                            flags=self._engine_flags | tower_flags(pol),
                            seed=(2 * (int(self._seed_base) & 0x3FFFFFFF) + which) << 32)
         _fpu.apply(eng, _fpu.policy_fpu(pol))
+        _ptemp.apply(eng, _ptemp.policy_policy_temp(pol))
         return eng
 
     def _produce_match(self, pols) -> None:

@@ -13,6 +13,7 @@ import torch
 
 from . import engine as _eng
 from . import fpu as _fpu
+from . import policy_temp as _ptemp
 from .utils import import_and_get
 
 
@@ -119,6 +120,7 @@ class Policy:
         self._weights_version = None
         self.keep_reference_arena = True   # never-free arena + moving root, like the reference
         self.fpu = None               # first-play urgency (set_fpu): None = off, the reference's rule
+        self.policy_temp = None       # policy temperature of the search's priors (set_policy_temp): None = off
 
     # ---- construction / persistence (policy.py:36-63, :85-130, :181-208) ------------------
     def initialize(self, config):
@@ -135,6 +137,7 @@ class Policy:
         if "seed" in config:
             self.seed(config["seed"])
         self.set_fpu(config.get("fpu"))
+        self.set_policy_temp(config.get("policy_temp"))
 
     def set_fpu(self, fpu=True):
         """First-play urgency for every search made for this policy (Engine.set_fpu; include/azx.h has the definition):
@@ -147,6 +150,19 @@ class Policy:
         customary values as the author recalls them and are not checked here.  NOT the reference's behaviour; off by
         default; outside every parity claim."""
         self.fpu = _fpu.normalize_fpu(fpu)
+
+    def set_policy_temp(self, policy_temp):
+        """A policy temperature for the priors of every search made for this policy (Engine.set_policy_temp;
+        include/azx.h has the definition): the rows a search expands from are raised to the power eighths / 8 and
+        renormalised (temperature 8 / eighths), and the root select scores with the stored priors raised to
+        root_eighths / 8.  `policy_temp`: anything azalea_amd.policy_temp.normalize_policy_temp takes -- an int m (=
+        (m, 8)), an (eighths, root_eighths) tuple, a dict with those keys, or None / False / (8, 8) for off.  Also set
+        by config["policy_temp"] and by Player(policy_temp=...).  It is honoured wherever an engine is built for the
+        policy: choose_action (the single-game path behind play_game and evaluate), Player's engines,
+        evaluate_batched, evaluate_throughput's matches and tournaments.  It is a setting of the search, not of the
+        network: checkpoints do not carry it.  NOT the reference's behaviour; off by default; outside every parity
+        claim."""
+        self.policy_temp = _ptemp.normalize_policy_temp(policy_temp)
 
     @property
     def net(self):
@@ -243,6 +259,7 @@ class Policy:
             self._engine_moves = None
             self._weights_version = None
         _fpu.apply(self._engine, _fpu.policy_fpu(self))
+        _ptemp.apply(self._engine, _ptemp.policy_policy_temp(self))
         return self._engine
 
     def _sync_weights(self, eng):

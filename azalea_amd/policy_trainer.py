@@ -407,9 +407,21 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     with it; an absent key leaves the policy's own setting alone.  The defaults are lc0's / KataGo's customary values
     as the author recalls them and are not checked here.  One log line says whether it is on.  A ValueError, before
     anything is built, for anything azalea_amd.fpu.normalize_fpu refuses.  DESIGN 7.20 has what was and was not
-    measured."""
+    measured.
+
+    config["policy_temp"] = m, (eighths, root_eighths) or a dict with those keys, each in 1..8 (default absent; NOT the
+    reference's behaviour, and outside every parity claim): a policy temperature for the search's priors -- every search
+    made for the trained policy expands its nodes from the network's rows raised to the power eighths / 8 and
+    renormalised (temperature 8 / eighths), and scores at the root with the stored priors raised to root_eighths / 8
+    (Engine.set_policy_temp, include/azx.h has the definition).  Like config["fpu"] it is a property of the search, not
+    one of the self-play options above: it is put on the policy (Policy.set_policy_temp), so the self-play Player's
+    engines and every later evaluation of that policy object play with it; an absent key leaves the policy's own
+    setting alone.  Checkpoints do not carry it.  One log line says whether it is on.  A ValueError, before anything is
+    built, for anything azalea_amd.policy_temp.normalize_policy_temp refuses.  Its effect on training is NOT measured
+    (DESIGN 7.22)."""
     from .selfplay_options import from_config
     from . import fpu as _fpu
+    from . import policy_temp as _ptemp
     option_keywords, option_lines = from_config(config, policy)
     if "fpu" in config:
         try:
@@ -420,6 +432,15 @@ def train(policy, config, rundir, *, replaybuf=None, device_replay: bool = False
     option_lines = list(option_lines) + [
         "first-play urgency (config['fpu']): %s" % ("off" if policy_fpu is None else
             "on -- NOT the reference's behaviour: mode %s, value %g, reduction %g, root reduction %g" % policy_fpu)]
+    if "policy_temp" in config:
+        try:
+            policy.policy_temp = _ptemp.normalize_policy_temp(config["policy_temp"])
+        except ValueError as exc:
+            raise ValueError("config['policy_temp']: %s" % exc) from None
+    policy_ptemp = _ptemp.policy_policy_temp(policy)
+    option_lines = list(option_lines) + [
+        "policy temperature (config['policy_temp']): %s" % ("off" if policy_ptemp is None else
+            "on -- NOT the reference's behaviour: eighths %d, root eighths %d" % policy_ptemp)]
     apply_selfplay_tower(policy, config)
     os.makedirs("%s/checkpoints" % rundir, exist_ok=True)
     np.random.seed(config["seed"])

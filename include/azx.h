@@ -1152,6 +1152,69 @@ int azx_fpu_stats(azx_engine *e, int64_t out4[4]);
 int azx_fpu_score(int mode, float value, float reduction, float root_reduction, int is_root, int k, float nv_p, float tv_p,
                   const float *nv, const float *tv, const float *prior, float c_puct, int32_t *child_out);
 
+/* ---- Policy temperature for the search's priors ---------------------------------------------------------------------
+ * NOT the reference's behaviour (the search uses the evaluator's prior row as delivered there: search_tree.py:254-274,
+ * and that stays the default); additive, off unless asked for, and outside every parity claim.  Like first-play
+ * urgency a property of the ENGINE'S SEARCH, not a self-play option: it holds in every search the engine runs --
+ * azx_search, the phase API, throughput self-play, matches and tournaments (each engine with its own setting).
+ *
+ * azx_set_policy_temp(e, eighths, root_eighths): both in 1..8; (8, 8) is off, the default.  The temperature is 8 / m:
+ * m = 7, 6, 5, 4 give 1.14, 1.33, 1.6, 2.  The exponent is restricted to eighths so that P^(m/8) is a product of IEEE
+ * square roots, exact on the device and on the host alike (a powf or logf is not).
+ *
+ * THE DEFINITION (the tree kernels, azx_policy_temp_row and the tests' restatement are held to it bit for bit;
+ * csrc/policy_temp.h is the one text the kernels and the host compile).  One row operation, temper(P[0..k), m):
+ *   1. Each step is one float32 operation, unfused.  The square root and the divide are IEEE's.
+ *   2. If m = 8, the row is returned as it is.
+ *   3. GUARD.  If any P_j is not finite, is below 0 or is above 1, the row is returned as delivered.
+ *   4. s1 = sqrtf(P_j), s2 = sqrtf(s1), s3 = sqrtf(s2).
+ *   5. q_j is the left-to-right product of those s whose bit of m is set: bit 2 selects s1, bit 1 s2, bit 0 s3.
+ *   6. Z is the sum over j of (uint32_t)(q_j * 16777216.0f), taken as an integer so that no lane order can change a bit.
+ *   7. If Z == 0, the row is returned as delivered.
+ *   8. Zf = (float)Z * (1.0f / 16777216.0f).
+ *   9. The result is q_j / Zf.
+ * The row sums stay within k * 2^-24 of 1 up to the rounding of the k divides.
+ * A row the guard hands on is searched as the search of before searches it (the reference refuses a prior row with a
+ * negative or NaN entry, mcts.py:211-213, and so does the registered device evaluator's hand-over; azx_put_evals does
+ * not).  PUCT over non-finite priors is arithmetic on NaN and infinity, with one thing to know: below the root a node
+ * whose children have no visit yet takes its first child unscored -- every score is -0 + 0 while the priors are
+ * finite -- so a NaN or an infinite prior is first scored at the node's second visit.
+ * Where the rule acts:
+ *   AT EXPANSION.  When a node is expanded from a prior row (the network or an external evaluator), the children's
+ *     stored prior_prob is temper(row over the legal cells, eighths).  Expansions with ONE TABLE PRIOR for all children
+ *     are untouched -- tempering a constant row is the identity -- and so is the whole search of such an engine, the
+ *     root included: the uniform and hash evaluators and the rollout evaluator run the kernels and produce the bytes of
+ *     before this addition, whatever is set, and count nothing.
+ *   AT THE ROOT.  The root select scores with R = temper(stored priors of the root's children, root_eighths) in place
+ *     of the stored priors: the noise mix ((1 - eps) * R + eps * noise) and forced playouts' (k * Ps) * S read R.  The
+ *     stored priors are not rewritten, so a carried subtree stays consistent.
+ *   EVERYTHING ELSE reads the stored prior: first-play urgency's visited mass, the Gumbel root search's ln P, the
+ *     recorded rows, azx_get_root, azx_tree_dump.  Under the Gumbel root search root_eighths is unused (and not counted),
+ *     as first-play urgency's root_reduction is.
+ * With the option never set, or set and then set back to (8, 8), every output of the library is the same bytes as
+ * before this addition, from the same kernels.  Not part of this: AlphaZero's visit-dependent c(s) (with c_base near
+ * 2e4 it changes c by about 0.02 at 400 simulations), any change of default.
+ *
+ * azx_set_policy_temp: AZX_EINVAL, leaving the setting in place, for a value outside 1..8; AZX_ESTATE while a phase-API
+ *   search is in flight (between azx_search_begin and the last azx_search_step).  Zeroes azx_policy_temp_stats.
+ * azx_get_policy_temp: the setting as made (also while the rollout evaluator keeps it from acting).
+ * azx_policy_temp_stats: since the last azx_set_policy_temp, summed over the engine's games:
+ *   [0] expansions whose row was tempered;
+ *   [1] rows left as delivered by the guard or by Z == 0: expansions, and root rows (once per search, in the search's
+ *       first launch that finds the root expanded);
+ *   [2] searches begun whose root select scores with R (root_eighths != 8, no Gumbel root search);
+ *   [3] 0.
+ *   So [0] + [1] minus the root rows in [1] is the number of evaluated non-terminal positions expanded with eighths != 8.
+ * azx_policy_temp_row: the definition on the host for ONE row, no GPU: p_out = temper(p_in[0..k), eighths), *tempered =
+ *   1 where the row was changed by steps 4-9 and 0 where it came back as delivered (m = 8, the guard, Z == 0).  p_out
+ *   may be p_in.  AZX_EINVAL for k outside 1..AZX_CELL_STRIDE, null pointers or eighths outside 1..8.
+ * Additions WITHIN ABI revision 7 (azx_version stays 7; azx_config and azx_play_stats are unchanged): callers detect
+ * them by symbol (dlsym azx_set_policy_temp).  azx_kernel_info gains a field at its end, "; temp=off" or "; temp=M/8,R/8". */
+int azx_set_policy_temp(azx_engine *e, int eighths, int root_eighths);
+int azx_get_policy_temp(azx_engine *e, int *eighths, int *root_eighths);
+int azx_policy_temp_stats(azx_engine *e, int64_t out4[4]);
+int azx_policy_temp_row(int eighths, int k, const float *p_in, float *p_out, int *tempered);
+
 /* ---- the training step on the device ---------------------------------------------------------
  * Replaces policy_trainer.supervised_step(train=True) (azalea/policy_trainer.py:123-142: zero_grad, Network.run with
  * compute_loss, backward, optimizer.step) for HexNetwork (network.py:68-102, :120-152) under torch.optim.SGD

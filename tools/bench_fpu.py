@@ -81,15 +81,15 @@ def bench_py(lib, steps):
     return {k: line[k] for k in keep if k in line}
 
 
-def never_set(parent_lib, steps, repeats):
+def never_set(parent_lib, steps, repeats, option="first-play urgency"):
     runs = {"this": [], "parent": []}
     for _ in range(repeats):
         for name, lib in (("this", None), ("parent", parent_lib)):
             runs[name].append(bench_py(lib, steps))
             print("bench.py %s: %r" % (name, runs[name][-1]), file=sys.stderr, flush=True)
-    out = {"command": "python bench.py --gpus 1 --steps %d --warmup 5 --no-config5, first-play urgency never set; this build "
+    out = {"command": "python bench.py --gpus 1 --steps %d --warmup 5 --no-config5, %s never set; this build "
                       "and the parent commit's library (tools/lib_bench.py) alternating in one session, this build first"
-                      % steps, "order": ", ".join(["this, parent"] * repeats)}
+                      % (steps, option), "order": ", ".join(["this, parent"] * repeats)}
     for name, rs in runs.items():
         vs = [r["value"] for r in rs]
         out[name] = {"runs": rs, "median": statistics.median(vs), "min": min(vs), "max": max(vs),

@@ -22,5 +22,6 @@ _lib.OPTIONAL.update(["azx_set_gumbel", "azx_get_gumbel", "azx_gumbel_stats", "a
 _lib.OPTIONAL.update(["azx_set_rollout_evaluator", "azx_rollout_value", "azx_selftest_rollout", "azx_rollout_stats"])
 _lib.OPTIONAL.update(["azx_debug_tower_choice"])
 _lib.OPTIONAL.update(["azx_set_fpu", "azx_get_fpu", "azx_fpu_stats", "azx_fpu_score"])
+_lib.OPTIONAL.update(["azx_set_policy_temp", "azx_get_policy_temp", "azx_policy_temp_stats", "azx_policy_temp_row"])
 sys.argv = ["bench.py"] + sys.argv[2:]
 runpy.run_path(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), run_name="__main__")
